@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Batched-rollout benchmark: entity-steps/s on BASELINE.json's 4096 scenarios x 64 entities x 10k steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One bench "step" = one full pass of the hot path over the batch: sg_rollout of R x E x T
 (reset + T simulated steps, every scenario running to its end) with the scenarios resident in HBM.
 Every rank owns its own R scenarios (weak scaling: replicas are independent); RCCL is
-used only to dispatch the run configuration and to collect the per-replica metric rows.  With N > 1 the
-same run also times BASELINE.json configs[3] read literally (the 4096 scenarios split over the N ranks:
-"strong") and reports it beside the headline.  Prints ONE JSON line on rank 0.
+used only to dispatch the run configuration and to collect the per-replica metric rows.  Prints ONE
+JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, W untimed + K timed steps, the outputs of the
+last timed step (--dump-outputs), the line.  --full adds everything else, after the timed region: the
+oracle check of the final state (--verify), the CPU baseline, the live vector-ALU peak, the other
+single-GPU configs (c2, c5) beside the c3 headline, and with N > 1 the scaling shape `value` is not
+(`weak` = the whole batch per rank beside the default `strong` = the batch split over the ranks,
+BASELINE.json configs[3] read literally, or the reverse) plus the time-sliced strong shard.
 """
 import argparse
 import ctypes
@@ -220,6 +226,54 @@ def timed_passes(one_pass, steps, warmup, dist, sync):
     if dist is not None:
         dist.barrier()
     return time.perf_counter() - t0, ent_steps, stats
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs writes at most (under 64 MB with the .npy headers)
+DUMP_SEED = 20240807    # the sample of scenarios whose state is dumped when the whole state would not fit
+
+
+def dump_outputs(out_dir, rows, events, state):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy (float64; masks float32), every
+    value finite.  metric_<field> [R]: the metric rows; event_<field> [n]: the CollisionMetric events, sorted by (scenario, t,
+    other, type); state_<field>: the final state (poses / vels [R, E, 6] with 0.0 for the entities not in the scene -- state()'s
+    NaN -- which state_present [R, E] marks, dists [R, E], the collision rows split into their 32-bit halves
+    [R, E, (words,) 2] = low, high; t / n_steps / done [R]).  When everything would exceed DUMP_BUDGET, the state arrays hold a
+    fixed, seeded sample of the scenarios, listed in state_scenario_index.  A non-finite value anywhere else is an error."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    names = rows.dtype.names if hasattr(rows, "dtype") else list(rows)
+    for k in names:
+        if k != "reserved":
+            out["metric_" + k] = np.asarray(rows[k], np.float64)
+    if events is not None:
+        order = np.lexsort((events["type"], events["other"], events["t"], events["scenario"]))
+        for k in ("t", "scenario", "other", "type"):
+            out["event_" + k] = np.asarray(events[k][order], np.float64)
+    if state is not None:
+        coll = np.asarray(state["coll"], np.uint64)
+        present = np.asarray(state["present"], bool)
+        st = {"poses": np.where(present[..., None], state["poses"], 0.0).astype(np.float64),
+              "vels": np.where(present[..., None], state["vels"], 0.0).astype(np.float64),
+              "dists": np.asarray(state["dists"], np.float64), "present": present.astype(np.float32),
+              "coll": np.stack([coll & np.uint64(0xFFFFFFFF), coll >> np.uint64(32)], axis=-1).astype(np.float64),
+              "t": np.asarray(state["t"], np.float64), "n_steps": np.asarray(state["n_steps"], np.float64),
+              "done": np.asarray(state["done"], np.float64)}
+        R = len(st["t"])
+        fixed = sum(a.nbytes for a in out.values())
+        per_scenario = sum(a.nbytes for a in st.values()) / R
+        keep = min(R, int((DUMP_BUDGET - fixed - 8 * R) // per_scenario))
+        if keep < R:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(R, max(keep, 1), replace=False))
+            st = {k: a[idx] for k, a in st.items()}
+            st["scenario_index"] = idx.astype(np.float64)
+        out.update({"state_" + k: a for k, a in st.items()})
+    bad = [k for k, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {bad}")
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def collect(elapsed, ent_steps, dist):
@@ -443,7 +497,7 @@ def run_e2e(args):
                                             "Argoverse recordings, with hazard / RSS metrics -- other data, other machine: context, not a ratio"},
             "sample_metrics": all_metrics[0],
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = e2e_cpu_baseline(paths, dt, steps, cores)
         print(json.dumps(line, default=float))
         return line
@@ -502,13 +556,23 @@ def main(argv=None, make_engine=None, emit=True):
                          "the ranks -- BASELINE.json's metric and configs[3] as written: 4096 scenarios x 64 entities at 1 / 2 / 4 / 8 "
                          "GPUs = 512 per GPU at 8; weak = --scenarios per GPU.  With one rank the two are the same batch (reported "
                          "as \"weak\": per-GPU work is what it is).  With N > 1 the other one is timed too and reported under its own key")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, after its timed region: the oracle check (--verify's default), the CPU baseline, "
+                         "the live vector-ALU peak, the other single-GPU configs (c2, c5) with c3, and with N > 1 the other "
+                         "scaling shape and the time-sliced strong shard.  Off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's metric rows, collision "
+                         "events and final state) as DIR/<name>.npy, float64 / float32, at most 64 MB (larger batches: the "
+                         "state of a fixed, seeded sample of scenarios, listed in state_scenario_index.npy)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="c3 on one GPU: do not time the other single-GPU BASELINE configs (c2, c5) after the headline's timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="c3 on one GPU with --full: do not time the other single-GPU BASELINE configs (c2, c5) after the headline's "
+                         "timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--verify", type=int, default=None,
                     help="after the timed passes (outside the timed region) re-run this many scenarios spread over the batch "
                          "through the CPU oracle for the full horizon and compare the final state / metric rows / events bit "
-                         "for bit; a mismatch makes the exit code non-zero.  Default 16 (c5, c3rss: 4); 0 = off")
+                         "for bit; a mismatch makes the exit code non-zero.  Default with --full 16 (c5, c3rss: 4), "
+                         "without it 0 = off")
     ap.add_argument("--engine-factory", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--require-queue", action="store_true",
                     help="exit non-zero (code 4) unless every rank ran the table path as the one persistent launch "
@@ -519,6 +583,10 @@ def main(argv=None, make_engine=None, emit=True):
                     help="c5: SocialForce noise terms (social_force.py:106-114): off = std 0 (parity runs), device = the "
                          "reference's default std with the counter-based device RNG")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.workload == "e2e" and args.dump_outputs:
+        ap.error("--dump-outputs: the e2e pipeline has no single timed step to dump")
     if args.workload == "e2e" and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         raise SystemExit("--workload e2e is a one-GPU pipeline (its host side is the bottleneck); run one per GPU instead")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and make_engine is None:
@@ -598,7 +666,7 @@ def main(argv=None, make_engine=None, emit=True):
         def sync():
             pass
 
-    n_verify = args.verify if args.verify is not None else (4 if (crowd or wl.get("rss")) else 16)
+    n_verify = args.verify if args.verify is not None else ((4 if (crowd or wl.get("rss")) else 16) if args.full else 0)
 
     def verify(eng, K):
         """NOT timed: the state the last timed pass left against the CPU oracle, full horizon, K scenarios of this rank."""
@@ -616,15 +684,16 @@ def main(argv=None, make_engine=None, emit=True):
                      "oracle/sgym_oracle.c run over the full horizon, bit for bit")
         return v
 
-    def measure(R, sliced=None):
-        pipes, kernels = [], []
+    def measure(R, sliced=None, dump=None):
+        pipes, kernels, last = [], [], {}
         first = rank * R  # rank r owns scenarios [r R, (r + 1) R) of the seeded family (chunk-aligned: R % 64 == 0 or 1 rank)
         eng = make_engine(R, first) if sliced is None else make_engine(R, first, sliced)
 
         def one_pass():
             eng.rollout_async(T, do_reset=True)
             eng.synchronize()
-            rows, _ = eng.metrics()
+            rows, last["events"] = eng.metrics()
+            last["rows"] = rows
             # collection: every rank's per-replica metric rows to rank 0 (RCCL gather)
             D.gather_rows(np.stack([rows["ego_avg_speed"], rows["ego_max_speed"], rows["ego_distance_travelled"],
                                     rows["n_collisions"].astype(np.float64), rows["n_steps"].astype(np.float64)],
@@ -636,6 +705,8 @@ def main(argv=None, make_engine=None, emit=True):
             return int(rows["n_steps"].sum()) * E, (eng.last_kernel_ms(), n_launch, launch_ms, gross)
 
         elapsed, ent_steps, stats = timed_passes(one_pass, args.steps, args.warmup, dist, sync)
+        if dump and rank == 0:
+            dump_outputs(dump, last["rows"], last["events"], eng.state() if hasattr(eng, "state") else None)
         ver = None
         if n_verify > 0 and getattr(eng, "_bench_packed", None) is not None:
             ver = verify(eng, max(2, -(-n_verify // world)))
@@ -652,14 +723,14 @@ def main(argv=None, make_engine=None, emit=True):
         return dict(elapsed=worst, total=total, per_rank=per_rank, ent_steps=ent_steps, stats=stats, R=R, verified=ver,
                     sched=None if sched is None else sched.tolist(), kernel=kernels[-1] if kernels else None)
 
-    main_run = measure(shapes[args.scaling])
+    main_run = measure(shapes[args.scaling], dump=args.dump_outputs)
     other_run = None
-    if world > 1:
+    if world > 1 and args.full:
         other = "strong" if args.scaling == "weak" else "weak"
         other_run = (other, measure(shapes[other]))
 
     sliced_run = None
-    if world > 1 and live and args.workload == "c3":
+    if world > 1 and live and args.workload == "c3" and args.full:
         # BASELINE.json configs[3] read literally leaves each GPU a shard that cannot fill it (512 wavefronts on 1024 SIMDs);
         # the time-sliced path (workload c3s: its own accounting, final state + metrics + events) is what such a shard should
         # run through: timed beside the step-materialised figure, never instead of it
@@ -688,7 +759,7 @@ def main(argv=None, make_engine=None, emit=True):
         hbm = committed_profile(args.workload, "hbm_traffic", R, E, T)
         traffic = hbm["hbm_bytes_per_rollout"] / launches_per_rollout if hbm else None
         sq = committed_profile(args.workload, "pmc_sq", R, E)
-        peak = valu_peak(local_rank) if live else None
+        peak = valu_peak(local_rank) if live and args.full else None  # (a micro-benchmark run of its own)
         secondary = None
         if sq and peak:
             EP = E if E > 64 else max(4, 1 << (E - 1).bit_length())
@@ -852,15 +923,15 @@ def main(argv=None, make_engine=None, emit=True):
             line["degraded"] = "a rank ran the table path as chunk launches instead of the persistent launch (roofline.schedule)"
         # which engine produced the line (a stand-in injected by the CPU tests must never pass for the HIP library)
         line["engine"] = "scenario_gym_amd.RolloutEngine (libsgym_hip.so)" if live else (args.engine_factory or "injected stand-in (tests)")
-        if live and not args.no_cpu_baseline:  # (rank 0 only, after the timed region; the other ranks wait at the teardown)
+        if live and args.full and not args.no_cpu_baseline:  # (rank 0 only, after the timed region; the other ranks wait at the teardown)
             line["cpu_baseline"] = cpu_baseline(dict(E=E, T=T, dt=dt, ego_kind=ego_kind, crowd=crowd, rss=bool(wl.get("rss")), roads=bool(wl.get("roads"))))
-        if (live and world == 1 and args.workload == "c3" and not args.no_configs and emit
+        if (live and args.full and world == 1 and args.workload == "c3" and not args.no_configs and emit
                 and (R, E, T) == (WORKLOADS["c3"]["R"], WORKLOADS["c3"]["E"], 10000) and args.ego == "pid"):
             # the driver times ONE line: the other single-GPU BASELINE configs ride in it, each measured
             # the same way after the headline's timed region -- 3 timed passes, oracle-verified, its own roofline
             line["configs"] = {}
             for name in ("c2", "c5"):
-                sub = main(["--workload", name, "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], emit=False)
+                sub = main(["--workload", name, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], emit=False)
                 rf = sub["roofline"]
                 line["configs"][name] = {
                     "value": sub["value"], "unit": sub["unit"], "ms_per_step": sub["ms_per_step"], "steps": sub["steps"],

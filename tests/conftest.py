@@ -45,6 +45,26 @@ def scenario_arrays(g, prefix):
     )
 
 
+# the reference's own test inputs (scenarios, catalogs, road networks), tests/golden/make_golden_inputs.py
+INPUT_FIXTURES = ("inputs_xosc", "inputs_roads_1", "inputs_roads_2")
+
+
+@pytest.fixture(scope="session")
+def reference_inputs(tmp_path_factory):
+    """Directory holding the reference's test inputs in their original layout -- Scenarios/, Catalogs/, Road_Networks/ (the
+    scenarios name their catalogs and networks by relative paths) -- unpacked from the input fixtures."""
+    import lzma
+
+    root = tmp_path_factory.mktemp("input_files")
+    for name in INPUT_FIXTURES:
+        with np.load(os.path.join(GOLDEN, name + ".npz")) as g:
+            for rel in g.files:
+                path = root / rel
+                path.parent.mkdir(parents=True, exist_ok=True)
+                path.write_bytes(lzma.decompress(g[rel].tobytes()))
+    return str(root)
+
+
 @pytest.fixture(scope="session")
 def oracle():
     from oracle import oracle as O

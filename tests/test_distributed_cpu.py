@@ -86,7 +86,7 @@ def _bench_worker(rank, world, port, out_path):
         return _StandInEngine(R, first, 6, 40)
 
     line = bench.main(["--gpus", str(world), "--scenarios", "128", "--entities", "6", "--sim-steps", "40", "--steps", "2",
-                       "--warmup", "1", "--scaling", "strong", "--no-cpu-baseline"], make_engine=make_engine)
+                       "--warmup", "1", "--scaling", "strong", "--no-cpu-baseline", "--full"], make_engine=make_engine)
     assert made == [(64, rank * 64), (128, rank * 128)]  # the strong shape first (it is `value`), then the weak one
     if rank == 0:
         with open(out_path, "w") as f:
@@ -134,7 +134,7 @@ def test_bench_py_starts_its_own_ranks(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scenarios", "128", "--entities", "6",
-                          "--sim-steps", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                          "--sim-steps", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full",
                           "--engine-factory", "tests.standin_engine:make"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -147,3 +147,34 @@ def test_bench_py_starts_its_own_ranks(tmp_path):
     assert line["engine"] == "tests.standin_engine:make"
     ent_steps = 2 * 64 * 6 * 40 * 2
     assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 2 - ent_steps) < 1e-6 * ent_steps
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path, monkeypatch):
+    """A plain `bench.py` run (no --full) does W untimed + K timed passes and nothing else -- no oracle check, no CPU baseline,
+    no second shape -- and --dump-outputs writes what the last timed pass handed back (the metric rows) as float64 .npy files."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SGYM_FORCE_DIST"):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+
+    made = []
+
+    def make_engine(R, first):
+        made.append(_StandInEngine(R, first, 6, 40))
+        return made[-1]
+
+    out = tmp_path / "out"
+    line = bench.main(["--scenarios", "64", "--entities", "6", "--sim-steps", "40", "--steps", "5", "--warmup", "2",
+                       "--dump-outputs", str(out)], make_engine=make_engine, emit=False)
+    assert [e.passes for e in made] == [7]  # one engine, 2 warmup + 5 timed passes
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["verified"] is None
+    assert "cpu_baseline" not in line and "configs" not in line and "strong_sliced" not in line
+    ent_steps = 64 * 6 * 40 * 5
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 5 - ent_steps) < 1e-6 * ent_steps
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(got) == {"metric_ego_avg_speed", "metric_ego_max_speed", "metric_ego_distance_travelled", "metric_n_collisions",
+                        "metric_n_steps"}
+    assert all(a.dtype == np.float64 and a.shape == (64,) and np.isfinite(a).all() for a in got.values())
+    assert np.array_equal(got["metric_ego_max_speed"], 2.0 * np.arange(64)) and np.all(got["metric_n_steps"] == 40)

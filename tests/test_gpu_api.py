@@ -1395,7 +1395,7 @@ def test_bench_two_live_ranks_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(SGYM_DIST_BACKEND="gloo", SGYM_DIST_ONE_DEVICE="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scenarios", "1024", "--sim-steps", "2000",
-                          "--steps", "2", "--warmup", "1", "--verify", "4"], capture_output=True, text=True, timeout=600, env=env,
+                          "--steps", "2", "--warmup", "1", "--verify", "4", "--full"], capture_output=True, text=True, timeout=600, env=env,
                          cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1479,7 +1479,7 @@ def test_bench_line_carries_every_single_gpu_config(tmp_path):
     import sys
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--verify", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--verify", "2", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1494,6 +1494,53 @@ def test_bench_line_carries_every_single_gpu_config(tmp_path):
         assert c["value"] > 0 and c["steps"] == 3 and c["verified"]["equal"] and c["verified"]["steps"] == 10000
         assert 0.0 < c["roofline"]["frac"] <= 1.0 and c["roofline"]["kernel_ms"] > 0 and c["roofline"]["kernel"].startswith("sg::rollout_kernel")
     print(f"c3 {line['value'] / 1e9:.1f} G, c2 {cf['c2']['value'] / 1e9:.2f} G, c5 {cf['c5']['value'] / 1e9:.2f} G")
+
+
+def test_bench_dump_outputs_reproduce_and_are_the_engines(tmp_path):
+    """`bench.py --dump-outputs DIR`: two plain runs with the same arguments write the same files, bit for bit, and what they
+    write is what the library hands a caller of the same rollout (metric rows, events, final state of the same seeded batch)."""
+    import json
+    import subprocess
+    import sys
+
+    import scenario_gym_amd as sga
+    import scenario_gym_amd._lib as L
+    from scenario_gym_amd import synthetic
+
+    R, E, T = 256, 64, 600
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scenarios", str(R), "--sim-steps", str(T),
+                              "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["verified"] is None and "configs" not in line
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == set(b) and all(a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes() for k in a)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+
+    dt = 1.0 / 30.0
+    packed = synthetic.make_batch(R, E, n_steps=T, timestep=dt, ego_kind=L.KIND_AGENT_PID, seed=synthetic.SEED, first_scenario=0)
+    eng = sga.RolloutEngine(R, E, timestep=dt, terminal_conditions=["max_length"], event_capacity=64)
+    eng.set_slicing(False)
+    eng.upload(packed)
+    eng.rollout(T)
+    rows, events = eng.metrics()
+    st = eng.state()
+    eng.close()
+    for k in ("ego_avg_speed", "ego_max_speed", "ego_distance_travelled", "n_steps", "n_collisions"):
+        assert bits_equal(a["metric_" + k], rows[k].astype(np.float64)), k
+    assert len(a["event_t"]) == len(events) and np.array_equal(np.sort(a["event_scenario"]), np.sort(events["scenario"].astype(np.float64)))
+    here = st["present"][..., None]  # (entities not in the scene: NaN in state(), 0.0 in the dump)
+    assert np.array_equal(a["state_present"] != 0, st["present"]) and a["state_poses"].shape == (R, E, 6)
+    assert bits_equal(a["state_poses"], np.where(here, st["poses"], 0.0)) and bits_equal(a["state_vels"], np.where(here, st["vels"], 0.0))
+    assert bits_equal(a["state_dists"], st["dists"])
+    coll = a["state_coll"].astype(np.uint64)
+    assert np.array_equal(coll[..., 0] | (coll[..., 1] << np.uint64(32)), st["coll"])
 
 
 def test_chunk_launch_fallback_is_flagged(tmp_path):

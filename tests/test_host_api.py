@@ -288,8 +288,7 @@ def test_xosc_reader(tmp_path):
         import_scenario(str(tmp_path / "nope.xosc"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tests/input_files"), reason="build container only")
-def test_xosc_reader_on_reference_inputs():
+def test_xosc_reader_on_reference_inputs(reference_inputs):
     """Same knots / boxes / refs as the reference's own import_scenario (exported in the goldens)."""
     import glob
 
@@ -297,13 +296,12 @@ def test_xosc_reader_on_reference_inputs():
 
     g = load_golden("scenarios")
     for n in g["names"]:
-        s = import_scenario(glob.glob(f"/root/reference/tests/input_files/Scenarios/{n}*.xosc")[0])
+        s = import_scenario(glob.glob(os.path.join(reference_inputs, "Scenarios", f"{n}*.xosc"))[0])
         assert np.array_equal(np.concatenate([e.trajectory.data for e in s.entities]), g[f"{n}/scenario/knots"])
         assert [e.ref for e in s.entities] == list(g[f"{n}/scenario/refs"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tests/input_files"), reason="build container only")
-def test_xosc_reader_on_all_reference_inputs():
+def test_xosc_reader_on_all_reference_inputs(reference_inputs):
     """All 23 OpenSCENARIO files of the reference's tests: knots, boxes, catalog types, refs, ego and length read by
     scenario_gym_amd.xosc equal what the reference's own import_scenario produced (all_scenarios.npz)."""
     from scenario_gym_amd.entity import catalog_type_code
@@ -311,7 +309,7 @@ def test_xosc_reader_on_all_reference_inputs():
 
     g = load_golden("all_scenarios")
     for n in g["names"]:
-        s = import_scenario(f"/root/reference/tests/input_files/Scenarios/{n}.xosc")
+        s = import_scenario(os.path.join(reference_inputs, "Scenarios", f"{n}.xosc"))
         assert np.array_equal(np.concatenate([e.trajectory.data for e in s.entities]), g[f"{n}/scenario/knots"]), n
         assert [e.ref for e in s.entities] == list(g[f"{n}/scenario/refs"]), n
         assert np.array_equal([[e.bounding_box.width, e.bounding_box.length, e.bounding_box.center_x, e.bounding_box.center_y]
@@ -320,8 +318,7 @@ def test_xosc_reader_on_all_reference_inputs():
         assert s.entities.index(s.ego) == int(g[f"{n}/scenario/ego"]) and s.length == float(g[f"{n}/scenario/length"]), n
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tests/input_files/Road_Networks"), reason="build container only")
-def test_road_network_reader_on_all_reference_inputs():
+def test_road_network_reader_on_all_reference_inputs(reference_inputs):
     """The six road-network JSON files of the reference's tests: every geometry, its rings and the unions it belongs to
     (driveable / walkable / impenetrable surface, road, intersection, lane, pavement, crossing) as the reference's own
     RoadNetwork.create_from_json composed them (roads.npz)."""
@@ -329,7 +326,7 @@ def test_road_network_reader_on_all_reference_inputs():
 
     g = load_golden("roads")
     for n in g["networks"]:
-        a = RoadNetwork.create_from_json(f"/root/reference/tests/input_files/Road_Networks/{n}.json").polygon_arrays()
+        a = RoadNetwork.create_from_json(os.path.join(reference_inputs, "Road_Networks", f"{n}.json")).polygon_arrays()
 
         def by_id(ids, ring_off, vert_off, verts, layers):
             return {str(i): (int(layers[k]), [verts[vert_off[r]:vert_off[r + 1]].tobytes() for r in range(ring_off[k], ring_off[k + 1])])
@@ -415,40 +412,20 @@ def test_is_stationary():
     assert not is_stationary(a)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/scenario_gym"), reason="build container only")
-def test_route_finder_matches_reference():
+def test_route_finder_matches_reference(reference_inputs):
     """pedestrian/route.py on the Greenwich network (5 pavements, 4 crossings): the connection graph, its node positions
-    and breadth-first routes between random points equal the reference's RouteFinder (imported with the stand-ins; the
-    centre-line interpolation it calls is the stand-in's)."""
-    import subprocess
-    import sys
+    and breadth-first routes between random points equal the reference's RouteFinder (route.npz: its answers, recorded with
+    the stand-ins by tests/golden/make_golden_route.py; the centre-line interpolation it calls is the stand-in's)."""
     import json
 
     from scenario_gym_amd.road_network import RoadNetwork
     from scenario_gym_amd.route import RouteFinder
 
-    path = "/root/reference/tests/input_files/Road_Networks/Greenwich_Road_Network_002.json"
+    g = load_golden("route")
+    path = os.path.join(reference_inputs, "Road_Networks", str(g["network"]) + ".json")
     rf = RouteFinder(RoadNetwork.create_from_json(path))
-    rng = np.random.default_rng(0)
-    lo, hi = np.array([290.0, 288.0]), np.array([591.0, 496.0])
-    queries = rng.uniform(lo, hi, (12, 2, 2))
-    code = f"""
-import sys, json
-sys.dont_write_bytecode = True
-sys.path[:0] = ["{ROOT}/tests/golden/_refstubs", "/root/reference"]
-import numpy as np
-from scenario_gym.road_network import RoadNetwork
-from scenario_gym.pedestrian.route import RouteFinder
-rf = RouteFinder(RoadNetwork.create_from_json("{path}"))
-q = np.array({queries.tolist()})
-routes = [rf.find_route(a, b) for a, b in q]
-print(json.dumps(dict(graph={{str(k): v for k, v in rf.graph.items()}}, idx=rf.node_to_idx,
-                      data={{str(k): list(map(float, v)) for k, v in rf.node_data.items()}},
-                      routes=[None if r is None else r.tolist() for r in routes])))
-"""
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, MPLBACKEND="Agg"))
-    assert out.returncode == 0, out.stderr[-2000:]
-    ref = json.loads(out.stdout.strip().splitlines()[-1])
+    queries = g["queries"]
+    ref = json.loads(str(g["result"]))
     assert rf.node_to_idx == ref["idx"] and len(rf.graph) > 100
     assert {str(k): v for k, v in rf.graph.items()} == ref["graph"]
     for k, v in rf.node_data.items():

@@ -10,9 +10,6 @@ import pytest
 
 from conftest import bits_equal, load_golden
 
-REF_SCEN = "/root/reference/tests/input_files/Scenarios"
-REF_NETS = "/root/reference/tests/input_files/Road_Networks"
-
 
 def _split(d):
     d = json.loads(json.dumps(d))
@@ -30,23 +27,29 @@ def _golden_dict(g, n, key="to_dict"):
     return d
 
 
-def test_scenario_from_dict_to_dict_roundtrip_matches_reference():
+def test_scenario_from_dict_to_dict_roundtrip_matches_reference(reference_inputs):
     """The reference's to_dict of 9 shipped scenarios -> our Scenario.from_dict -> to_dict = what the reference's own
     to_json / from_json / to_dict round trip produced (entity classes by name, an unknown class name falling to Entity and
     losing its type-specific fields, catalogs, properties, files, actions, the road network by path)."""
     from scenario_gym_amd.scenario import Scenario
 
+    nets = os.path.join(reference_inputs, "Road_Networks")
     g = load_golden("json")
     for n in [str(x) for x in g["names"]]:
         d = _golden_dict(g, n)
         rn = d["road_network"]
         if rn is not None:
-            rn["path"] = os.path.join(REF_NETS, rn["name"] + ".json")   # (what to_json(road_network_path=<dir>) wrote)
+            rn["path"] = os.path.join(nets, rn["name"] + ".json")   # (what to_json(road_network_path=<dir>) wrote)
         s = Scenario.from_dict(d)
         assert [type(e).__name__ for e in s.entities] == [str(c) for c in g[f"{n}/roundtrip_classes"]], n
         assert (s.road_network is not None) == bool(g[f"{n}/roundtrip_has_network"]), n
-        got, trajs = _split(s.to_dict(road_network_path=REF_NETS))
+        got, trajs = _split(s.to_dict(road_network_path=nets))
         want = json.loads(str(g[f"{n}/roundtrip"]))
+        if want["road_network"] is not None:
+            # the reference wrote <its network directory>/<name>.json: the same file name, under the directory given here
+            w = want["road_network"]
+            assert got["road_network"]["path"] == os.path.join(nets, w["name"] + ".json") == os.path.join(nets, os.path.basename(w["path"])), n
+            w["path"] = got["road_network"]["path"]
         assert got == want, n
         for i, t in enumerate(trajs):
             assert bits_equal(t, g[f"{n}/traj_{i}"]), (n, i)
@@ -81,25 +84,25 @@ def test_scenario_json_files(tmp_path):
     assert other.road_network is not None
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCEN), reason="build container only")
-def test_xosc_import_to_dict_matches_reference():
+def test_xosc_import_to_dict_matches_reference(reference_inputs):
     """Our import of the reference's .xosc files (native scan and ElementTree reader) -> to_dict = the reference's: catalog
     entries with their group, mass, performance (in the reference's shifted fields), axles, properties and files; FileHeader
     properties; UserDefinedActions; the embedded road network."""
     from scenario_gym_amd.xosc import import_scenario, import_scenario_et
 
+    scen = os.path.join(reference_inputs, "Scenarios")
     g = load_golden("json")
     names = [str(x) for x in g["names"]]
     for n in names:
         want = json.loads(str(g[f"{n}/to_dict"]))
         for imp in (import_scenario, import_scenario_et):
-            s = imp(os.path.join(REF_SCEN, n + ".xosc"))
+            s = imp(os.path.join(scen, n + ".xosc"))
             got, trajs = _split(s.to_dict())
             assert got == want, (n, imp.__name__)
             for i, t in enumerate(trajs):
                 assert bits_equal(t, g[f"{n}/traj_{i}"]), (n, i)
     n = names[0]
-    emb = import_scenario(os.path.join(REF_SCEN, n + ".xosc")).to_dict(road_network_path=None)["road_network"]
+    emb = import_scenario(os.path.join(scen, n + ".xosc")).to_dict(road_network_path=None)["road_network"]
     assert sorted(emb.keys()) == [str(k) for k in g[f"{n}/embedded_keys"]]
     import hashlib
 
@@ -203,12 +206,12 @@ def test_load_scenarios_takes_json_and_xosc(tmp_path):
     assert m[:n] == m[n:]
 
 
-def test_bulk_ingest_equals_object_path(tmp_path, monkeypatch):
+def test_bulk_ingest_equals_object_path(tmp_path, monkeypatch, reference_inputs):
     """packing.load_and_pack: OpenSCENARIO files on the usual path are packed straight from the native scan (no Scenario /
     Entity / Trajectory / Agent objects); SG_INGEST_OBJECTS=1 sends every file through import_scenario + pack_scenarios.
     Same arrays, bit for bit -- generated files (several widths in one batch, a trajectory given out of time order and one
-    without headings, so that the constructor's slow branches run) and, in the build container, every shipped scenario of
-    the reference (road networks, elevation, catalogs of three kinds, files the strict scan hands to the document reader)."""
+    without headings, so that the constructor's slow branches run) and every shipped scenario of the reference (its test
+    inputs: road networks, elevation, catalogs of three kinds, files the strict scan hands to the document reader)."""
     import glob
 
     from scenario_gym_amd import xosc_write as W
@@ -224,11 +227,9 @@ def test_bulk_ingest_equals_object_path(tmp_path, monkeypatch):
         p = os.path.join(root, "Scenarios", f"s{i}.xosc")
         W.write_scenario(p, ents)
         paths.append(p)
-    sets = [paths]
-    ref = sorted(glob.glob("/root/reference/tests/input_files/Scenarios/*.xosc"))
-    if ref:
-        sets.append(ref)
-    for ps in sets:
+    ref = sorted(glob.glob(os.path.join(reference_inputs, "Scenarios", "*.xosc")))
+    assert len(ref) == 23
+    for ps in (paths, ref):
         for relabel in (True, False):
             monkeypatch.delenv("SG_INGEST_OBJECTS", raising=False)
             a = load_and_pack(ps, relabel=relabel)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Usage (on the GPU box): bash tools/profile_round.sh <tag> [bench args, e.g. --workload c5 --steps 1]
-# Produces under gpurun_out/ (copy what is to be judged into profiles/):
+# Produces under $SG_PROFILE_OUT (default profile_out/; copy what is to be judged into profiles/):
 #   <tag>_bench.json         the plain bench line (no profiler attached)
 #   <tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats of the same command
 #   <tag>_hbm_traffic.json   FETCH_SIZE / WRITE_SIZE (separate --pmc passes), summed over the rollout-kernel
@@ -8,22 +8,23 @@
 #   <tag>_pmc_sq.txt/.json   SQ instruction mix per wave-step (tools/pmc_sq.sh)
 #   latest_<workload>_{hbm_traffic,pmc_sq}.json   the same two records under the names bench.py reads from profiles/
 tag=${1:-r01}; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out
-python3 bench.py "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
-cut -c1-300 gpurun_out/${tag}_bench.json
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_trace -o t -- python3 bench.py --no-cpu-baseline --no-configs "$@" > gpurun_out/${tag}_bench_under_trace.log 2>&1
-f=$(find gpurun_out/${tag}_trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" gpurun_out/${tag}_kernel_stats.csv
+out=${SG_PROFILE_OUT:-profile_out}
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp && mkdir -p "$out"
+python3 bench.py "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+cut -c1-300 $out/${tag}_bench.json
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_trace -o t -- python3 bench.py --no-cpu-baseline --no-configs "$@" > $out/${tag}_bench_under_trace.log 2>&1
+f=$(find $out/${tag}_trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $out/${tag}_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $c --output-format csv -d gpurun_out/${tag}_pmc_$c -o p -- python3 bench.py --no-cpu-baseline --no-configs "$@" --steps 1 --warmup 0 > gpurun_out/${tag}_pmc_$c.log 2>&1
+  timeout 600 rocprofv3 --pmc $c --output-format csv -d $out/${tag}_pmc_$c -o p -- python3 bench.py --no-cpu-baseline --no-configs "$@" --steps 1 --warmup 0 > $out/${tag}_pmc_$c.log 2>&1
 done
-python3 - "$tag" <<'PY'
+python3 - "$tag" "$out" <<'PY'
 import csv, glob, json, sys
-tag = sys.argv[1]
-line = json.loads([l for l in open(f"gpurun_out/{tag}_pmc_WRITE_SIZE.log") if l.startswith("{")][-1])
+tag, out_dir = sys.argv[1:3]
+line = json.loads([l for l in open(f"{out_dir}/{tag}_pmc_WRITE_SIZE.log") if l.startswith("{")][-1])
 cfg = line["config"]
 out = {}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    f = glob.glob(f"gpurun_out/{tag}_pmc_{c}/**/*counter_collection.csv", recursive=True)
+    f = glob.glob(f"{out_dir}/{tag}_pmc_{c}/**/*counter_collection.csv", recursive=True)
     out[c] = sum(float(r["Counter_Value"]) for r in csv.DictReader(open(f[0]))
                  if "rollout_kernel" in r["Kernel_Name"] and r["Counter_Name"] == c)
 wl = cfg["name"]
@@ -43,8 +44,8 @@ rec = dict(scenarios=cfg["scenarios_per_gpu"], entities=cfg["entities"], sim_ste
                 "summed over every rollout_kernel dispatch (the reset-only launch included, it is tiny); KB units x1024, "
                 "corrected by the factors measured on a known byte count in this library's access shape "
                 "(profiles/r03_counter_calibration.json: FETCH_SIZE x2.0, WRITE_SIZE x1.0)")
-json.dump(rec, open(f"gpurun_out/{tag}_hbm_traffic.json", "w"), indent=1)
-json.dump(rec, open(f"gpurun_out/latest_{wl}_hbm_traffic.json", "w"), indent=1)  # what bench.py looks for under profiles/
+json.dump(rec, open(f"{out_dir}/{tag}_hbm_traffic.json", "w"), indent=1)
+json.dump(rec, open(f"{out_dir}/latest_{wl}_hbm_traffic.json", "w"), indent=1)  # what bench.py looks for under profiles/
 print(rec)
 PY
 bash tools/pmc_sq.sh "$tag" "$@" | cut -c1-400

@@ -6,7 +6,8 @@ array and byte for byte, with what is committed.  Build container only (needs /r
 
 Prints one line per generator (seconds, arrays identical / arrays) and the total "N / N"; exit code 1 when any array differs
 or a committed array is missing from the regenerated file.  --update copies the regenerated files over the committed ones.
-tests/test_oracle_golden.py::test_fixtures_regenerate_bit_for_bit runs the fast generators through this module.
+The generators run the reference's own code, so this is done by hand, not by the test suite; make_golden_inputs and
+make_golden_route read where the reference is from SG_REFERENCE.
 """
 import argparse
 import os
@@ -27,6 +28,7 @@ GENERATORS = {
     "make_golden_actions": ["actions"],
     "make_golden_all_scenarios": ["all_scenarios"],
     "make_golden_collision_types": ["collision_types"],
+    "make_golden_inputs": ["inputs_xosc", "inputs_roads_1", "inputs_roads_2"],
     "make_golden_json": ["json", "elevation"],
     "make_golden_long": ["long"],
     "make_golden_mixed_peds": ["mixed_peds"],
@@ -34,6 +36,7 @@ GENERATORS = {
     "make_golden_ped_roads": ["ped_roads"],
     "make_golden_random_walk": ["random_walk"],
     "make_golden_roads": ["roads"],
+    "make_golden_route": ["route"],
     "make_golden_rss": ["rss"],
     "make_golden_sensors": ["sensors"],
 }
