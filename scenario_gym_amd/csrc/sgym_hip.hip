@@ -109,7 +109,8 @@ struct sg_handle {
     // first one's code.  A give-up is STICKY: every later call that runs or reads the batch fails with its message until
     // sg_reset / sg_upload start the batch anew (the state is undefined in between).
     char last_kernel[96] = {0};     // sg_last_kernel
-    int q_waves_per_cu[3] = {-1, -1, -1}; // occupancy of rollout_kernel_tabq / _planar / _rss_tabq (slots_of), queried once
+    int q_waves_per_cu[3] = {-1, -1, -1}; // occupancy of rollout_kernel_tabq / _planar / _rss_tabq (slots_of), queried once per G
+    int q_waves_G = 0;                    // ... the tile width they were queried for
     unsigned *q_host = nullptr;
     int q_head = 0, q_count = 0;    // next slot to use; launches not yet looked at
     bool q_failed = false;
@@ -679,6 +680,10 @@ static void forget_queue_failure(sg_handle *h)
 static size_t slots_of(sg_handle *h, bool rss)
 {
     const size_t by_bounds = (size_t)h->n_simd * (size_t)(rss ? SG_WAVES_PER_SIMD : (h->planar ? SG_PLANAR_WAVES : SG_TAB_WAVES));
+    if (h->q_waves_G != h->G) { // (sg_upload widens the tiles of a pedestrian batch: another kernel instance, another occupancy)
+        std::fill(h->q_waves_per_cu, h->q_waves_per_cu + 3, -1);
+        h->q_waves_G = h->G;
+    }
     int &cached = h->q_waves_per_cu[rss ? 2 : (h->planar ? 1 : 0)];
     if (cached < 0) cached = rss ? sgl::rss_tabq_waves_per_cu(h->G) : sgl::tabq_waves_per_cu(h->G, h->planar);
     return cached > 0 ? std::min(by_bounds, (size_t)cached * (size_t)(h->n_simd / 4)) : by_bounds;
@@ -891,11 +896,13 @@ static int launch_rollout(sg_handle *h, int n_steps, int do_reset, int force, co
 }
 // what no fused rollout variant carries (launch_rollout_impl runs these step by step, sg_tick appends the same launches)
 static bool unfused_off_road(const sg_handle *h) { return !h->wide && h->has_ped && (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD); }
-static bool unfused_rss(const sg_handle *h)
+// a call that runs the RSS callback (`rss`) runs it as rss_kernel behind every step: decided by the batch alone, never by
+// rss_fused (sg_tick asks before it sets rss_fused)
+static bool unfused_rss(const sg_handle *h, bool rss)
 {
-    return !h->wide && h->rss_fused && h->WV == 8 && (h->has_ped || (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD));
+    return rss && !h->wide && h->WV == 8 && (h->has_ped || (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD));
 }
-static bool needs_unfused_extras(const sg_handle *h) { return unfused_off_road(h) || unfused_rss(h); }
+static bool needs_unfused_extras(const sg_handle *h) { return unfused_off_road(h) || unfused_rss(h, h->rss_fused); }
 
 static int launch_rollout_impl(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions)
 {
@@ -919,7 +926,7 @@ static int launch_rollout_impl(sg_handle *h, int n_steps, int do_reset, int forc
         // does to `done`, so a condition added afterwards is the same as one in the list); the RSS callback on scenarios of
         // 257..512 entities with pedestrian agents or ego_off_road (rss_kernel, as beyond 512).  A scenario that is done sits
         // the later launches out.  Rare enough combinations not to deserve kernel variants of their own.
-        const bool off_road = unfused_off_road(h), rss = unfused_rss(h);
+        const bool off_road = unfused_off_road(h), rss = unfused_rss(h, h->rss_fused);
         const bool rss_was = h->rss_fused;
         if (rss) h->rss_fused = false;
         h->n_launches = 0;
@@ -1972,11 +1979,14 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
         h->timing_now = false;
         h->n_launches = 0;
         h->launch_ev.clear();
-        h->rss_fused = rss_tick && !unfused_rss(h); // (as launch_rollout_impl: the callback as a launch of its own where no fused variant exists)
+        // (as launch_rollout_impl: the callback as a launch of its own where no fused variant exists -- rss_fused only for a
+        // variant that fills the line-test queue, or rss_lines_kernel would replay what an earlier launch left in it)
+        const bool rss_alone = unfused_rss(h, rss_tick);
+        h->rss_fused = rss_tick && !rss_alone;
         rc = h->wide ? launch_wide(h, 1, 0, 1, h->d_actions) : launch_main(h, 1, 0, 1, h->d_actions, nullptr, false, &ev_next);
         if (!rc && unfused_off_road(h)) // (launch_rollout_impl: the same launches behind the step)
             sg::ego_off_road_kernel<<<dim3((unsigned)((h->R + 63) / 64)), dim3(64), 0, h->stream>>>(h->p);
-        if (!rc && unfused_rss(h))
+        if (!rc && rss_alone)
             sg::rss_kernel<<<dim3((unsigned)h->R), dim3(512), 0, h->stream>>>(h->p, 0, h->d_rss_state, h->d_rss_code, h->d_rss_safe, h->d_rss_seen);
         h->rss_fused = false;
         hipError_t e = hipSuccess;
