@@ -70,7 +70,6 @@ struct sg_handle {
     bool uploaded = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timing_now = true;       // this call records its timing events (calls of >= 16 steps, and every table-path call)
     bool timed = false;
     Params p{};
     ReusePool static_allocs, state_allocs;
@@ -133,7 +132,6 @@ struct sg_handle {
     int32_t tick_layers[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int32_t *d_rss_state = nullptr, *d_rss_code = nullptr; // [NE] sg_rss_update
     int32_t *d_rss_seen = nullptr;                         // [R]
-    bool rss_fused = false;                                // this launch runs the callback inside rollout_kernel_rss
     bool rss_enabled = false;                              // sg_set_rss: RSSDistances runs after every step of sg_rollout / sg_step
     bool ego_first = true;                                 // every scenario's ego is its entity 0
     double *d_rss_safe = nullptr;                          // [NE][2]
@@ -483,51 +481,74 @@ static dim3 tab_grid(const sg_handle *h, const sg::TabGroups &tg)
 
 // the entry point the handle launched last for a step loop (sg_last_kernel): what a kernel trace of the call shows
 static void note_kernel(sg_handle *h, const char *fmt, int a = 0, int b = 0) { snprintf(h->last_kernel, sizeof h->last_kernel, fmt, a, b); }
-// the rollout kernel family of this handle's batch (launchers: sgym_launch.hpp, one object per family)
-static void launch_variant(sg_handle *h, dim3 grid, int n_steps, int do_reset, int force, const double *d_actions,
-                           const double *d_tab, bool use_tab, const sg::TabGroups &tg)
+
+// the rollout kernel families launch_variant launches (launchers: sgym_launch.hpp, one object per family)
+enum class Fam { ROAD_W8, RSS_W8, PED_W8, PLAIN_W8, CROWD, CROWD_RIDERS, RSS_PED, RSS_ROAD, PED, RSS_TAB, RSS, ROAD, TAB, TAB_ROWS, PLAIN };
+
+// the family of a launch for this handle's batch: `rss` the RSS callback inside the kernel (it fills the line-test queue),
+// `tab` the controlled lanes' poses from the pre-pass table (plan_call)
+static Fam pick_family(const sg_handle *h, bool rss, bool tab)
+{
+    const bool ped = h->has_ped, off_road = (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD) != 0;
+    if (h->WV == 8) { // 257..512 entities (the table path never runs at this width)
+        if (!ped && off_road) return Fam::ROAD_W8;
+        if (rss && !ped) return Fam::RSS_W8;
+        return ped ? Fam::PED_W8 : Fam::PLAIN_W8;
+    }
+    if (ped && h->all_ped && h->G == 64 && crowd_road_ok(h) && crowd_allowed(h) && !rss) return Fam::CROWD;
+    if (tab && ped && h->G == 64) return Fam::CROWD_RIDERS;
+    if (ped && rss) return Fam::RSS_PED;
+    if (rss && off_road) return Fam::RSS_ROAD;
+    if (ped) return Fam::PED;
+    if (rss && tab && h->WV == 1) return Fam::RSS_TAB;
+    if (rss) return Fam::RSS;
+    if (off_road) return Fam::ROAD;
+    if (tab && h->WV == 1 && h->n_ctl > 0) return Fam::TAB;
+    return tab ? Fam::TAB_ROWS : Fam::PLAIN;
+}
+
+static void launch_variant(sg_handle *h, Fam fam, dim3 grid, int n_steps, int do_reset, int force, const double *d_actions,
+                           const double *d_tab, const sg::TabGroups &tg)
 {
     const int G = h->G, WV = h->WV;
     const hipStream_t s = h->stream;
     const sgl::RolloutArgs a{&h->p, h->cfg.timestep, n_steps, do_reset, force, d_actions, nullptr};
     const sgl::RolloutArgs at{&h->p, h->cfg.timestep, n_steps, 0, force, nullptr, d_tab}; // table variants never reset
-    if (WV == 8 && !h->has_ped && (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD)) { // 257..512 entities, ego_off_road
-        // (RSSDistances + ego_off_road in one wide rollout: no fused variant at that width -- launch_rollout_impl and sg_tick clear
-        // rss_fused for it and run the callback as a launch of its own behind every step: unfused_rss)
-        note_kernel(h, "sg::rollout_kernel_road<64, 8>");
-        sgl::rollout_road(64, 8, grid, s, a);
-        return;
+    switch (fam) {
+    // 257..512 entities, eight wavefronts: ego_off_road / the RSS callback inside / pedestrian agents / vehicles and replay only
+    case Fam::ROAD_W8: note_kernel(h, "sg::rollout_kernel_road<64, 8>"); sgl::rollout_road(64, 8, grid, s, a); break;
+    case Fam::RSS_W8: note_kernel(h, "sg::rollout_kernel_rss<64, 8>"); sgl::rollout_rss(64, 8, false, grid, s, a); break;
+    case Fam::PED_W8: note_kernel(h, "sg::rollout_kernel<64, 8, true, false>"); sgl::rollout_ped(64, 8, false, grid, s, a); break;
+    case Fam::PLAIN_W8: note_kernel(h, "sg::rollout_kernel<64, 8, false, false>"); sgl::rollout_plain(64, 8, false, grid, s, a); break;
+    case Fam::CROWD: note_kernel(h, h->n_ped_models > 1 ? "sg::rollout_kernel_crowd_models<%d>" : "sg::rollout_kernel_crowd<%d>", WV);
+        sgl::rollout_crowd(WV, false, grid, s, a, h->n_ped_models > 1); break;
+    case Fam::CROWD_RIDERS: note_kernel(h, "sg::rollout_kernel_crowd_riders<%d>", WV); sgl::rollout_crowd(WV, true, grid, s, at); break;
+    case Fam::RSS_PED: note_kernel(h, "sg::rollout_kernel_rss_ped<%d, %d>", std::max(G, 16), WV); sgl::rollout_ped(G, WV, true, grid, s, a); break;
+    case Fam::RSS_ROAD: note_kernel(h, "sg::rollout_kernel_rss_road<%d, %d>", G, WV); sgl::rollout_rss(G, WV, true, grid, s, a); break;
+    case Fam::PED: note_kernel(h, "sg::rollout_kernel<%d, %d, true, false>", std::max(G, 16), WV); sgl::rollout_ped(G, WV, false, grid, s, a); break;
+    case Fam::RSS_TAB: note_kernel(h, "sg::rollout_kernel_rss_tab<%d>", G); sgl::rollout_rss_tab(G, tab_grid(h, tg), s, h->p, h->cfg.timestep, force, tg); break;
+    case Fam::RSS: note_kernel(h, "sg::rollout_kernel_rss<%d, %d>", G, WV); sgl::rollout_rss(G, WV, false, grid, s, a); break;
+    case Fam::ROAD: note_kernel(h, "sg::rollout_kernel_road<%d, %d>", G, WV); sgl::rollout_road(G, WV, grid, s, a); break;
+    case Fam::TAB: note_kernel(h, h->planar ? "sg::rollout_kernel_tab_planar<%d>" : "sg::rollout_kernel_tab<%d>", G);
+        sgl::rollout_tab(G, h->planar, tab_grid(h, tg), s, h->p, h->cfg.timestep, force, tg); break;
+    case Fam::TAB_ROWS: note_kernel(h, "sg::rollout_kernel<%d, %d, false, true>", G, WV); sgl::rollout_plain(G, WV, true, grid, s, at); break;
+    case Fam::PLAIN: note_kernel(h, "sg::rollout_kernel<%d, %d, false, false>", G, WV); sgl::rollout_plain(G, WV, false, grid, s, a); break;
     }
-    if (WV == 8 && h->rss_fused && !h->has_ped) // 257..512 entities: the RSS callback inside the kernel, eight wavefronts
-        note_kernel(h, "sg::rollout_kernel_rss<64, 8>"), sgl::rollout_rss(64, 8, false, grid, s, a);
-    else if (WV == 8 && h->has_ped) // 257..512 entities with pedestrian agents: the general pedestrian variant on eight wavefronts
-        note_kernel(h, "sg::rollout_kernel<64, 8, true, false>"), sgl::rollout_ped(64, 8, false, grid, s, a);
-    else if (WV == 8) // ... vehicles and replay only (launch_rollout never takes the table path at this width)
-        note_kernel(h, "sg::rollout_kernel<64, 8, false, false>"), sgl::rollout_plain(64, 8, false, grid, s, a);
-    else if (h->has_ped && h->all_ped && G == 64 && crowd_road_ok(h) && crowd_allowed(h) && !h->rss_fused)
-        note_kernel(h, h->n_ped_models > 1 ? "sg::rollout_kernel_crowd_models<%d>" : "sg::rollout_kernel_crowd<%d>", WV),
-            sgl::rollout_crowd(WV, false, grid, s, a, h->n_ped_models > 1);
-    else if (use_tab && h->has_ped && G == 64) // (launch_rollout: a crowd with riders, their table is d_tab)
-        note_kernel(h, "sg::rollout_kernel_crowd_riders<%d>", WV), sgl::rollout_crowd(WV, true, grid, s, at);
-    else if (h->has_ped && h->rss_fused)
-        note_kernel(h, "sg::rollout_kernel_rss_ped<%d, %d>", std::max(G, 16), WV), sgl::rollout_ped(G, WV, true, grid, s, a);
-    else if (h->rss_fused && (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD))
-        note_kernel(h, "sg::rollout_kernel_rss_road<%d, %d>", G, WV), sgl::rollout_rss(G, WV, true, grid, s, a);
-    else if (h->has_ped)
-        note_kernel(h, "sg::rollout_kernel<%d, %d, true, false>", std::max(G, 16), WV), sgl::rollout_ped(G, WV, false, grid, s, a);
-    else if (h->rss_fused && use_tab && WV == 1) // (launch_rollout: the controlled lanes' poses come from the pre-pass table)
-        note_kernel(h, "sg::rollout_kernel_rss_tab<%d>", G), sgl::rollout_rss_tab(G, tab_grid(h, tg), s, h->p, h->cfg.timestep, force, tg);
-    else if (h->rss_fused)
-        note_kernel(h, "sg::rollout_kernel_rss<%d, %d>", G, WV), sgl::rollout_rss(G, WV, false, grid, s, a);
-    else if (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD)
-        note_kernel(h, "sg::rollout_kernel_road<%d, %d>", G, WV), sgl::rollout_road(G, WV, grid, s, a);
-    else if (use_tab && WV == 1 && h->n_ctl > 0)
-        note_kernel(h, h->planar ? "sg::rollout_kernel_tab_planar<%d>" : "sg::rollout_kernel_tab<%d>", G), sgl::rollout_tab(G, h->planar, tab_grid(h, tg), s, h->p, h->cfg.timestep, force, tg);
-    else if (use_tab)
-        note_kernel(h, "sg::rollout_kernel<%d, %d, false, true>", G, WV), sgl::rollout_plain(G, WV, true, grid, s, at);
-    else
-        note_kernel(h, "sg::rollout_kernel<%d, %d, false, false>", G, WV), sgl::rollout_plain(G, WV, false, grid, s, a);
 }
+
+// What one call launches, decided by plan_call before anything is launched (the schedules: launch_plan)
+enum Schedule { SCHED_WIDE, SCHED_STEPWISE, SCHED_ONE, SCHED_TAB_DUMMY, SCHED_TAB };
+struct LaunchPlan {
+    Schedule schedule = SCHED_ONE;
+    Fam reset_fam = Fam::PLAIN; // the reset launch (the table path resets with the non-table variant)
+    Fam fam = Fam::PLAIN;       // the step launches
+    bool rss_lines = false;     // the kernel runs the RSS callback and fills the line-test queue: rss_lines_kernel after it
+    bool rss_alone = false;     // rss_kernel after the reset and after every step
+    bool off_road = false;      // ego_off_road_kernel after every step
+    bool riders = false, rss_tab = false;
+    int ctl = sgl::CTL_GENERAL, ctl_metrics = 1; // the controller pre-pass of the table path
+    bool timed = false;         // the call records its timing events
+};
 
 static int get_event(sg_handle *h, size_t idx, hipEvent_t *out)
 {
@@ -540,32 +561,32 @@ static int get_event(sg_handle *h, size_t idx, hipEvent_t *out)
     return SG_OK;
 }
 
-// one rollout_kernel launch on the handle's stream, bracketed by its own pair of timing events
-// (groups: the block groups of a grouped table-variant launch, launch_rollout; else every block runs n_steps on d_tab)
-static int launch_main(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions, const double *d_tab,
-                       bool use_tab, size_t *ev_next, const sg::TabGroups *groups = nullptr)
+// one rollout_kernel launch of family `fam` on the handle's stream, bracketed by its own pair of timing events when the plan is
+// timed (d_tab: a table variant's table; groups: the block groups of a grouped table-variant launch, else every block runs n_steps)
+static int launch_main(sg_handle *h, const LaunchPlan &pl, Fam fam, int n_steps, int do_reset, int force, const double *d_actions,
+                       const double *d_tab, size_t *ev_next, const sg::TabGroups *groups = nullptr)
 {
     const sg::TabGroups tg = groups ? *groups : one_group(h, d_tab, n_steps);
     dim3 grid(h->WV == 1 ? (unsigned)(h->NE / 64) : (unsigned)h->R);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc;
-    if (h->timing_now) {
+    if (pl.timed) {
         if ((rc = get_event(h, *ev_next, &e0)) || (rc = get_event(h, *ev_next + 1, &e1))) return rc;
         HIP_TRY(h, hipEventRecord(e0, h->stream));
     }
-    launch_variant(h, grid, n_steps, do_reset, force, d_actions, d_tab, use_tab, tg);
+    launch_variant(h, fam, grid, n_steps, do_reset, force, d_actions, d_tab, tg);
     HIP_TRY(h, hipGetLastError());
-    if (use_tab && d_tab && h->n_ctl > 0 && h->p.ev_cap > 0 && n_steps > 0) {
+    if (d_tab && h->n_ctl > 0 && h->p.ev_cap > 0 && n_steps > 0) {
         // a controlled ego's pose at an event of this chunk is a row of the chunk's controller table: copied into the event
         // now -- before the event below, which the pre-pass of a later chunk waits for before it reuses the buffer
         sg::event_ego_pose_kernel<<<dim3((unsigned)h->R), dim3(64), 0, h->stream>>>(h->p, tg);
         HIP_TRY(h, hipGetLastError());
     }
-    if (h->rss_fused) { // (launch_variant ran a rollout_kernel_rss* variant)
+    if (pl.rss_lines) { // (launch_variant ran a rollout_kernel_rss* variant)
         sgl::rss_lines(tab_grid(h, tg), h->stream, h->p, tg);
         HIP_TRY(h, hipGetLastError());
     }
-    if (!h->timing_now) return SG_OK;
+    if (!pl.timed) return SG_OK;
     HIP_TRY(h, hipEventRecord(e1, h->stream));
     if (n_steps > 0) { // reset-only launches are not counted as hot-path launches
         h->launch_ev.push_back((int)*ev_next);
@@ -575,10 +596,6 @@ static int launch_main(sg_handle *h, int n_steps, int do_reset, int force, const
     return SG_OK;
 }
 
-// ScenarioGym.rollout / n x step for the whole batch.  Scenarios without pedestrians and with at least
-// SG_TAB_MIN_STEPS steps to do take the two-kernel path: control_kernel integrates the PID / vehicle agents
-// for a chunk of steps on its own stream while rollout_kernel<TAB> consumes the previous chunks' tables -- large batches as
-// two or three pipelines on streams of their own (below).
 // Scenarios of more than 512 entities (sgym_wide.hpp): State.reset / n x ScenarioGym.step as four kernels per step.  Every
 // scenario that may run steps in lockstep (a done scenario sits the step out unless `force`).  The host never waits here: every
 // 64 steps a one-workgroup kernel writes the number of running scenarios into page-locked memory, and rollout() stops
@@ -599,7 +616,13 @@ static int ensure_wide(sg_handle *h) // (the scratch of the multi-kernel step; s
     return SG_OK;
 }
 
-static int launch_wide(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions)
+// RSSDistances.__call__ as a launch of its own (no fused variant carries it: plan_call's rss_alone)
+static void launch_rss_alone(sg_handle *h, int reset) { sg::rss_kernel<<<dim3((unsigned)h->R), dim3(512), 0, h->stream>>>(h->p, reset, h->d_rss_state, h->d_rss_code, h->d_rss_safe, h->d_rss_seen); }
+// the ego_off_road terminal condition behind a step of a variant without it (plan_call's off_road)
+static void launch_off_road(sg_handle *h) { sg::ego_off_road_kernel<<<dim3((unsigned)((h->R + 63) / 64)), dim3(64), 0, h->stream>>>(h->p); }
+
+// (rss: sg_set_rss at this width -- RSSDistances.__call__ as a launch of its own after the reset and after every step)
+static int launch_wide(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions, bool rss)
 {
     const int R = h->R, EP = h->EP;
     int rc = SG_OK;
@@ -614,20 +637,15 @@ static int launch_wide(sg_handle *h, int n_steps, int do_reset, int force, const
         note_kernel(h, "sg::wide_move_kernel + wide_commit_kernel + wide_collide_kernel + wide_finish_kernel");
         sgl::wide_step(ge, gs, h->stream, h->p, h->cfg.timestep, wa, !h->has_ped);
     };
-    // sg_set_rss at this width: RSSDistances.__call__ as a launch of its own after the reset and after every step
-    auto rss = [&](int reset) {
-        if (h->rss_fused)
-            sg::rss_kernel<<<dim3((unsigned)R), dim3(512), 0, h->stream>>>(h->p, reset, h->d_rss_state, h->d_rss_code, h->d_rss_safe, h->d_rss_seen);
-    };
     if (do_reset) {
         one(do_reset == 2 ? 2 : 1, nullptr);
-        rss(do_reset == 2 ? 2 : 1);
+        if (rss) launch_rss_alone(h, do_reset == 2 ? 2 : 1);
         HIP_TRY(h, hipGetLastError());
     }
     const unsigned first_check = h->wide_check;
     for (int k = 0; k < n_steps; ++k) {
         one(0, d_actions ? d_actions + (size_t)k * R * 2 : nullptr);
-        rss(0);
+        if (rss) launch_rss_alone(h, 0);
         if (!force && (k & 63) == 63 && k + 1 < n_steps) { // is anybody still running?
             HIP_TRY(h, hipGetLastError());
             bool nobody = false;
@@ -878,7 +896,6 @@ static int launch_queue(sg_handle *h, int n_steps, int force, const double *d_ac
 }
 
 
-static int launch_rollout_impl(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions);
 // Work of a failed call may still be running on the controller stream and the pipeline streams (the fan-out of the table
 // path joins them into h->stream only at its end): wait for it, so that a later sg_synchronize / sg_upload / table regrow,
 // which look at h->stream alone, never free a buffer a kernel is reading.
@@ -888,214 +905,232 @@ static void drain_streams(sg_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipGetLastError();
 }
-static int launch_rollout(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions)
-{
-    const int rc = launch_rollout_impl(h, n_steps, do_reset, force, d_actions);
-    if (rc) drain_streams(h);
-    return rc;
-}
-// what no fused rollout variant carries (launch_rollout_impl runs these step by step, sg_tick appends the same launches)
-static bool unfused_off_road(const sg_handle *h) { return !h->wide && h->has_ped && (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD); }
-// a call that runs the RSS callback (`rss`) runs it as rss_kernel behind every step: decided by the batch alone, never by
-// rss_fused (sg_tick asks before it sets rss_fused)
-static bool unfused_rss(const sg_handle *h, bool rss)
-{
-    return rss && !h->wide && h->WV == 8 && (h->has_ped || (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD));
-}
-static bool needs_unfused_extras(const sg_handle *h) { return unfused_off_road(h) || unfused_rss(h, h->rss_fused); }
 
-static int launch_rollout_impl(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions)
+// What a call of n_steps steps launches (`rss`: the RSS callback runs inside the rollout kernel, rss_fused_call; `allow_tab`: the
+// table path may be taken).  Pure: no HIP calls, nothing written; the environment is read per call.
+static LaunchPlan plan_call(const sg_handle *h, int n_steps, bool rss, bool allow_tab)
 {
-    if (h->q_failed && do_reset != 1) return fail(h, SG_ERR_HIP, "%s", h->q_msg); // (a give-up is sticky until the batch starts anew)
-    if (do_reset == 1) forget_queue_failure(h); // (State.reset of the whole batch)
-    h->last_schedule = 0;
-    if (h->wide) {
-        h->n_launches = 0;
-        h->launch_ev.clear();
-        h->timing_now = n_steps >= 16;
-        if (h->timing_now) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        const int rcw = launch_wide(h, n_steps, do_reset, force, d_actions);
-        if (rcw) return rcw;
-        if (h->timing_now) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-        h->timed = h->timing_now;
-        return SG_OK;
+    LaunchPlan pl;
+    const bool off_road = (h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD) != 0;
+    if (h->wide) { // RSSDistances.__call__ as a launch of its own after the reset and after every step; timed from 16 steps
+        pl.schedule = SCHED_WIDE;
+        pl.rss_alone = rss;
+        pl.timed = n_steps >= 16;
+        return pl;
     }
-    if (needs_unfused_extras(h)) {
-        // Combinations no fused variant carries go step by step with the missing part as a launch of its own behind every step:
-        // pedestrian agents AND the ego_off_road terminal condition (ego_off_road_kernel: check_terminal is the last thing a step
-        // does to `done`, so a condition added afterwards is the same as one in the list); the RSS callback on scenarios of
-        // 257..512 entities with pedestrian agents or ego_off_road (rss_kernel, as beyond 512).  A scenario that is done sits
-        // the later launches out.  Rare enough combinations not to deserve kernel variants of their own.
-        const bool off_road = unfused_off_road(h), rss = unfused_rss(h, h->rss_fused);
-        const bool rss_was = h->rss_fused;
-        if (rss) h->rss_fused = false;
-        h->n_launches = 0;
-        h->launch_ev.clear();
-        h->timing_now = false;
-        h->timed = false;
-        size_t evn = 0;
-        int rc1 = SG_OK;
-        auto rss_launch = [&](int reset) {
-            sg::rss_kernel<<<dim3((unsigned)h->R), dim3(512), 0, h->stream>>>(h->p, reset, h->d_rss_state, h->d_rss_code, h->d_rss_safe, h->d_rss_seen);
-        };
-        if (do_reset) {
-            rc1 = launch_main(h, 0, do_reset, 0, nullptr, nullptr, false, &evn);
-            if (!rc1 && rss) rss_launch(do_reset == 2 ? 2 : 1);
-        }
-        for (int k = 0; k < n_steps && !rc1; ++k) {
-            rc1 = launch_main(h, 1, 0, force, d_actions ? d_actions + (size_t)k * h->R * 2 : nullptr, nullptr, false, &evn);
-            if (rc1) break;
-            if (off_road) sg::ego_off_road_kernel<<<dim3((unsigned)((h->R + 63) / 64)), dim3(64), 0, h->stream>>>(h->p);
-            if (rss) rss_launch(0);
-        }
-        h->rss_fused = rss_was;
-        if (rc1) return rc1;
-        HIP_TRY(h, hipGetLastError());
-        return SG_OK;
+    // Combinations no fused variant carries go step by step with the missing part as a launch of its own behind every step:
+    // pedestrian agents AND the ego_off_road terminal condition (ego_off_road_kernel: check_terminal is the last thing a step
+    // does to `done`, so a condition added afterwards is the same as one in the list); the RSS callback on scenarios of
+    // 257..512 entities with pedestrian agents or ego_off_road (rss_kernel, as beyond 512).  A scenario that is done sits
+    // the later launches out.  Rare enough combinations not to deserve kernel variants of their own.  Not timed.
+    pl.off_road = h->has_ped && off_road;
+    pl.rss_alone = rss && h->WV == 8 && (h->has_ped || off_road);
+    pl.rss_lines = rss && !pl.rss_alone;
+    if (pl.off_road || pl.rss_alone) {
+        pl.schedule = SCHED_STEPWISE;
+        pl.reset_fam = pl.fam = pick_family(h, pl.rss_lines, false);
+        return pl;
     }
-    const int tab_min = h->tab_min, chunk_steps = std::max(1, h->chunk_steps), no_overlap = !h->overlap;
-    h->n_launches = 0;
-    h->launch_ev.clear();
-    size_t ev_next = 0;
     // the table variant serves SG_TAB_LANES controlled lanes per wavefront; denser batches keep their controllers
     // in the rollout kernel, where they fill the wavefront anyway
     // (a crowd with riders: lanes of other kinds ride the crowd kernel on a pre-pass table; short calls -- the per-tick loop of
     // an RL driver -- keep the general pedestrian variant, like the table path keeps the in-kernel controllers)
-    const bool riders = h->crowd_riders && crowd_road_ok(h) && !h->rss_fused && h->n_ctl > 0 && n_steps >= tab_min;
+    pl.riders = allow_tab && h->crowd_riders && crowd_road_ok(h) && !rss && h->n_ctl > 0 && n_steps >= h->tab_min;
     // (the RSS callback inside the kernel: its controlled lanes ride the table too -- rollout_kernel_rss_tab -- which takes the
     // controller code out of the one variant that has no issue slot to spare; launches stay within the line-test queue)
-    const bool rss_tab = h->rss_fused && h->WV == 1 && !h->has_ped && !(h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD) && h->n_ext == 0 &&
-                         h->n_ctl > 0 && n_steps >= tab_min && env_int("SG_RSS_TAB", 1) != 0;
-    const bool use_tab = riders || rss_tab || (h->WV <= 4 && !h->has_ped && !h->rss_fused && !(h->cfg.terminal_mask & SG_TERM_EGO_OFF_ROAD) && h->n_ext == 0 && n_steps >= tab_min && h->max_ctl_per_block <= SG_TAB_LANES(h->G, h->WV));
+    pl.rss_tab = allow_tab && rss && h->WV == 1 && !h->has_ped && !off_road && h->n_ext == 0 && h->n_ctl > 0 && n_steps >= h->tab_min &&
+                 env_int("SG_RSS_TAB", 1) != 0;
+    const bool use_tab = pl.riders || pl.rss_tab || (allow_tab && h->WV <= 4 && !h->has_ped && !rss && !off_road && h->n_ext == 0 &&
+                                                     n_steps >= h->tab_min && h->max_ctl_per_block <= SG_TAB_LANES(h->G, h->WV));
     // short calls (the per-tick loop of an RL driver) are not timed: four event records cost more than their kernel
-    h->timing_now = use_tab || n_steps >= 16;
-    if (h->timing_now) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    int rc = SG_OK;
-    if (!use_tab && h->rss_fused && n_steps > h->rssq_steps) { // the line-test queues hold rssq_steps steps per launch (ensure_rss)
-        for (int k0 = 0; k0 < n_steps && !rc; k0 += h->rssq_steps)
-            rc = launch_main(h, std::min(h->rssq_steps, n_steps - k0), k0 == 0 ? do_reset : 0, force,
-                             d_actions ? d_actions + (size_t)k0 * h->R * 2 : nullptr, nullptr, false, &ev_next);
-    } else if (!use_tab) {
-        rc = launch_main(h, n_steps, do_reset, force, d_actions, nullptr, false, &ev_next);
-    } else {
-        if (do_reset && (rc = launch_main(h, 0, do_reset, 0, nullptr, nullptr, false, &ev_next))) return rc;
-        if (h->n_ctl == 0) { // nothing to integrate: the table variant reads (and ignores) one dummy row
-            if (!h->d_tab[0]) {
-                HIP_TRY(h, hipMalloc((void **)&h->d_tab[0], 64 * sizeof(double)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_tab[1], 64 * sizeof(double)));
-                h->tab_bytes = 64 * sizeof(double);
-                h->n_tab = 2;
-                HIP_TRY(h, hipMemsetAsync(h->d_tab[0], 0, 64 * sizeof(double), h->stream));
+    pl.timed = use_tab || n_steps >= 16;
+    pl.reset_fam = pick_family(h, rss, false);
+    pl.fam = pick_family(h, rss, use_tab);
+    pl.schedule = !use_tab ? SCHED_ONE : h->n_ctl == 0 ? SCHED_TAB_DUMMY : SCHED_TAB;
+    // the table path's pre-pass: the riders' own; the fast one for the RSS table variant (the ego's metrics are the rollout
+    // kernel's, from its own velocities); else the general one, which keeps the ego's metrics
+    if (pl.riders) pl.ctl = sgl::CTL_RIDERS;
+    else if (pl.rss_tab && env_int("SG_RSS_CTL_FAST", 1) != 0) pl.ctl = sgl::CTL_FAST;
+    pl.ctl_metrics = pl.riders || pl.rss_tab ? 0 : 1;
+    return pl;
+}
+
+// The steps of the table path: one launch on a dummy table without controlled lanes, else the persistent queue launch where it
+// fits, else the chunk launches
+static int launch_table(sg_handle *h, const LaunchPlan &pl, int n_steps, int force, const double *d_actions, size_t *ev_next)
+{
+    if (pl.schedule == SCHED_TAB_DUMMY) { // nothing to integrate: the table variant reads (and ignores) one dummy row
+        if (!h->d_tab[0]) {
+            HIP_TRY(h, hipMalloc((void **)&h->d_tab[0], 64 * sizeof(double)));
+            HIP_TRY(h, hipMalloc((void **)&h->d_tab[1], 64 * sizeof(double)));
+            h->tab_bytes = 64 * sizeof(double);
+            h->n_tab = 2;
+            HIP_TRY(h, hipMemsetAsync(h->d_tab[0], 0, 64 * sizeof(double), h->stream));
+        }
+        return launch_main(h, pl, pl.fam, n_steps, 0, force, nullptr, h->d_tab[0], ev_next);
+    }
+    const bool no_overlap = !h->overlap;
+    const size_t np = (size_t)h->p.n_ctl_pad, row = (size_t)sg::CT_PLANES * sg::CT_W * np; // doubles per step, all planes
+    // chunk length: SG_CHUNK_STEPS, capped so that one table buffer stays under 1 GiB
+    int ch = (int)std::min<size_t>((size_t)std::max(1, h->chunk_steps), std::max<size_t>(1, ((size_t)1 << 27) / row));
+    ch = std::min(ch, n_steps);
+    if (pl.rss_tab) ch = std::min(ch, std::max(1, h->rssq_steps)); // one launch fills at most the line-test queue
+    // one persistent launch (sgym_queue.hpp) where the batch is one wavefront per block and nothing rides along; the
+    // pre-pass role must leave most of the wavefront slots to the rollout
+    int rc = SG_QUEUE_FALLBACK;
+    if (h->queue_mode && h->WV == 1 && !pl.riders && !no_overlap && np / 64 <= std::min((size_t)h->n_simd, slots_of(h, pl.rss_tab)) / 2 /* a
+        SIMD of its own for every pre-pass role, and at least as many rollout wavefronts resident beside them */)
+        rc = launch_queue(h, n_steps, force, d_actions, ch, ev_next, pl.rss_tab);
+    if (rc != SG_QUEUE_FALLBACK) return rc;
+    h->last_schedule = 1;
+    // The chunk launches of rounds 1-4 (crowds with riders, the RSS table variant, tiles of several wavefronts, SG_QUEUE=0):
+    // the pre-pass (its own stream) writes chunk c + 1 into the second table buffer while the rollout kernel reads chunk c
+    const int NB = 2; // table buffers
+    const int ctl_slice = h->ctl_slice; // the pre-pass in launches of ctl_slice steps (its load then moves between SIMDs)
+    if (ch > h->p.tab_steps || (size_t)(h->p.tab_steps + 1) * row * sizeof(double) > h->tab_bytes || NB > h->n_tab) {
+        // grow: tab_steps + 1 rows per lane is part of the table addressing
+        const int ts = std::max(ch, h->p.tab_steps);
+        const size_t need = (size_t)(ts + 1) * row * sizeof(double);
+        if (need > h->tab_bytes || NB > h->n_tab) { // (the buffers outlive sg_upload: the next batch of the same shape reuses them)
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->ctl_stream));
+            for (int b = 0; b < 4; ++b) {
+                if (h->d_tab[b]) HIP_TRY(h, hipFree(h->d_tab[b]));
+                h->d_tab[b] = nullptr;
             }
-            rc = launch_main(h, n_steps, 0, force, nullptr, h->d_tab[0], true, &ev_next);
-        } else {
-            const size_t np = (size_t)h->p.n_ctl_pad, row = (size_t)sg::CT_PLANES * sg::CT_W * np; // doubles per step, all planes
-            // chunk length: SG_CHUNK_STEPS, capped so that one table buffer stays under 1 GiB
-            int ch = (int)std::min<size_t>((size_t)chunk_steps, std::max<size_t>(1, ((size_t)1 << 27) / row));
-            ch = std::min(ch, n_steps);
-            if (rss_tab) ch = std::min(ch, std::max(1, h->rssq_steps)); // one launch fills at most the line-test queue
-            // one persistent launch (sgym_queue.hpp) where the batch is one wavefront per block and nothing rides along; the
-            // pre-pass role must leave most of the wavefront slots to the rollout
-            if (h->queue_mode && h->WV == 1 && !riders && !no_overlap && (size_t)h->p.n_ctl_pad / 64 <= std::min((size_t)h->n_simd, slots_of(h, rss_tab)) / 2 /* a SIMD of
-                its own for every pre-pass role, and at least as many rollout wavefronts resident beside them */) {
-                rc = launch_queue(h, n_steps, force, d_actions, ch, &ev_next, rss_tab);
-                if (rc != SG_QUEUE_FALLBACK) {
-                    if (rc) return rc;
-                    if (h->timing_now) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-                    h->timed = h->timing_now;
-                    return SG_OK;
-                }
-                rc = SG_OK;
+            const size_t bytes = std::max(need, h->tab_bytes);
+            h->tab_bytes = 0;
+            h->n_tab = 0;
+            for (int b = 0; b < NB; ++b) {
+                HIP_TRY(h, hipMalloc((void **)&h->d_tab[b], bytes));
+                poison(h->stream, h->d_tab[b], bytes);
             }
-            h->last_schedule = 1;
-            // The chunk launches of rounds 1-4 (crowds with riders, the RSS table variant, tiles of several wavefronts, SG_QUEUE=0):
-            // the pre-pass (its own stream) writes chunk c + 1 into the second table buffer while the rollout kernel reads chunk c
-            const int NB = 2; // table buffers
-            const int ctl_slice = h->ctl_slice; // the pre-pass in launches of ctl_slice steps (its load then moves between SIMDs)
-            if (ch > h->p.tab_steps || (size_t)(h->p.tab_steps + 1) * row * sizeof(double) > h->tab_bytes || NB > h->n_tab) {
-                // grow: tab_steps + 1 rows per lane is part of the table addressing
-                const int ts = std::max(ch, h->p.tab_steps);
-                const size_t need = (size_t)(ts + 1) * row * sizeof(double);
-                if (need > h->tab_bytes || NB > h->n_tab) { // (the buffers outlive sg_upload: the next batch of the same shape reuses them)
-                    HIP_TRY(h, hipStreamSynchronize(h->stream));
-                    HIP_TRY(h, hipStreamSynchronize(h->ctl_stream));
-                    for (int b = 0; b < 4; ++b) {
-                        if (h->d_tab[b]) HIP_TRY(h, hipFree(h->d_tab[b]));
-                        h->d_tab[b] = nullptr;
-                    }
-                    const size_t bytes = std::max(need, h->tab_bytes);
-                    h->tab_bytes = 0;
-                    h->n_tab = 0;
-                    for (int b = 0; b < NB; ++b) {
-                        HIP_TRY(h, hipMalloc((void **)&h->d_tab[b], bytes));
-                        poison(h->stream, h->d_tab[b], bytes);
-                    }
-                    h->tab_bytes = bytes;
-                    h->n_tab = NB;
-                }
-                h->p.tab_steps = ts;
-            }
-            hipStream_t cs = no_overlap ? h->stream : h->ctl_stream;
-            hipEvent_t e;
-            if (!no_overlap) { // the other streams start after everything queued so far (reset, uploads)
-                if ((rc = get_event(h, ev_next++, &e))) return rc;
-                HIP_TRY(h, hipEventRecord(e, h->stream));
-                HIP_TRY(h, hipStreamWaitEvent(cs, e, 0));
-            }
-            const dim3 cgrid((unsigned)(np / 64));
-            const bool rss_fast = env_int("SG_RSS_CTL_FAST", 1) != 0;
-            // chunks of the time axis: lengths double from two slices up to `ch` -- the rollout kernel cannot start before
-            // the table of its chunk exists, and the pre-pass of the chunks after it (about 0.4x the rollout kernel's time
-            // per step) then always finishes under the rollout kernel
-            std::vector<int> ck0, cn;
-            for (int k0 = 0, n = 0, c = 0; k0 < n_steps; k0 += n, ++c) {
-                n = std::min(std::min(ch, c < 20 ? (2 * h->ctl_slice) << c : ch), n_steps - k0);
-                ck0.push_back(k0);
-                cn.push_back(n);
-            }
-            const int C = (int)cn.size();
-            std::vector<hipEvent_t> ctl_done((size_t)C, nullptr), chunk_done((size_t)C, nullptr);
-            int ctl_issued = 0;
-            auto issue_ctl = [&](int upto) -> int { // the pre-pass of the chunks up to `upto`, each into buffer (chunk mod NB)
-                for (; ctl_issued <= upto && ctl_issued < C; ++ctl_issued) {
-                    const int c = ctl_issued, k0 = ck0[(size_t)c], n = cn[(size_t)c];
-                    double *tab = h->d_tab[c % NB];
-                    if (!no_overlap && c >= NB) // the buffer is free once the rollout is through chunk c - NB
-                        HIP_TRY(h, hipStreamWaitEvent(cs, chunk_done[(size_t)(c - NB)], 0));
-                    for (int s0 = 0; s0 < n; s0 += ctl_slice) {
-                        const int ns = std::min(ctl_slice, n - s0);
-                        if (riders)
-                            sgl::control(sgl::CTL_RIDERS, cgrid, cs, h->p, h->cfg.timestep, ns, c == 0 && s0 == 0, k0 + s0, d_actions, tab, s0, 0);
-                        else if (rss_tab && rss_fast) // (the ego's metrics are the rollout kernel's, from its own velocities)
-                            sgl::control(sgl::CTL_FAST, cgrid, cs, h->p, h->cfg.timestep, ns, c == 0 && s0 == 0, k0 + s0, d_actions, tab, s0, 0);
-                        else
-                            sgl::control(sgl::CTL_GENERAL, cgrid, cs, h->p, h->cfg.timestep, ns, c == 0 && s0 == 0, k0 + s0, d_actions, tab, s0,
-                                         rss_tab ? 0 : 1);
-                    }
-                    HIP_TRY(h, hipGetLastError());
-                    if (!no_overlap) {
-                        const int rc2 = get_event(h, ev_next++, &ctl_done[(size_t)c]);
-                        if (rc2) return rc2;
-                        HIP_TRY(h, hipEventRecord(ctl_done[(size_t)c], cs));
-                    }
-                }
-                return SG_OK;
-            };
-            for (int c = 0; c < C; ++c) {
-                // (chunk c + NB - 1 goes into the buffer of chunk c - 1, whose launches were queued by the previous iteration)
-                if ((rc = issue_ctl(std::min(C - 1, c + NB - 1)))) return rc;
-                const int b = c % NB;
-                const sg::TabGroups tg = one_group(h, h->d_tab[b], cn[(size_t)c]);
-                if (!no_overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream, ctl_done[(size_t)c], 0));
-                if ((rc = launch_main(h, cn[(size_t)c], 0, force, nullptr, h->d_tab[b], true, &ev_next, &tg))) return rc;
-                chunk_done[(size_t)c] = h->ev_pool[ev_next - 1];
+            h->tab_bytes = bytes;
+            h->n_tab = NB;
+        }
+        h->p.tab_steps = ts;
+    }
+    hipStream_t cs = no_overlap ? h->stream : h->ctl_stream;
+    hipEvent_t e;
+    if (!no_overlap) { // the other streams start after everything queued so far (reset, uploads)
+        if ((rc = get_event(h, (*ev_next)++, &e))) return rc;
+        HIP_TRY(h, hipEventRecord(e, h->stream));
+        HIP_TRY(h, hipStreamWaitEvent(cs, e, 0));
+    }
+    const dim3 cgrid((unsigned)(np / 64));
+    // chunks of the time axis: lengths double from two slices up to `ch` -- the rollout kernel cannot start before
+    // the table of its chunk exists, and the pre-pass of the chunks after it (about 0.4x the rollout kernel's time
+    // per step) then always finishes under the rollout kernel
+    std::vector<int> ck0, cn;
+    for (int k0 = 0, n = 0, c = 0; k0 < n_steps; k0 += n, ++c) {
+        n = std::min(std::min(ch, c < 20 ? (2 * h->ctl_slice) << c : ch), n_steps - k0);
+        ck0.push_back(k0);
+        cn.push_back(n);
+    }
+    const int C = (int)cn.size();
+    std::vector<hipEvent_t> ctl_done((size_t)C, nullptr), chunk_done((size_t)C, nullptr);
+    int ctl_issued = 0;
+    auto issue_ctl = [&](int upto) -> int { // the pre-pass of the chunks up to `upto`, each into buffer (chunk mod NB)
+        for (; ctl_issued <= upto && ctl_issued < C; ++ctl_issued) {
+            const int c = ctl_issued, k0 = ck0[(size_t)c], n = cn[(size_t)c];
+            double *tab = h->d_tab[c % NB];
+            if (!no_overlap && c >= NB) // the buffer is free once the rollout is through chunk c - NB
+                HIP_TRY(h, hipStreamWaitEvent(cs, chunk_done[(size_t)(c - NB)], 0));
+            for (int s0 = 0; s0 < n; s0 += ctl_slice)
+                sgl::control(pl.ctl, cgrid, cs, h->p, h->cfg.timestep, std::min(ctl_slice, n - s0), c == 0 && s0 == 0, k0 + s0, d_actions,
+                             tab, s0, pl.ctl_metrics);
+            HIP_TRY(h, hipGetLastError());
+            if (!no_overlap) {
+                const int rc2 = get_event(h, (*ev_next)++, &ctl_done[(size_t)c]);
+                if (rc2) return rc2;
+                HIP_TRY(h, hipEventRecord(ctl_done[(size_t)c], cs));
             }
         }
+        return SG_OK;
+    };
+    for (int c = 0; c < C; ++c) {
+        // (chunk c + NB - 1 goes into the buffer of chunk c - 1, whose launches were queued by the previous iteration)
+        if ((rc = issue_ctl(std::min(C - 1, c + NB - 1)))) return rc;
+        const int b = c % NB;
+        const sg::TabGroups tg = one_group(h, h->d_tab[b], cn[(size_t)c]);
+        if (!no_overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream, ctl_done[(size_t)c], 0));
+        if ((rc = launch_main(h, pl, pl.fam, cn[(size_t)c], 0, force, nullptr, h->d_tab[b], ev_next, &tg))) return rc;
+        chunk_done[(size_t)c] = h->ev_pool[*ev_next - 1];
+    }
+    return SG_OK;
+}
+
+// ScenarioGym.rollout / n x step for the whole batch as `pl` says (every schedule but the time-sliced one).  Scenarios without
+// pedestrians and with at least SG_TAB_MIN_STEPS steps to do take the two-kernel path: control_kernel integrates the PID / vehicle
+// agents for a chunk of steps on its own stream while rollout_kernel<TAB> consumes the previous chunks' tables.  Only the table
+// path synchronises (to grow a buffer): sg_tick, which never takes it, runs this inside its graph capture.
+static int launch_plan(sg_handle *h, const LaunchPlan &pl, int n_steps, int do_reset, int force, const double *d_actions)
+{
+    h->n_launches = 0;
+    h->launch_ev.clear();
+    if (pl.timed) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    size_t ev_next = 0;
+    int rc = SG_OK;
+    switch (pl.schedule) {
+    case SCHED_WIDE: // scenarios of more than 512 entities: the multi-kernel step
+        rc = launch_wide(h, n_steps, do_reset, force, d_actions, pl.rss_alone);
+        break;
+    case SCHED_STEPWISE: // one launch per step, each followed by what no fused variant carries (rss_alone, off_road)
+        h->timed = false;
+        if (do_reset && !(rc = launch_main(h, pl, pl.reset_fam, 0, do_reset, 0, nullptr, nullptr, &ev_next)) && pl.rss_alone)
+            launch_rss_alone(h, do_reset == 2 ? 2 : 1);
+        for (int k = 0; k < n_steps && !rc; ++k) {
+            if ((rc = launch_main(h, pl, pl.fam, 1, 0, force, d_actions ? d_actions + (size_t)k * h->R * 2 : nullptr, nullptr, &ev_next))) break;
+            if (pl.off_road) launch_off_road(h);
+            if (pl.rss_alone) launch_rss_alone(h, 0);
+        }
+        if (!rc) HIP_TRY(h, hipGetLastError());
+        break;
+    case SCHED_ONE: { // one launch for the reset and every step (launches of rssq_steps steps when they fill the line-test queue)
+        const int per = pl.rss_lines ? std::max(1, h->rssq_steps) : n_steps;
+        int k0 = 0;
+        do {
+            rc = launch_main(h, pl, pl.fam, std::min(per, n_steps - k0), k0 == 0 ? do_reset : 0, force,
+                             d_actions ? d_actions + (size_t)k0 * h->R * 2 : nullptr, nullptr, &ev_next);
+        } while (!rc && (k0 += per) < n_steps);
+        break;
+    }
+    case SCHED_TAB_DUMMY:
+    case SCHED_TAB: // the table path (table variants never reset: the reset is a launch of the non-table variant)
+        if (!do_reset || !(rc = launch_main(h, pl, pl.reset_fam, 0, do_reset, 0, nullptr, nullptr, &ev_next)))
+            rc = launch_table(h, pl, n_steps, force, d_actions, &ev_next);
+        break;
     }
     if (rc) return rc;
-    if (h->timing_now) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    h->timed = h->timing_now;
+    if (pl.timed) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    h->timed = pl.timed;
     return SG_OK;
+}
+
+// a call of the C ABI: plan, launch, and after a failure wait for what is still running
+static int launch_rollout(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions, bool rss = false)
+{
+    if (do_reset == 1) forget_queue_failure(h); // (State.reset of the whole batch: until then a give-up is sticky)
+    int rc = h->q_failed ? fail(h, SG_ERR_HIP, "%s", h->q_msg) : SG_OK;
+    if (!rc) {
+        h->last_schedule = 0;
+        rc = launch_plan(h, plan_call(h, n_steps, rss, true), n_steps, do_reset, force, d_actions);
+    }
+    if (rc) drain_streams(h);
+    return rc;
+}
+
+// Does this call hand the RSS callback to its launches (plan_call: inside the rollout kernel, or rss_kernel behind every step)?
+// sg_set_rss on, the ego entity 0 of every scenario, and for `live_only` callers records of this batch from an earlier call.
+// Then the records and the line-test queue are made here, before any graph capture (sg_tick); *fresh: the records are new.
+static int rss_fused_call(sg_handle *h, bool live_only, bool *fused, bool *fresh = nullptr)
+{
+    bool made = false;
+    int rc = SG_OK;
+    *fused = h->rss_enabled && h->ego_first && (!live_only || rss_live(h));
+    if (*fused && !(rc = ensure_rss(h, &made))) rc = ensure_rssq(h);
+    if (fresh) *fresh = made;
+    return rc;
 }
 
 // ScenarioGym.rollout time-sliced (sgym_device.hpp, SliceArgs): the reset launch, the clock, the slices of the time axis
@@ -1221,10 +1256,11 @@ static int launch_sliced(sg_handle *h, int n_steps)
     const double *tab = ctl ? h->d_slice_tab : nullptr;
     h->n_launches = 0;
     h->launch_ev.clear();
-    h->timing_now = true;
+    LaunchPlan reset = plan_call(h, 0, false, false); // State.reset by the batch's variant (not counted as a hot-path launch), timed
+    reset.timed = true;
     size_t ev_next = 0;
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    if ((rc = launch_main(h, 0, 1, 0, nullptr, nullptr, false, &ev_next))) return rc; // State.reset (not counted as a hot-path launch)
+    if ((rc = launch_main(h, reset, reset.reset_fam, 0, 1, 0, nullptr, nullptr, &ev_next))) return rc;
     hipEvent_t e_reset = nullptr;
     if (ctl) { // the pre-pass reads the reset state
         if ((rc = get_event(h, ev_next++, &e_reset))) return rc;
@@ -1793,17 +1829,10 @@ extern "C" int sg_reset(sg_handle *h)
     if (!h) return SG_ERR_INVALID;
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_reset: no scenarios uploaded");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    int rc;
-    if (h->rss_enabled && h->ego_first) {
-        bool fresh = false;
-        if ((rc = ensure_rss(h, &fresh)) || (rc = ensure_rssq(h))) return rc;
-        h->rss_fused = true;
-        rc = launch_rollout(h, 0, 1, 0, nullptr);
-        h->rss_fused = false;
-    } else {
-        rc = launch_rollout(h, 0, 1, 0, nullptr);
-        if (!rc && h->rss_enabled) rc = sg_rss_update(h, 1);
-    }
+    bool fused = false;
+    int rc = rss_fused_call(h, false, &fused);
+    if (!rc) rc = launch_rollout(h, 0, 1, 0, nullptr, fused);
+    if (!rc && h->rss_enabled && !fused) rc = sg_rss_update(h, 1);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SG_OK;
@@ -1817,16 +1846,9 @@ extern "C" int sg_reset_scenarios(sg_handle *h, const uint8_t *mask)
     if (!h->d_reset_mask) HIP_TRY(h, hipMalloc((void **)&h->d_reset_mask, (size_t)h->R));
     HIP_TRY(h, hipMemcpyAsync(h->d_reset_mask, mask, (size_t)h->R, hipMemcpyHostToDevice, h->stream));
     h->p.reset_mask = h->d_reset_mask;
-    int rc;
-    if (h->rss_enabled && h->ego_first && rss_live(h)) { // the flagged scenarios' RSS histories start anew as well
-        bool fresh = false;
-        if ((rc = ensure_rss(h, &fresh)) || (rc = ensure_rssq(h))) return rc;
-        h->rss_fused = true;
-        rc = launch_rollout(h, 0, 2, 0, nullptr);
-        h->rss_fused = false;
-    } else {
-        rc = launch_rollout(h, 0, 2, 0, nullptr);
-    }
+    bool fused = false; // (the flagged scenarios' RSS histories start anew as well)
+    int rc = rss_fused_call(h, true, &fused);
+    if (!rc) rc = launch_rollout(h, 0, 2, 0, nullptr, fused);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SG_OK;
@@ -1888,18 +1910,14 @@ extern "C" int sg_step(sg_handle *h, int32_t n_steps, const double *actions, int
         if (n) HIP_TRY(h, hipMemsetAsync(h->d_actions, 0, n * sizeof(double), h->stream));
         d_act = h->d_actions;
     }
-    int rc = SG_OK;
-    if (h->rss_enabled && h->ego_first && rss_live(h)) {
-        bool fresh = false;
-        if (!(rc = ensure_rss(h, &fresh))) rc = ensure_rssq(h);
-        h->rss_fused = true;
-        if (!rc) rc = launch_rollout(h, n_steps, 0, 1, d_act);
-        h->rss_fused = false;
-    } else if (h->rss_enabled) {
+    bool fused = false;
+    int rc = rss_fused_call(h, true, &fused);
+    if (rc) return rc;
+    if (h->rss_enabled && !fused) { // (no records of this batch yet, or the ego is not entity 0) one step per launch
         for (int k = 0; k < n_steps && !rc; ++k)
             if (!(rc = launch_rollout(h, 1, 0, 1, d_act + (size_t)k * h->R * 2))) rc = sg_rss_update(h, 0);
     } else {
-        rc = launch_rollout(h, n_steps, 0, 1, d_act);
+        rc = launch_rollout(h, n_steps, 0, 1, d_act, fused);
     }
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1960,11 +1978,8 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
     // sg_set_rss: the callback runs after the step, inside the captured launch (like sg_step; without records of a reset --
     // the callback was switched on after sg_upload -- through sg_rss_update after the graph)
     if (h->wide && (rc = ensure_wide(h))) return rc;
-    const bool rss_tick = h->rss_enabled && h->ego_first && rss_live(h);
-    if (rss_tick) { // (allocations stay outside the capture)
-        bool fresh = false;
-        if ((rc = ensure_rss(h, &fresh)) || (rc = ensure_rssq(h))) return rc;
-    }
+    bool rss_tick = false; // (allocations stay outside the capture)
+    if ((rc = rss_fused_call(h, true, &rss_tick))) return rc;
     const bool same = h->tick_exec && h->tick_gen == h->generation && h->tick_w == width && h->tick_h == height &&
                       h->tick_rss == rss_tick && h->tick_nw == nw && h->tick_nh == nh && h->tick_nl == n_layers &&
                       std::equal(layers, layers + n_layers, h->tick_layers);
@@ -1975,20 +1990,8 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
         HIP_TRY(h, hipMemcpy(dl, layers, (size_t)n_layers * sizeof(int32_t), hipMemcpyHostToDevice));
         hipGraph_t graph = nullptr;
         HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        size_t ev_next = 0;
-        h->timing_now = false;
-        h->n_launches = 0;
-        h->launch_ev.clear();
-        // (as launch_rollout_impl: the callback as a launch of its own where no fused variant exists -- rss_fused only for a
-        // variant that fills the line-test queue, or rss_lines_kernel would replay what an earlier launch left in it)
-        const bool rss_alone = unfused_rss(h, rss_tick);
-        h->rss_fused = rss_tick && !rss_alone;
-        rc = h->wide ? launch_wide(h, 1, 0, 1, h->d_actions) : launch_main(h, 1, 0, 1, h->d_actions, nullptr, false, &ev_next);
-        if (!rc && unfused_off_road(h)) // (launch_rollout_impl: the same launches behind the step)
-            sg::ego_off_road_kernel<<<dim3((unsigned)((h->R + 63) / 64)), dim3(64), 0, h->stream>>>(h->p);
-        if (!rc && rss_alone)
-            sg::rss_kernel<<<dim3((unsigned)h->R), dim3(512), 0, h->stream>>>(h->p, 0, h->d_rss_state, h->d_rss_code, h->d_rss_safe, h->d_rss_seen);
-        h->rss_fused = false;
+        // the step as sg_step runs it, never on the table path (one step: not timed); launch_plan does not synchronise
+        rc = launch_plan(h, plan_call(h, 1, rss_tick, false), 1, 0, 1, h->d_actions);
         hipError_t e = hipSuccess;
         if (!rc && h->wide) {
             // scenarios of more than 512 entities: the entity layers tile by tile (raster_kernel), empty surfaces (no road
@@ -2063,26 +2066,19 @@ extern "C" int sg_rollout_async(sg_handle *h, int32_t max_steps, int32_t do_rese
                                      "use sg_set_external_poses + sg_step tick by tick", h->n_ext);
     if (max_steps < 0) return fail(h, SG_ERR_INVALID, "sg_rollout: max_steps < 0");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (h->rss_enabled && h->ego_first) {
-        // the callback inside the rollout kernel (rollout_kernel_rss): after the reset and after every step of ONE launch
-        bool fresh = false;
-        int rc = ensure_rss(h, &fresh);
-        if (!rc) rc = ensure_rssq(h);
-        if (rc) return rc;
-        h->rss_fused = true;
-        rc = launch_rollout(h, max_steps, do_reset || fresh ? 1 : 0, 0, nullptr);
-        h->rss_fused = false;
-        return rc;
-    }
+    // the callback inside the rollout kernel (rollout_kernel_rss): after the reset and after every step of ONE launch
+    bool fused = false, fresh = false;
+    int rc = rss_fused_call(h, false, &fused, &fresh);
+    if (rc) return rc;
+    if (fused) return launch_rollout(h, max_steps, do_reset || fresh ? 1 : 0, 0, nullptr, true);
     if (h->rss_enabled) { // (sg_rss_update reports why not: the ego is not entity 0) one step per launch
-        int rc = SG_OK;
         if (do_reset && ((rc = launch_rollout(h, 0, 1, 0, nullptr)) || (rc = sg_rss_update(h, 1)))) return rc;
         for (int k = 0; k < max_steps; ++k)
             if ((rc = launch_rollout(h, 1, 0, 0, nullptr)) || (rc = sg_rss_update(h, 0))) return rc;
         return SG_OK;
     }
     if (do_reset && slicing_pays(h, max_steps)) {
-        const int rc = launch_sliced(h, max_steps);
+        rc = launch_sliced(h, max_steps);
         if (rc != SG_SLICE_FALLBACK) return rc;
     }
     // external-action slots are fed (0, 0) here; drive them with sg_step(actions)

@@ -1,5 +1,6 @@
-"""Every rollout kernel family the dispatcher can pick (launch_variant / launch_queue / launch_sliced / launch_wide in
-csrc/sgym_hip.hip), reached on purpose through each host entry point that can reach it, and checked against the CPU oracle.
+"""Every rollout kernel family the dispatcher can pick (plan_call / pick_family in csrc/sgym_hip.hip; launched by
+launch_variant / launch_queue / launch_sliced / launch_wide), reached on purpose through each host entry point that can reach
+it, and checked against the CPU oracle.
 
 VARIANTS is a plain table: a batch recipe, the knobs that steer the dispatcher to the family, the entry point
 (sg_rollout, sg_step with actions, sg_tick) and the exact sg_last_kernel() string.  Each GPU row asserts the name and
