@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 5 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel */
+#define SG_ABI_VERSION 6 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points */
 
 typedef enum {
     SG_OK = 0,
@@ -370,6 +370,30 @@ int sg_raster_map(sg_handle *h, double width, double height, int32_t nw, int32_t
  * observation call (sg_raster_*, sg_future_collision) or sg_destroy. */
 int sg_raster_map_device(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
                          const int32_t *layers, const uint8_t **d_out);
+
+/* State.get_road_info_at_entity (state/state.py:330-338) for every entity slot of the batch at its current pose: the
+ * geometries x of the scenario's network with x.boundary.contains(Point(pose[:2])) -- strictly inside the polygon's exterior
+ * ring and outside its holes; a point on one of its rings is not contained.  Every polygon of sg_road_networks answers for
+ * itself, whatever its SG_LAYER_* bits (zero included); the answer is exact for the fp64 coordinates given.  Per slot
+ * i = scenario * n_entities + slot:
+ *   count[i]       how many geometries contain the entity (it may exceed cap); -1 for a slot that is not in State.poses
+ *                  (padding, vanished, not spawned yet: the reference raises KeyError); 0 in a scenario without a network
+ *                  (the reference returns ([], [])) and on a handle without sg_set_road_networks
+ *   geoms[i][cap]  their indices in ascending order, -1 behind the last: the polygon's position within its own network
+ *                  (polygon poly_off[n] is index 0 of network n).  May be NULL; `cap` is ignored then
+ *   layers[i]      the OR of the SG_LAYER_* bits of ALL containing polygons, those beyond cap too.  May be NULL
+ * outputs_device == 0: HOST buffers, synchronous.  Otherwise all three are DEVICE pointers; the kernel is queued on
+ * sg_stream(h) behind the handle's pending work and the call does not wait (valid after sg_synchronize).
+ * SG_ERR_INVALID: count NULL, cap < 0.  One lookup in the cell grid of sg_set_road_networks per entity: the cell lists the
+ * polygons covering it and the polygons whose boundary crosses it, and only the latter are tested, on their edges there. */
+int sg_road_info(sg_handle *h, int32_t cap, int32_t *count, int32_t *geoms, uint32_t *layers, int32_t outputs_device);
+
+/* RoadNetwork.get_geometries_at_point (road_network/road_network.py:375-407) for n points: point k = (xy[k][0], xy[k][1])
+ * against the network of scenario scenario_of_point[k].  count [n], geoms [n][cap], layers [n] as above (count is never
+ * -1 here; a point with a NaN coordinate is in nothing).  HOST arrays, synchronous.  SG_ERR_INVALID: n < 0, count NULL,
+ * cap < 0, xy or scenario_of_point NULL with n > 0, a scenario index outside [0, n_scenarios). */
+int sg_road_info_points(sg_handle *h, int64_t n, const int32_t *scenario_of_point, const double *xy, int32_t cap, int32_t *count,
+                        int32_t *geoms, uint32_t *layers);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

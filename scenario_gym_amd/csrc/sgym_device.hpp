@@ -42,6 +42,7 @@
 #include "sgym_core.hpp"
 #include "sgym_agents.hpp"
 #include "sgym_road.hpp"
+#include "sgym_geom.hpp"
 #include "sgym_crowd.hpp"
 #include "sgym_collide.hpp"
 #include "sgym_grid.hpp"

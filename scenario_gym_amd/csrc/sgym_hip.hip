@@ -148,6 +148,9 @@ struct sg_handle {
     std::vector<void *> road_allocs;                   // sg_set_road_networks
     sg::RoadIndex road{};                              // host copy of the device pointers (raster kernels take it by value)
     bool has_road = false;
+    sg::RoadGeom geom{};                               // ... and of the per-geometry lists beside it (sg_road_info; arrays in road_allocs)
+    void *ri_buf = nullptr;                            // device scratch of sg_road_info / sg_road_info_points (grown on demand)
+    size_t ri_cap = 0;
     int ped_serial = 0;                                // env SG_PED_SERIAL: pedestrian pair loop one pedestrian per lane
     int ctl_slice = 64;                                // steps per control_kernel launch (env SG_CTL_SLICE)
     int n_launches = 0;           // rollout_kernel launches of the last call
@@ -424,6 +427,7 @@ extern "C" int sg_destroy(sg_handle *h)
     if (h->pin_sd) (void)hipHostFree(h->pin_sd);
     if (h->pin_ev) (void)hipHostFree(h->pin_ev);
     if (h->obs_buf) (void)hipFree(h->obs_buf);
+    if (h->ri_buf) (void)hipFree(h->ri_buf);
     if (h->d_reset_mask) (void)hipFree(h->d_reset_mask);
     if (h->d_term_flags) (void)hipFree(h->d_term_flags);
     if (h->d_rss_state) (void)hipFree(h->d_rss_state);
@@ -1473,6 +1477,7 @@ extern "C" int sg_upload(sg_handle *h, const sg_scenarios *sc)
     h->p.rssq = nullptr; h->p.rssq_n = nullptr;
     h->has_road = false;
     h->road = sg::RoadIndex{};
+    h->geom = sg::RoadGeom{};
     h->uploaded = false; // (the controller table buffers stay: launch_rollout regrows them when the new batch needs more)
     h->ego_first = true;
     ++h->generation;
@@ -2523,6 +2528,11 @@ struct RoadBuild {
     std::vector<uint32_t> net_flags;   // bit 0: walkable surface has area, bit 1: impenetrable surface has area
     std::vector<int64_t> imp_off;      // per network: range of imp_edges
     std::vector<double> imp_edges;     // the ring edges of the impenetrable polygons, polygon by polygon
+    // sg::RoadGeom (sgym_geom.hpp): per cell the polygons that cover it or touch it, by name
+    std::vector<uint32_t> ref_off, ref;
+    std::vector<sg::RoadCand> xcand;   // candidates of the polygons without layer bits (the layer index above skips them)
+    std::vector<int32_t> xcand_edges;
+    std::vector<int32_t> poly0;
 };
 
 int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
@@ -2555,11 +2565,14 @@ int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
     B.imp_off.push_back((int64_t)B.imp_edges.size() / 4);
     sg::RoadNet N{};
     N.cell_base = (int64_t)B.cells.size();
+    const int64_t gq0 = (int64_t)B.poly_layers.size() - (q1 - q0);
+    B.poly0.push_back((int32_t)gq0);
     if (!(lo[0] <= hi[0])) { // no geometry: an empty 1 x 1 grid
         N.x0 = N.y0 = 0.0; N.inv_cell = 1.0; N.nx = N.ny = 1;
         B.nets.push_back(N);
         B.cells.push_back(0);
         B.cell_off.push_back((uint32_t)B.cand.size());
+        B.ref_off.push_back((uint32_t)B.ref.size());
         return 0;
     }
     double c = 1.0; // cell side: 1 m unless the network is so large that this would take more than 2^21 cells
@@ -2574,16 +2587,20 @@ int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
     B.cells.resize((size_t)N.cell_base + ncell, 0);
     uint16_t *cells = B.cells.data() + N.cell_base;
     struct Entry { uint32_t cell; sg::RoadCand cd; };
-    std::vector<Entry> entries; // candidates of this network, sorted by cell below
+    std::vector<Entry> entries, xentries; // candidates of this network (x: of its polygons without layer bits), sorted by cell below
+    struct GRef { uint32_t cell; int32_t poly; uint32_t code; };
+    std::vector<GRef> grefs;    // the per-geometry lists of this network's cells (sg::RoadGeom), sorted by (cell, polygon) below
     auto cix = [&](double x, double x0, int nmax) { return std::max(0, std::min(nmax - 1, (int)std::floor((x - x0) / c))); };
     std::vector<uint8_t> touched;
     std::vector<std::pair<uint32_t, int32_t>> hits; // (local cell, edge) of one polygon
-    const int64_t gq0 = (int64_t)B.poly_layers.size() - (q1 - q0);
     for (int64_t q = q0; q < q1; ++q) {
         const int64_t gq = gq0 + (q - q0);
         const int64_t e0 = B.poly_edge_off[gq], e1 = B.poly_edge_off[gq + 1];
         const uint32_t L = B.poly_layers[gq] & 0xffu;
-        if (e1 <= e0 || !L) continue;
+        if (e1 <= e0) continue;
+        // (a polygon without layer bits changes nothing the layer kernels read: its candidates go to xcand, and L = 0 leaves
+        // the cell words as they are)
+        std::vector<int32_t> &edge_lists = L ? B.cand_edges : B.xcand_edges;
         double plo[2] = {INFINITY, INFINITY}, phi[2] = {-INFINITY, -INFINITY};
         for (int64_t i = e0; i < e1; ++i)
             for (int c2 = 0; c2 < 2; ++c2) { plo[c2] = std::min(plo[c2], B.edges[4 * i + c2]); phi[c2] = std::max(phi[c2], B.edges[4 * i + c2]); }
@@ -2620,7 +2637,7 @@ int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
             const int ix = (int)(cell % (uint32_t)N.nx), iy = (int)(cell / (uint32_t)N.nx);
             sg::RoadCand cd{};
             cd.poly = (int32_t)gq;
-            cd.edge_off = (uint32_t)B.cand_edges.size();
+            cd.edge_off = (uint32_t)edge_lists.size();
             if (b - a > 65535) return -1;
             cd.n_edges = (uint16_t)(b - a);
             int loc = 2;
@@ -2632,9 +2649,9 @@ int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
             }
             if (loc == 2) return -2; // every reference point of the cell lies on this polygon's boundary
             cd.ref_inside = (uint8_t)(loc == 1);
-            for (size_t k = a; k < b; ++k) B.cand_edges.push_back(hits[k].second);
+            for (size_t k = a; k < b; ++k) edge_lists.push_back(hits[k].second);
             cells[cell] |= (uint16_t)(L << 8);
-            entries.push_back({cell, cd});
+            (L ? entries : xentries).push_back({cell, cd});
             a = b;
         }
         for (int iy = iy0; iy <= iy1; ++iy) {
@@ -2648,17 +2665,37 @@ int build_road_network(const sg_road_networks *in, int n, RoadBuild &B)
                         inside = sg::rn_polygon_locate(B.edges.data(), e0, e1, N.x0 + (ix + 0.5) * c, N.y0 + (iy + 0.5) * c) == 1;
                         known = true;
                     }
-                    if (inside) cells[cell] |= (uint16_t)L;
+                    if (inside) {
+                        cells[cell] |= (uint16_t)L;
+                        grefs.push_back({cell, (int32_t)gq, (uint32_t)sg::RG_FULL << sg::RG_SHIFT | (uint32_t)gq});
+                    }
                 }
             }
         }
     }
     std::stable_sort(entries.begin(), entries.end(), [](const Entry &x, const Entry &y) { return x.cell < y.cell; });
+    std::stable_sort(xentries.begin(), xentries.end(), [](const Entry &x, const Entry &y) { return x.cell < y.cell; });
     // CSR (global over all networks: cell_off has one entry per cell + a final one appended by the caller)
-    size_t k = 0;
+    size_t k = 0, kx = 0;
     for (size_t cell = 0; cell < ncell; ++cell) {
         B.cell_off.push_back((uint32_t)B.cand.size());
-        while (k < entries.size() && entries[k].cell == cell) B.cand.push_back(entries[k++].cd);
+        while (k < entries.size() && entries[k].cell == cell) {
+            grefs.push_back({(uint32_t)cell, entries[k].cd.poly, (uint32_t)sg::RG_CAND << sg::RG_SHIFT | (uint32_t)B.cand.size()});
+            B.cand.push_back(entries[k++].cd);
+        }
+        while (kx < xentries.size() && xentries[kx].cell == cell) {
+            grefs.push_back({(uint32_t)cell, xentries[kx].cd.poly, (uint32_t)sg::RG_XCAND << sg::RG_SHIFT | (uint32_t)B.xcand.size()});
+            B.xcand.push_back(xentries[kx++].cd);
+        }
+    }
+    if (std::max(B.cand.size(), std::max(B.xcand.size(), B.poly_layers.size())) >= ((size_t)1 << sg::RG_SHIFT)) return -3;
+    if (B.ref.size() + grefs.size() >= ((size_t)1 << 32)) return -3;
+    // a polygon is in a cell's list once: as a candidate where its boundary touches the cell, else as a cover
+    std::sort(grefs.begin(), grefs.end(), [](const GRef &x, const GRef &y) { return x.cell != y.cell ? x.cell < y.cell : x.poly < y.poly; });
+    size_t kg = 0;
+    for (size_t cell = 0; cell < ncell; ++cell) {
+        B.ref_off.push_back((uint32_t)B.ref.size());
+        while (kg < grefs.size() && grefs[kg].cell == cell) B.ref.push_back(grefs[kg++].code);
     }
     B.nets.push_back(N);
     return 0;
@@ -2691,18 +2728,24 @@ extern "C" int sg_set_road_networks(sg_handle *h, const sg_road_networks *in)
     free_pool(h->road_allocs);
     h->has_road = false;
     h->p.road = nullptr;
+    h->geom = sg::RoadGeom{};
     RoadBuild B;
     B.poly_edge_off.push_back(0);
     B.imp_off.push_back(0);
     for (int n = 0; n < in->n_networks; ++n)
         if (int brc = build_road_network(in, n, B))
             return fail(h, SG_ERR_INVALID, "sg_set_road_networks: network %d cannot be indexed (%s)", n,
-                        brc == -1 ? "more than 65535 edges of one polygon in one cell" : "a cell whose reference points all lie on a polygon boundary");
+                        brc == -1 ? "more than 65535 edges of one polygon in one cell"
+                        : brc == -3 ? "more than 2^30 polygons or boundary cells" : "a cell whose reference points all lie on a polygon boundary");
     B.cell_off.push_back((uint32_t)B.cand.size());
+    B.ref_off.push_back((uint32_t)B.ref.size());
+    if (B.ref.empty()) B.ref.push_back(0u);
+    if (B.xcand.empty()) B.xcand.push_back(sg::RoadCand{});
+    if (B.xcand_edges.empty()) B.xcand_edges.push_back(0);
     if (B.cand.empty()) B.cand.push_back(sg::RoadCand{});
     if (B.cand_edges.empty()) B.cand_edges.push_back(0);
     if (B.edges.empty()) B.edges.assign(4, 0.0);
-    if (B.nets.empty()) { B.nets.push_back(sg::RoadNet{0.0, 0.0, 1.0, 1, 1, 0}); B.cells.push_back(0); B.cell_off.insert(B.cell_off.begin(), 0u); B.net_flags.push_back(0); B.imp_off.push_back(0); }
+    if (B.nets.empty()) { B.nets.push_back(sg::RoadNet{0.0, 0.0, 1.0, 1, 1, 0}); B.cells.push_back(0); B.cell_off.insert(B.cell_off.begin(), 0u); B.ref_off.insert(B.ref_off.begin(), 0u); B.poly0.push_back(0); B.net_flags.push_back(0); B.imp_off.push_back(0); }
     if (B.imp_edges.empty()) B.imp_edges.assign(4, 0.0);
     std::vector<int32_t> nos(in->net_of_scenario, in->net_of_scenario + h->R);
     auto &A = h->road_allocs;
@@ -2735,16 +2778,97 @@ extern "C" int sg_set_road_networks(sg_handle *h, const sg_road_networks *in)
         if ((rc = dev_upload(h, A, &R.imp_aux, aux))) return rc;
         if ((rc = dev_upload(h, A, &R.imp_m, big))) return rc;
     }
+    sg::RoadGeom G{};
+    if ((rc = dev_upload(h, A, &G.ref_off, B.ref_off))) return rc;
+    if ((rc = dev_upload(h, A, &G.ref, B.ref))) return rc;
+    if ((rc = dev_upload(h, A, &G.xcand, B.xcand))) return rc;
+    if ((rc = dev_upload(h, A, &G.xcand_edges, B.xcand_edges))) return rc;
+    if ((rc = dev_upload(h, A, &G.poly0, B.poly0))) return rc;
     R.n_nets = in->n_networks;
     std::vector<sg::RoadIndex> one(1, R);
     const sg::RoadIndex *dR = nullptr;
     if ((rc = dev_upload(h, A, &dR, one))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors go out of scope
     h->road = R;
+    h->geom = G;
     h->p.road = dR;
     h->has_road = true;
     ++h->generation;
     return SG_OK;
+}
+
+// ---- which road geometries contain each entity / each point (sgym_geom.hpp) ------------------------------------------
+// Device scratch of its own: the observation scratch holds what sg_raster_map_device / sg_tick handed out, which stays valid.
+static int road_info_scratch(sg_handle *h, size_t bytes, unsigned char **out)
+{
+    if (bytes > h->ri_cap) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->ri_buf) HIP_TRY(h, hipFree(h->ri_buf));
+        h->ri_buf = nullptr;
+        h->ri_cap = 0;
+        HIP_TRY(h, hipMalloc(&h->ri_buf, bytes));
+        poison(h->stream, h->ri_buf, bytes);
+        h->ri_cap = bytes;
+    }
+    *out = (unsigned char *)h->ri_buf;
+    return SG_OK;
+}
+
+// n queries on the handle's stream (behind whatever rollout work is pending there) with HOST outputs; d_scen / d_xy: the points
+// already in the scratch behind the outputs' room (nullptr: the entity slots)
+static int road_info_host(sg_handle *h, unsigned char *d, int64_t n, const int32_t *d_scen, const double *d_xy, int32_t cap, int32_t *count,
+                          int32_t *geoms, uint32_t *layers)
+{
+    int32_t *d_count = reinterpret_cast<int32_t *>(d);
+    uint32_t *d_layers = reinterpret_cast<uint32_t *>(d + (size_t)n * 4);
+    int32_t *d_geoms = reinterpret_cast<int32_t *>(d + (size_t)n * 8);
+    sgl::road_info(h->stream, h->p, h->road, h->geom, h->has_road, d_scen, d_xy, n, cap, d_count, geoms ? d_geoms : nullptr, layers ? d_layers : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (layers) HIP_TRY(h, hipMemcpyAsync(layers, d_layers, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (geoms && cap > 0) HIP_TRY(h, hipMemcpyAsync(geoms, d_geoms, (size_t)n * cap * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+extern "C" int sg_road_info(sg_handle *h, int32_t cap, int32_t *count, int32_t *geoms, uint32_t *layers, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (!geoms) cap = 0;
+    if (!count || cap < 0) return fail(h, SG_ERR_INVALID, "sg_road_info: null count or cap < 0");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_road_info: no scenarios uploaded");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int64_t n = (int64_t)h->R * h->E;
+    if (outputs_device) { // stream-ordered, not synchronised (sg_raster_map_device)
+        sgl::road_info(h->stream, h->p, h->road, h->geom, h->has_road, nullptr, nullptr, n, cap, count, geoms, layers);
+        HIP_TRY(h, hipGetLastError());
+        return SG_OK;
+    }
+    unsigned char *d = nullptr;
+    if (int rc = road_info_scratch(h, (size_t)n * 4 * (2 + (size_t)cap), &d)) return rc;
+    return road_info_host(h, d, n, nullptr, nullptr, cap, count, geoms, layers);
+}
+
+extern "C" int sg_road_info_points(sg_handle *h, int64_t n, const int32_t *scenario_of_point, const double *xy, int32_t cap, int32_t *count,
+                                   int32_t *geoms, uint32_t *layers)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (!geoms) cap = 0;
+    if (n < 0 || !count || cap < 0 || (n > 0 && (!xy || !scenario_of_point))) return fail(h, SG_ERR_INVALID, "sg_road_info_points: null array, n < 0 or cap < 0");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_road_info_points: no scenarios uploaded");
+    for (int64_t i = 0; i < n; ++i)
+        if (scenario_of_point[i] < 0 || scenario_of_point[i] >= h->R)
+            return fail(h, SG_ERR_INVALID, "sg_road_info_points: scenario_of_point[%lld]=%d out of range", (long long)i, scenario_of_point[i]);
+    if (n == 0) return SG_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t out_bytes = (size_t)n * 4 * (2 + (size_t)cap), xy_off = (out_bytes + 15) & ~(size_t)15;
+    unsigned char *d = nullptr;
+    if (int rc = road_info_scratch(h, xy_off + (size_t)n * 20, &d)) return rc;
+    double *d_xy = reinterpret_cast<double *>(d + xy_off);
+    int32_t *d_scen = reinterpret_cast<int32_t *>(d + xy_off + (size_t)n * 16);
+    HIP_TRY(h, hipMemcpyAsync(d_xy, xy, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_scen, scenario_of_point, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    return road_info_host(h, d, n, d_scen, d_xy, cap, count, geoms, layers);
 }
 
 // the raster kernels of sg_raster_map / sg_raster_map_device on the handle's stream; *d_out = [R][n_layers][nh][nw]

@@ -40,6 +40,10 @@ void rollout_rss_tab(int G, dim3 grid, hipStream_t s, const sg::Params &p, doubl
 void rss_lines(dim3 grid, hipStream_t s, const sg::Params &p, const sg::TabGroups &tg);
 // k_road.hip: rollout_kernel_road<G, WV>
 void rollout_road(int G, int WV, dim3 grid, hipStream_t s, const RolloutArgs &a);
+// k_geom.hip (sgym_geom.hpp): road_info_kernel, one lane per query -- the entity slots of the batch (xy == nullptr, n = R * E) or n
+// caller-supplied points; all pointers DEVICE
+void road_info(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, const sg::RoadGeom &G, bool has_road, const int32_t *scen,
+               const double *xy, int64_t n, int cap, int32_t *count, int32_t *geoms, uint32_t *layers);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

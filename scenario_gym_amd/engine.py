@@ -293,6 +293,52 @@ class RolloutEngine:
         st = L.SgRoadNetworks(len(networks), p(nos), p(poly_off), p(ring_off), p(vert_off), p(verts), p(layers))
         self._check(self.lib.sg_set_road_networks(self.h, C.byref(st)), "sg_set_road_networks")
 
+    def road_info(self, cap=32, torch_out=False):
+        """State.get_road_info_at_entity (state/state.py:330-338) for every entity slot at its current pose (sg_road_info):
+        (count [R, E] int32, geoms [R, E, cap] int32, layers [R, E]).  count = how many geometries of the scenario's network
+        contain the entity (-1: the slot is not in State.poses; 0 without a network); geoms = their indices within the network
+        as set_road_networks got it (`RoadNetwork.geometry_index` order), ascending, -1 behind the last; layers = the OR of
+        their LAYER_* bits.  Host form: numpy arrays; when some entity lies in more than `cap` geometries the query is
+        repeated once with cap = count.max(), so no list comes back truncated.  torch_out: torch tensors in HBM (int32;
+        layers as int32 bit patterns) the kernel writes directly, ordered after it; lists stop at `cap` there, count tells."""
+        R, E, cap = self.R, self.E, int(cap)
+        if torch_out:
+            import torch
+
+            dev = f"cuda:{self.cfg.device}"
+            count = torch.empty((R, E), dtype=torch.int32, device=dev)
+            geoms = torch.empty((R, E, cap), dtype=torch.int32, device=dev)
+            layers = torch.empty((R, E), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(count.device).synchronize()  # (the allocator's work before the handle's stream writes)
+            self._check(self.lib.sg_road_info(self.h, cap, count.data_ptr(), geoms.data_ptr() if cap > 0 else None,
+                                              layers.data_ptr(), 1), "sg_road_info")
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+            return count, geoms, layers
+        while True:
+            count, layers = np.empty((R, E), np.int32), np.empty((R, E), np.uint32)
+            geoms = np.empty((R, E, cap), np.int32)
+            self._check(self.lib.sg_road_info(self.h, cap, count.ctypes.data, geoms.ctypes.data if cap > 0 else None,
+                                              layers.ctypes.data, 0), "sg_road_info")
+            if count.size == 0 or int(count.max()) <= cap:
+                return count, geoms, layers
+            cap = int(count.max())
+
+    def road_info_points(self, scenario_of_point, xy, cap=32):
+        """RoadNetwork.get_geometries_at_point (road_network/road_network.py:375-407) for n points (sg_road_info_points):
+        point k = xy[k] against the network of scenario scenario_of_point[k].  Returns (count [n], geoms [n, cap], layers [n])
+        as road_info does, re-queried once when a list would not fit."""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        scen = np.ascontiguousarray(np.broadcast_to(np.asarray(scenario_of_point, np.int32), (len(xy),)))
+        n, cap = len(xy), int(cap)
+        while True:
+            count, layers = np.empty(n, np.int32), np.empty(n, np.uint32)
+            geoms = np.empty((n, cap), np.int32)
+            self._check(self.lib.sg_road_info_points(self.h, n, scen.ctypes.data, xy.ctypes.data, cap, count.ctypes.data,
+                                                     geoms.ctypes.data if cap > 0 else None, layers.ctypes.data), "sg_road_info_points")
+            if n == 0 or int(count.max()) <= cap:
+                return count, geoms, layers
+            cap = int(count.max())
+
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];
         layers: 0 = entity, or one LAYER_* bit of scenario_gym_amd.road_network."""

@@ -311,6 +311,36 @@ class BatchedScenarioGym:
             self._fut[key] = self.engine.raster_map(codes, width, height, nw, nh)
         return self._fut[key]
 
+    def _road_info(self, cap: int = 32):
+        """(count [R, E], geoms [R, E, >= cap], layers [R, E]) of engine.road_info for the current state, cached per state."""
+        key = ("road_info",)
+        if self._fut is None or key not in self._fut or self._fut[key][1].shape[2] < cap:
+            self._set_road_networks()
+            self._fut = dict(self._fut or {})
+            self._fut[key] = self.engine.road_info(cap)
+        return self._fut[key]
+
+    def road_info(self, cap: int = 32):
+        """State.get_road_info_at_entity for the whole batch: count [R, E] (-1: the entity is not in the scene), geoms
+        [R, E, cap or more] indices into each scenario's `road_network.geometry_index()` (-1 behind the last), layers [R, E]
+        LAYER_* bits of the containing geometries.  No list is truncated."""
+        return self._road_info(int(cap))
+
+    def get_geometries_at_points(self, index: int, xy):
+        """RoadNetwork.get_geometries_at_point (road_network.py:375-407) of scenario `index`'s network for the points
+        xy [n, 2], on the device: one (class names, objects) pair per point."""
+        rn = self.scenarios[index].road_network
+        xy = np.asarray(xy, np.float64).reshape(-1, 2)
+        if not rn:
+            return [([], []) for _ in xy]
+        self._set_road_networks()
+        count, geoms, _ = self.engine.road_info_points(np.full(len(xy), index, np.int32), xy)
+        out = []
+        for c, g in zip(count, geoms):
+            objs = [rn.geometry_index()[j] for j in g[:c]]
+            out.append(([o.__class__.__name__ for o in objs], objs))
+        return out
+
     def _rss_results(self):
         if self._rss_cache is None:
             self._rss_cache = self.engine.rss()
@@ -560,6 +590,10 @@ class ScenarioGym:
 
     def get_metrics(self) -> Dict[str, Any]:
         return self._b.get_metrics()[0]
+
+    def get_geometries_at_point(self, x: float, y: float):
+        """RoadNetwork.get_geometries_at_point(x, y) (road_network.py:375-407) of the scenario's road network, on the device."""
+        return self._b.get_geometries_at_points(0, [[x, y]])[0]
 
     def close(self) -> None:
         pass

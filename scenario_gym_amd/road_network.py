@@ -11,9 +11,14 @@ condition and the RasterizedMapSensor layers.
 Elevation: geometries may carry an `Elevation` list of (x, y, z) samples; `elevation_at_point` interpolates them as the
 reference does (road_network.py:446-520) and the OpenSCENARIO reader uses it for trajectories without z.
 
-Not mirrored: OpenDRIVE import, lane graphs, and the repair of invalid
+Not mirrored: OpenDRIVE import and the repair of invalid
 (self-intersecting) boundaries through GEOS `make_valid` / `buffer` (base.py:94-118) -- rings are used as given, with
 the even-odd rule.
+
+Which geometries contain a point (`get_geometries_at_point`, road_network.py:375-407) is answered on the device, for
+batches of entities or points: `State.get_road_info_at_entity`, `ScenarioGym.get_geometries_at_point`,
+`BatchedScenarioGym.get_geometries_at_points` / `road_info`.  `geometry_index()` maps the indices the device returns to
+the objects here.  The lane graph (road_network.py:330-373) is host-only.
 """
 import json
 import os
@@ -197,6 +202,7 @@ class RoadNetwork:
         self.pavements, self.crossings, self.buildings = list(pavements), list(crossings), list(buildings)
         self._arrays = None
         self._elev = None
+        self._lane_parents = {}
 
     @classmethod
     def create_from_file(cls, filepath: str):
@@ -240,6 +246,54 @@ class RoadNetwork:
     @property
     def road_network_geometries(self) -> List[RoadGeometry]:
         return self.roads + self.intersections + self.lanes + self.pavements + self.crossings + self.buildings
+
+    def geometry_index(self) -> List[RoadGeometry]:
+        """Polygon k of `polygon_arrays()` -- the index the device's road query returns (sg_road_info) -- is geometry k of
+        this list: `road_network_geometries`, evaluated once."""
+        if getattr(self, "_geometry_index", None) is None:
+            self._geometry_index = self.road_network_geometries
+        return self._geometry_index
+
+    # ------------------------------------------------------------------ the lane graph (road_network.py:330-373)
+    @property
+    def road_network_objects(self) -> List[RoadObject]:
+        return self.road_network_geometries
+
+    def object_by_id(self, i: str) -> RoadObject:
+        """road_network.py:330-337."""
+        return {x.id: x for x in self.road_network_objects}[i]
+
+    @property
+    def driveable_lanes(self) -> List[Lane]:
+        """road_network.py:339-342."""
+        return [l for l in self.lanes if l.type == "driving"]
+
+    def _lanes_by_id(self) -> Dict[str, Lane]:
+        return {l.id: l for l in self.lanes}
+
+    def get_successor_lanes(self, l: Lane) -> List[Lane]:
+        """road_network.py:349-351 (the order of a lane's successors is a per-process set order in the reference)."""
+        by_id = self._lanes_by_id()
+        return [by_id[i] for i in l.successors]
+
+    def get_predecessor_lanes(self, l: Lane) -> List[Lane]:
+        """road_network.py:353-355."""
+        by_id = self._lanes_by_id()
+        return [by_id[i] for i in l.predecessors]
+
+    def get_connecting_roads(self, i: Intersection) -> List[Road]:
+        """road_network.py:357-359 (connecting_roads holds ids; a RoadObject equals its id)."""
+        return [r for r in self.roads if r in i.connecting_roads]
+
+    def get_intersections(self, r: Road) -> List[Intersection]:
+        """road_network.py:361-363."""
+        return [i for i in self.intersections if r in i.connecting_roads]
+
+    def get_lane_parent(self, l: Lane):
+        """road_network.py:365-373: the road or intersection the lane belongs to, None for a free-standing lane."""
+        if l not in self._lane_parents:
+            self._lane_parents[l] = next((x for x in self.roads + self.intersections if l in x.lanes), None)
+        return self._lane_parents[l]
 
     def to_dict(self) -> Dict[str, Any]:
         """road_network.py:409-414."""

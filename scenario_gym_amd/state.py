@@ -191,6 +191,21 @@ class State:
         device from the scenario's road network: bool [n_layers, nh, nw]."""
         return self._gym._raster_map(tuple(layers), float(width), float(height), int(nw), int(nh))[self._i]
 
+    def get_road_info_at_entity(self, e: Entity):
+        """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's
+        position -- "Road", "Intersection", "Lane", "Pavement", "Crossing", "Building", the objects the scenario's RoadNetwork
+        holds, in `road_network_geometries` order.  ([], []) without a road network; KeyError for an entity that is not in
+        `poses`.  Computed on the device for every entity of the batch at once (sg_road_info), cached per state."""
+        k = self._scenario.entities.index(e) if e in self._scenario.entities else -1
+        if k < 0 or not self._s()["present"][self._i, k]:
+            raise KeyError(e)
+        rn = self._scenario.road_network
+        if not rn:
+            return [], []
+        count, geoms, _ = self._gym._road_info()
+        objs = [rn.geometry_index()[j] for j in geoms[self._i, k, :count[self._i, k]]]
+        return [o.__class__.__name__ for o in objs], objs
+
     def get_entities_in_area(self, area) -> List[Entity]:
         """state.py:340-354: entities whose centre point lies strictly inside `area`.  The reference takes a shapely
         (Multi)Polygon; here `area` is anything with `.exterior.coords`, or an (n, 2) array of ring vertices (simple

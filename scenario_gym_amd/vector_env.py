@@ -41,6 +41,7 @@ class VectorScenarioEnv:
 
         packed, _ = pack_scenarios(self.scenarios, create_agent)
         self.n_envs = packed.n_scenarios
+        self._ego = np.array([sc.entities.index(sc.ego) for sc in self.scenarios], np.int64)
         self.engine = RolloutEngine(packed.n_scenarios, packed.n_entities, timestep=timestep,
                                     terminal_conditions=self.terminal_conditions, device=device)
         self.engine.upload(packed)
@@ -95,6 +96,20 @@ class VectorScenarioEnv:
             self.done = np.zeros(self.n_envs, bool)
             obs = self._observe()  # the restarted environments return the first observation of their new episode
         return obs, reward, done, {"terminal_flags": flags}
+
+    def road_info(self, cap: int = 32):
+        """State.get_road_info_at_entity for the ego of every environment (sg_road_info): count [R], geoms [R, cap] indices
+        into the scenario's `road_network.geometry_index()`, layers [R] LAYER_* bits.  torch_obs: torch tensors in HBM (lists
+        stop at cap); else numpy arrays (no list truncated)."""
+        count, geoms, layers = self.engine.road_info(cap, torch_out=self.torch_obs)
+        if self.torch_obs:
+            import torch
+
+            r = torch.arange(self.n_envs, device=count.device)
+            e = torch.as_tensor(self._ego, device=count.device)
+            return count[r, e], geoms[r, e], layers[r, e]
+        r = np.arange(self.n_envs)
+        return count[r, self._ego], geoms[r, self._ego], layers[r, self._ego]
 
     def close(self):
         self.engine.close()

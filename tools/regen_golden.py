@@ -35,6 +35,7 @@ GENERATORS = {
     "make_golden_ped_noise": ["ped_noise"],
     "make_golden_ped_roads": ["ped_roads"],
     "make_golden_random_walk": ["random_walk"],
+    "make_golden_road_info": ["road_info"],
     "make_golden_roads": ["roads"],
     "make_golden_route": ["route"],
     "make_golden_rss": ["rss"],
