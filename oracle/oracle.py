@@ -105,6 +105,23 @@ def surface_contains(net, layer, xs, ys):
     return out.astype(bool)
 
 
+def geoms_at_points(net, xs, ys, cap=32):
+    """RoadNetwork.get_geometries_at_point for many points, every polygon asked for every point (sgo_geoms_at_points):
+    (count [n] int32 -- it may exceed cap, geoms [n, cap] int32 ascending with -1 behind the last, layers [n] uint32)."""
+    net = _road(net)
+    L = lib()
+    L.sgo_geoms_at_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sgo_geoms_at_points.restype = None
+    xs = np.ascontiguousarray(np.atleast_1d(xs), np.float64)
+    ys = np.ascontiguousarray(np.atleast_1d(ys), np.float64)
+    n, cap = len(xs), int(cap)
+    count, layers = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    geoms = np.full((n, cap), -1, np.int32)
+    L.sgo_geoms_at_points(None if net is None else net.ref(), n, _p(xs), _p(ys), cap, _p(count), _p(geoms) if cap > 0 else None,
+                          _p(layers))
+    return count, geoms, layers
+
+
 def raster_map(poses, bbox, ego, net, layers, width=20.0, height=20.0, nw=20, nh=20):
     """RasterizedMapSensor._step (sensor/map.py:136-149): [n_layers][nh][nw] bool; layers: 0 = entity, else a LAYER_* bit."""
     net = _road(net)

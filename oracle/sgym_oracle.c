@@ -610,7 +610,14 @@ static int orient_sign(double ax, double ay, double bx, double by, double px, do
     const double bound = 1e-15 * (fabs(dl) + fabs(dr)); /* > (3 + 16 eps) eps of Shewchuk's stage-A bound */
     if (det > bound) return 1;
     if (det < -bound) return -1;
-    /* = ax*by - ax*py - px*by - ay*bx + ay*px + py*bx  (px*py cancels): six exact products, summed exactly */
+    /* = ax*by - ax*py - px*by - ay*bx + ay*px + py*bx  (px*py cancels): six exact products, summed exactly.  Exact only while
+     * the products' error terms do not underflow: coordinates below 2^200 are scaled by 2^300 first (no sign changes; every
+     * product of two coordinates above 1e-146 is then exact -- a coordinate of 5e-324 beside a vertex at 0 was not) */
+    const double m = fmax(fmax(fmax(fabs(ax), fabs(ay)), fmax(fabs(bx), fabs(by))), fmax(fabs(px), fabs(py)));
+    if (m < 0x1p+200) {
+        const double s = 0x1p+300;
+        ax *= s; ay *= s; bx *= s; by *= s; px *= s; py *= s;
+    }
     const double fa[6] = {ax, -ax, -px, -ay, ay, py}, fb[6] = {by, py, by, bx, px, bx};
     double e[12];
     int n = 0;
@@ -649,6 +656,7 @@ static int ray_edge(double x1, double y1, double x2, double y2, double px, doubl
 static int polygon_contains(const sgo_road_network *net, int k, double x, double y)
 {
     int cross = 0;
+    if (x != x || y != y) return 0; /* NaN: in nothing (every comparison below would be false, and the orientation sign not) */
     for (int64_t r = net->ring_off[k]; r < net->ring_off[k + 1]; ++r) {
         const int64_t a = net->vert_off[r], b = net->vert_off[r + 1];
         for (int64_t i = a; i < b; ++i) {
@@ -690,6 +698,43 @@ void sgo_surface_contains_points(const sgo_road_network *net, uint32_t layer, in
             if (!(net->layers[k] & layer) || xs[q] < b[0] || xs[q] > b[2] || ys[q] < b[1] || ys[q] > b[3]) continue;
             out[q] = (uint8_t)polygon_contains(net, k, xs[q], ys[q]);
         }
+    free(bb);
+}
+
+/* RoadNetwork.get_geometries_at_point (road_network.py:375-407) for many points: every polygon is asked for every point
+ * (no grid; a polygon whose bounding box misses the point is skipped), whatever its layer bits.  Per point: count = how
+ * many polygons contain it (it may exceed cap), geoms[q * cap ..] = the first cap of their indices, ascending, -1 behind
+ * the last (NULL: none are written), layers = the OR of the layer bits of ALL of them (NULL: not written). */
+void sgo_geoms_at_points(const sgo_road_network *net, int n, const double *xs, const double *ys, int cap, int32_t *count,
+                         int32_t *geoms, uint32_t *layers)
+{
+    const int P = net ? net->n_polygons : 0;
+    double *bb = (double *)malloc((size_t)(P > 0 ? P : 1) * 4 * sizeof(double));
+    for (int k = 0; k < P; ++k) {
+        double *b = bb + (size_t)k * 4;
+        b[0] = b[1] = INFINITY;
+        b[2] = b[3] = -INFINITY;
+        for (int64_t i = net->vert_off[net->ring_off[k]]; i < net->vert_off[net->ring_off[k + 1]]; ++i) {
+            b[0] = fmin(b[0], net->verts[2 * i]); b[1] = fmin(b[1], net->verts[2 * i + 1]);
+            b[2] = fmax(b[2], net->verts[2 * i]); b[3] = fmax(b[3], net->verts[2 * i + 1]);
+        }
+    }
+    if (!geoms) cap = 0;
+    for (int q = 0; q < n; ++q) {
+        int c = 0;
+        uint32_t L = 0;
+        for (int k = 0; k < P; ++k) {
+            const double *b = bb + (size_t)k * 4;
+            if (!(xs[q] >= b[0] && xs[q] <= b[2] && ys[q] >= b[1] && ys[q] <= b[3])) continue; /* (NaN: in nothing) */
+            if (!polygon_contains(net, k, xs[q], ys[q])) continue;
+            if (c < cap) geoms[(size_t)q * cap + c] = k;
+            L |= net->layers[k];
+            ++c;
+        }
+        for (int k = c; k < cap; ++k) geoms[(size_t)q * cap + k] = -1;
+        count[q] = c;
+        if (layers) layers[q] = L;
+    }
     free(bb);
 }
 

@@ -23,6 +23,15 @@ __host__ __device__ inline void rn_two_sum(double a, double b, double &s, double
 __host__ __device__ __attribute__((noinline)) inline int rn_orient_exact(double ax, double ay, double bx, double by, double px, double py)
 {
     // (ax - px)(by - py) - (ay - py)(bx - px) = ax*by - ax*py - px*by - ay*bx + ay*px + py*bx
+    // The two-term products are exact only while their error terms do not underflow (a coordinate of 5e-324 beside a vertex at
+    // 0 did: a point one denormal step outside a corner came out inside).  A common power of two changes no sign and is exact:
+    // with it every product of two coordinates above 1e-146 is exact; coordinates beyond 2^200 stay as they are.
+    const double m = __builtin_fmax(__builtin_fmax(__builtin_fmax(__builtin_fabs(ax), __builtin_fabs(ay)), __builtin_fmax(__builtin_fabs(bx), __builtin_fabs(by))),
+                                    __builtin_fmax(__builtin_fabs(px), __builtin_fabs(py)));
+    if (m < 0x1p+200) {
+        const double s = 0x1p+300;
+        ax *= s; ay *= s; bx *= s; by *= s; px *= s; py *= s;
+    }
     const double fa[6] = {ax, -ax, -px, -ay, ay, py}, fb[6] = {by, py, by, bx, px, bx};
     double e[12];
     int n = 0;

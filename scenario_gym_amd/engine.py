@@ -278,10 +278,12 @@ class RolloutEngine:
         nos = np.ascontiguousarray(net_of_scenario, np.int32)
         assert nos.shape == (self.R,)
         poly_off, ring_off, vert_off, verts, layers = [0], [np.zeros(1, np.int64)], [np.zeros(1, np.int64)], [], []
+        n_ring = n_vert = 0
         for a in networks:
             ro, vo = np.asarray(a["ring_off"], np.int64), np.asarray(a["vert_off"], np.int64)
-            ring_off.append(ro[1:] + ring_off[-1][-1])
-            vert_off.append(vo[1:] + vert_off[-1][-1])
+            ring_off.append(ro[1:] + n_ring)  # (running totals: a network without polygons or rings adds nothing)
+            vert_off.append(vo[1:] + n_vert)
+            n_ring, n_vert = n_ring + int(ro[-1]), n_vert + int(vo[-1])
             verts.append(np.asarray(a["verts"], np.float64).reshape(-1, 2))
             layers.append(np.asarray(a["layers"], np.uint32))
             poly_off.append(poly_off[-1] + len(a["layers"]))

@@ -4,12 +4,12 @@ sg_road_info_points -- against the real reference's answers (tests/golden/road_i
 (road_network.py:330-373).  The GPU tests go through the C ABI and read only tests/golden/."""
 import json
 import os
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from conftest import load_golden, scenario_arrays
+from road_shapes import _contains_all, _edges_of
 from test_host_api import scenario_from_arrays
 
 gpu = pytest.mark.gpu
@@ -67,45 +67,6 @@ def sga():
 
 
 # ---------------------------------------------------------------- CPU: the fixture, the lane graph, the index -> object map
-def _exact_orient(ax, ay, bx, by, px, py):
-    F = Fraction
-    return (F(bx) - F(ax)) * (F(py) - F(ay)) - (F(by) - F(ay)) * (F(px) - F(ax))
-
-
-def _contains_all(edges, poly_edge_off, px, py):
-    """bool per polygon: crossing number of its rings for the ray towards +x, half-open in y; the orientation in exact rational
-    arithmetic wherever fp64 could be in doubt; a point on an edge is in nothing."""
-    x1, y1, x2, y2 = edges.T
-    o = (x2 - x1) * (py - y1) - (y2 - y1) * (px - x1)
-    mag = np.abs((x2 - x1) * (py - y1)) + np.abs((y2 - y1) * (px - x1))
-    box = (np.minimum(x1, x2) <= px) & (px <= np.maximum(x1, x2)) & (np.minimum(y1, y2) <= py) & (py <= np.maximum(y1, y2))
-    straddle = (y1 > py) != (y2 > py)
-    sign = np.sign(o)
-    for k in np.nonzero((np.abs(o) <= 1e-9 * mag) & (straddle | box))[0]:
-        e = _exact_orient(x1[k], y1[k], x2[k], y2[k], px, py)
-        sign[k] = (e > 0) - (e < 0)
-    on = box & (sign == 0)
-    cross = straddle & (np.where(y2 > y1, sign, -sign) > 0)
-    starts = poly_edge_off[:-1]
-    n_cross = np.add.reduceat(cross.astype(np.int64), starts)
-    n_on = np.add.reduceat(on.astype(np.int64), starts)
-    empty = poly_edge_off[1:] == starts
-    return (n_cross % 2 == 1) & (n_on == 0) & ~empty
-
-
-def _edges_of(a):
-    """([n][4] ring edges polygon by polygon, edge offsets per polygon) of a polygon_arrays() dict."""
-    edges, off = [], [0]
-    for q in range(len(a["ring_off"]) - 1):
-        n = 0
-        for r in range(a["ring_off"][q], a["ring_off"][q + 1]):
-            v = a["verts"][a["vert_off"][r]:a["vert_off"][r + 1]]
-            edges.append(np.concatenate([v, np.roll(v, -1, axis=0)], axis=1))
-            n += len(v)
-        off.append(off[-1] + n)
-    return np.concatenate(edges), np.array(off)
-
-
 def test_fixture_answers_are_the_exact_crossing_number():
     """Every answer of road_info.npz, all six networks and all their points (uniform, on vertices, 1e-9 beside vertices, edge
     midpoints), recomputed from the rings of roads.npz: strictly inside the exterior ring and outside the holes, on a ring =
