@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 6 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers */
 
 typedef enum {
     SG_OK = 0,
@@ -394,6 +394,39 @@ int sg_road_info(sg_handle *h, int32_t cap, int32_t *count, int32_t *geoms, uint
  * cap < 0, xy or scenario_of_point NULL with n > 0, a scenario index outside [0, n_scenarios). */
 int sg_road_info_points(sg_handle *h, int64_t n, const int32_t *scenario_of_point, const double *xy, int32_t cap, int32_t *count,
                         int32_t *geoms, uint32_t *layers);
+
+/* The observers of the two calls below: observer k is entity slot slot[k] of scenario scenario[k] -- ANY entity of its
+ * scenario, as the reference's sensors are built per entity (RasterizedMapSensor(entity, ...) sensor/map.py:136-271,
+ * FutureCollisionDetector(entity, horizon) sensor/common.py:60-106; create_agent gives them to agents of non-ego entities).
+ * HOST arrays [n], copied once into a device list the handle owns; duplicates are allowed and the order is the caller's.  The
+ * list holds until it is replaced, cleared (n == 0) or sg_upload (which forgets it, as it forgets the road networks);
+ * sg_reset / sg_step / sg_rollout keep it.  SG_ERR_STATE before sg_upload.  SG_ERR_INVALID: n < 0, a NULL array with n > 0, a
+ * scenario outside [0, n_scenarios), a slot outside [0, n_entities), a slot of SG_KIND_NONE, n above 2^31 - 1 (one workgroup
+ * serves one observer: the grid limit).  A refused call leaves the handle without observers.  Replacing or setting a list waits
+ * for the work queued on sg_stream(h) first (a queued observation call may still read the previous list): do it between
+ * episodes, not inside a pipelined step loop. */
+int sg_set_observers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot);
+
+/* RasterizedMapSensor._step (sensor/map.py:136-271) for every observer, in the observer's frame (rotated by its heading +
+ * pi/2): out[k][l][i][j] as sg_raster_map has it for the ego -- layers[l] = 0 the "entity" layer, otherwise ONE SG_LAYER_* bit,
+ * 1..8 layers; a surface layer on a handle without networks or in a scenario without one is all zeros; an observer that is
+ * not in State.poses (the reference sensor reads state.poses[entity]) gets all zeros.  For the observer (r, ego of r) the
+ * bytes are those of sg_raster_map.  out: [n_observers][n_layers][nh][nw] bytes.  outputs_device == 0: HOST buffer,
+ * synchronous (the maps pass through the handle's observation scratch: an observation call).  Otherwise `out` is a DEVICE
+ * pointer; the kernel is queued on sg_stream(h) behind the handle's pending work and the call does not wait (valid after
+ * sg_synchronize).  With no observers set: SG_OK, nothing is written.  A persistent rollout launch that gave up is reported as
+ * by the other observation calls (sticky); a call that does not wait -- device outputs, no observers -- reports what is
+ * known when it is made, and the give-up of a launch still in flight is reported by the next call that synchronises.  One
+ * workgroup per observer computes all layers in one pass over the grid points.  Not part of the sg_tick graph. */
+int sg_raster_map_observers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                            const int32_t *layers, uint8_t *out, int32_t outputs_device);
+
+/* FutureCollisionDetector._step (sensor/common.py:87-106) for every observer at the current State.t of its scenario:
+ * out[k] = 1 iff, at one of the n_samples times np.linspace(t, t + horizon, n_samples), the observer's box at its
+ * trajectory.position_at_t(t_j) overlaps another entity's box at that entity's own position_at_t(t_j); presence is not
+ * consulted and a box equal to the observer's never counts, as in sg_future_collision, whose answer the observer
+ * (r, ego of r) reproduces.  out: [n_observers] bytes, HOST or DEVICE as in sg_raster_map_observers. */
+int sg_future_collision_observers(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGYM_LIB") or os.path.join(HERE, "lib", "libsgym_hip.so")  # SGYM_LIB: A/B builds
 
 SG_OK = 0
-ABI_VERSION = 6
+ABI_VERSION = 7
 (KIND_NONE, KIND_REPLAY, KIND_AGENT_REPLAY, KIND_AGENT_PID, KIND_AGENT_VEHICLE, KIND_AGENT_PEDESTRIAN,
  KIND_AGENT_EXTERNAL) = range(7)
 TERM_MAX_LENGTH, TERM_COLLISION, TERM_EGO_COLLISION, TERM_EGO_OFF_ROAD = 1, 2, 4, 8
@@ -33,6 +33,7 @@ SYMBOLS = (
     "sg_set_road_networks", "sg_raster_map", "sg_raster_map_device", "sg_reset_scenarios", "sg_terminal_flags", "sg_tick", "sg_set_collision_tolerance", "sg_read_collision_points", "sg_rss_update", "sg_rss_read", "sg_set_rss",
     "sg_group_create", "sg_group_destroy", "sg_group_size", "sg_group_handle", "sg_group_upload", "sg_group_rollout",
     "sg_group_read_metrics", "sg_group_last_error", "sg_host_alloc", "sg_host_free", "sg_road_info", "sg_road_info_points",
+    "sg_set_observers", "sg_raster_map_observers", "sg_future_collision_observers",
 )
 
 
@@ -194,6 +195,9 @@ def load():
     lib.sg_raster_map_device.argtypes = [H, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.sg_road_info.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_road_info_points.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sg_set_observers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.sg_raster_map_observers.argtypes = [H, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_future_collision_observers.argtypes = [H, C.c_double, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_debug_trig32.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -95,24 +95,24 @@ class EgoLocalizationSensor(Sensor):
 class FutureCollisionDetector(Sensor):
     """sensor/common.py:59-106: the localisation observation plus `future_collision` -- does the entity's box, moved along
     its trajectory over `horizon` seconds (10 samples), meet another entity's box at that entity's trajectory position?
-    The look-ahead runs on the device for the whole batch (sg_future_collision); the sensor's entity must be the
-    scenario's ego."""
+    The look-ahead runs on the device for the whole batch: sg_future_collision for the egos, one
+    sg_future_collision_observers call for the sensors of all other entities."""
 
     def __init__(self, entity: Entity, horizon: float = 5.0):
         super().__init__(entity)
         self.horizon = horizon
 
     def _step(self, state):
-        if state.scenario.ego is not self.entity:
-            raise NotImplementedError("the device look-ahead is evaluated for the ego of each scenario")
-        return FutureCollisionObservation(self.entity, *state.get_entity_data(self.entity), state.future_collision(self.horizon))
+        return FutureCollisionObservation(self.entity, *state.get_entity_data(self.entity),
+                                          state.future_collision(self.horizon, entity=self.entity))
 
 
 class RasterizedMapSensor(Sensor):
     """sensor/map.py:26-271: an n x n grid in the entity's frame with one plane per layer -- the bounding boxes of the
     present entities ("entity") and the unions of road-network polygons ("driveable_surface", "road", "intersection",
-    "lane", "walkable_surface", "pavement", "crossing") -- computed on the device for the ego of every scenario
-    (sg_raster_map).  Default layers as in the reference: entity + driveable_surface."""
+    "lane", "walkable_surface", "pavement", "crossing") -- computed on the device: sg_raster_map for the egos, one
+    sg_raster_map_observers call for the sensors of all other entities.  Default layers as in the reference: entity +
+    driveable_surface."""
 
     _all_layers = ["entity", "driveable_surface", "road", "intersection", "lane", "walkable_surface", "pavement", "crossing"]
 
@@ -135,9 +135,7 @@ class RasterizedMapSensor(Sensor):
         return (len(self.layers), self.nw, self.nh) if self.channels_first else (self.nw, self.nh, len(self.layers))
 
     def _step(self, state):
-        if state.scenario.ego is not self.entity:
-            raise NotImplementedError("the device raster is evaluated for the ego of each scenario")
-        m = state.raster_map(self.layers, self.width, self.height, self.nw, self.nh)
+        m = state.raster_map(self.layers, self.width, self.height, self.nw, self.nh, entity=self.entity)
         return MapObservation(self.entity, *state.get_entity_data(self.entity), m if self.channels_first else m.transpose(1, 2, 0))
 
 

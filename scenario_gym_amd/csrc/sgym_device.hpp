@@ -50,3 +50,4 @@
 #include "sgym_rollout.hpp"
 #include "sgym_control.hpp"
 #include "sgym_sensors.hpp"
+#include "sgym_observers.hpp"

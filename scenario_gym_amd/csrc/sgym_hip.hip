@@ -151,6 +151,9 @@ struct sg_handle {
     sg::RoadGeom geom{};                               // ... and of the per-geometry lists beside it (sg_road_info; arrays in road_allocs)
     void *ri_buf = nullptr;                            // device scratch of sg_road_info / sg_road_info_points (grown on demand)
     size_t ri_cap = 0;
+    int32_t *d_observers = nullptr;                    // sg_set_observers: [2][obs_list_cap] scenario, slot of every observer (grown on demand)
+    int64_t n_obs = 0, obs_list_cap = 0;               // observers set (0: none); sg_upload forgets them
+    std::vector<uint8_t> slot_empty;                   // [R * E] the slot is SG_KIND_NONE in the uploaded batch (what sg_set_observers refuses)
     int ped_serial = 0;                                // env SG_PED_SERIAL: pedestrian pair loop one pedestrian per lane
     int ctl_slice = 64;                                // steps per control_kernel launch (env SG_CTL_SLICE)
     int n_launches = 0;           // rollout_kernel launches of the last call
@@ -428,6 +431,7 @@ extern "C" int sg_destroy(sg_handle *h)
     if (h->pin_ev) (void)hipHostFree(h->pin_ev);
     if (h->obs_buf) (void)hipFree(h->obs_buf);
     if (h->ri_buf) (void)hipFree(h->ri_buf);
+    if (h->d_observers) (void)hipFree(h->d_observers);
     if (h->d_reset_mask) (void)hipFree(h->d_reset_mask);
     if (h->d_term_flags) (void)hipFree(h->d_term_flags);
     if (h->d_rss_state) (void)hipFree(h->d_rss_state);
@@ -1478,6 +1482,7 @@ extern "C" int sg_upload(sg_handle *h, const sg_scenarios *sc)
     h->has_road = false;
     h->road = sg::RoadIndex{};
     h->geom = sg::RoadGeom{};
+    h->n_obs = 0; // the observers are slots of a batch
     h->uploaded = false; // (the controller table buffers stay: launch_rollout regrows them when the new batch needs more)
     h->ego_first = true;
     ++h->generation;
@@ -1487,7 +1492,9 @@ extern "C" int sg_upload(sg_handle *h, const sg_scenarios *sc)
     h->sliceable = true;
     free_pool(h->slice_allocs);
     h->slice_T = -1;
+    h->slot_empty.resize((size_t)h->R * h->E);
     for (size_t i = 0; i < (size_t)h->R * h->E; ++i) {
+        h->slot_empty[i] = sc->kind[i] == SG_KIND_NONE;
         h->sliceable = h->sliceable && (sc->kind[i] == SG_KIND_NONE || sc->kind[i] == SG_KIND_REPLAY || sc->kind[i] == SG_KIND_AGENT_REPLAY ||
                                         sc->kind[i] == SG_KIND_AGENT_PID || sc->kind[i] == SG_KIND_AGENT_VEHICLE);
         h->has_ped = h->has_ped || sc->kind[i] == SG_KIND_AGENT_PEDESTRIAN;
@@ -2948,6 +2955,94 @@ extern "C" int sg_raster_entities(sg_handle *h, double width, double height, int
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_raster_entities: %s", hipGetErrorString(e));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+// ---- observations for any entity: a list of observers (sgym_observers.hpp) -----------------------------------------------
+// the sticky give-up of check_queue for a call that does not wait for the stream: a launch still running is judged by the
+// next call that synchronises
+static int queue_gave_up(sg_handle *h) { return h->q_failed ? fail(h, SG_ERR_HIP, "%s", h->q_msg) : SG_OK; }
+
+extern "C" int sg_set_observers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot)
+{
+    if (!h) return SG_ERR_INVALID;
+    h->n_obs = 0; // a refused call leaves the handle without observers
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_set_observers: no scenarios uploaded");
+    if (n < 0 || (n > 0 && (!scenario || !slot))) return fail(h, SG_ERR_INVALID, "sg_set_observers: n < 0 or null array");
+    if (n > 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "sg_set_observers: more than 2^31 - 1 observers (one workgroup each: the grid limit)");
+    for (int64_t k = 0; k < n; ++k) {
+        if (scenario[k] < 0 || scenario[k] >= h->R) return fail(h, SG_ERR_INVALID, "sg_set_observers: scenario[%lld]=%d out of range", (long long)k, scenario[k]);
+        if (slot[k] < 0 || slot[k] >= h->E) return fail(h, SG_ERR_INVALID, "sg_set_observers: slot[%lld]=%d out of range", (long long)k, slot[k]);
+        if (h->slot_empty[(size_t)scenario[k] * h->E + slot[k]])
+            return fail(h, SG_ERR_INVALID, "sg_set_observers: slot %d of scenario %d holds no entity (SG_KIND_NONE)", slot[k], scenario[k]);
+    }
+    if (n == 0) return SG_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued observation call may still read the previous list)
+    if (n > h->obs_list_cap) {
+        if (h->d_observers) HIP_TRY(h, hipFree(h->d_observers));
+        h->d_observers = nullptr;
+        h->obs_list_cap = 0;
+        HIP_TRY(h, hipMalloc(&h->d_observers, (size_t)n * 2 * sizeof(int32_t)));
+        h->obs_list_cap = n;
+    }
+    HIP_TRY(h, hipMemcpy(h->d_observers, scenario, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_observers + h->obs_list_cap, slot, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->n_obs = n;
+    return SG_OK;
+}
+
+extern "C" int sg_raster_map_observers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                                       const int32_t *layers, uint8_t *out, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+        return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_map_observers: no scenarios uploaded");
+    for (int k = 0; k < n_layers; ++k) {
+        const uint32_t L = (uint32_t)layers[k];
+        if (layers[k] < 0 || L > 255u || (L & (L - 1)))
+            return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: layers[%d]=%d is not 0 or one SG_LAYER_* bit", k, layers[k]);
+    }
+    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!out) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: null out");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = h->d_observers, *d_slot = h->d_observers + h->obs_list_cap;
+    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
+        sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, out);
+        HIP_TRY(h, hipGetLastError());
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    const size_t bytes = (size_t)h->n_obs * n_layers * nw * nh;
+    unsigned char *d = nullptr;
+    if (int rc = obs_scratch(h, bytes, &d)) return rc;
+    sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, d);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (n_samples < 1 || !(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: bad argument");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_future_collision_observers: no scenarios uploaded");
+    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!out) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: null out");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = h->d_observers, *d_slot = h->d_observers + h->obs_list_cap;
+    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
+        sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, out);
+        HIP_TRY(h, hipGetLastError());
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    unsigned char *d = nullptr;
+    if (int rc = obs_scratch(h, (size_t)h->n_obs, &d)) return rc;
+    sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, d);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, d, (size_t)h->n_obs, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return check_queue(h); // (a persistent launch that gave up: sticky)
 }
 

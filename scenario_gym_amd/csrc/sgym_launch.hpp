@@ -44,6 +44,12 @@ void rollout_road(int G, int WV, dim3 grid, hipStream_t s, const RolloutArgs &a)
 // caller-supplied points; all pointers DEVICE
 void road_info(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, const sg::RoadGeom &G, bool has_road, const int32_t *scen,
                const double *xy, int64_t n, int cap, int32_t *count, int32_t *geoms, uint32_t *layers);
+// k_obs.hip (sgym_observers.hpp): observers_raster_kernel / observers_future_kernel, one workgroup per observer (scen[k], slot[k]);
+// scen / slot / out DEVICE, layers HOST (1..8 codes of sg_raster_map); out [n][n_layers][nh][nw] resp. [n] bytes
+void observers_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool has_road, const int32_t *scen, const int32_t *slot,
+                      int64_t n, double width, double height, int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out);
+void observers_future(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
+                      unsigned char *out);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -104,6 +104,7 @@ class RolloutEngine:
             raise RuntimeError(f"sg_create failed ({rc}): {msg}")
         self._view = None
         self._keep = None
+        self._n_obs = 0  # observers set (set_observers)
         if social_force is not None and "models" in social_force:  # per-agent models (BatchedScenarioGym)
             self.set_ped_models(social_force["models"], social_force.get("model_of"), noise=social_force.get("noise"),
                                 noise_seed=social_force.get("noise_seed", 0), normals=social_force.get("normals"))
@@ -215,6 +216,7 @@ class RolloutEngine:
             routes=None if packed.routes is None else np.ascontiguousarray(packed.routes, np.float64),
         )
         sc = L.SgScenarios(*[None if arrs[n] is None else arrs[n].ctypes.data for n, _ in L.SgScenarios._fields_])
+        self._n_obs = 0  # (sg_upload forgets the observers)
         self._check(self.lib.sg_upload(self.h, C.byref(sc)), "sg_upload")
         self._view = L.SgStateView()
         self._check(self.lib.sg_state_view_get(self.h, C.byref(self._view)), "sg_state_view_get")
@@ -340,6 +342,56 @@ class RolloutEngine:
             if n == 0 or int(count.max()) <= cap:
                 return count, geoms, layers
             cap = int(count.max())
+
+    def set_observers(self, scenario, slot):
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers -- observer k is entity slot
+        slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
+        sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
+        forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
+        scen = np.ascontiguousarray(scenario, np.int32).ravel()
+        slot = np.ascontiguousarray(slot, np.int32).ravel()
+        if scen.shape != slot.shape:
+            raise ValueError("set_observers: scenario and slot must have the same length")
+        self._n_obs = 0
+        self._check(self.lib.sg_set_observers(self.h, len(scen), scen.ctypes.data if len(scen) else None,
+                                              slot.ctypes.data if len(scen) else None), "sg_set_observers")
+        self._n_obs = len(scen)
+
+    def _obs_out(self, shape, torch_out):
+        if torch_out:
+            import torch
+
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.cfg.device}")
+            torch.cuda.current_stream(out.device).synchronize()  # (the allocator's work before the handle's stream writes)
+            return out, out.data_ptr() if out.numel() else None
+        out = np.empty(shape, np.uint8)
+        return out, out.ctypes.data if out.size else None
+
+    def raster_map_observers(self, layers, width=20.0, height=20.0, nw=20, nh=20, torch_out=False):
+        """RasterizedMapSensor._step (sensor/map.py:136-271) in the frame of every observer of set_observers
+        (sg_raster_map_observers): bool [n, n_layers, nh, nw]; layers as in raster_map.  An observer that is not in the scene
+        gets zeros.  torch_out: a torch uint8 tensor in HBM the kernel writes directly; this wrapper waits for the kernel
+        (sg_synchronize) before it returns, so the tensor can be used on any torch stream -- the C call itself does not wait."""
+        lay = np.ascontiguousarray(layers, np.int32)
+        out, ptr = self._obs_out((self._n_obs, len(lay), int(nh), int(nw)), torch_out)
+        self._check(self.lib.sg_raster_map_observers(self.h, float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data,
+                                                     ptr, int(bool(torch_out))), "sg_raster_map_observers")
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+            return out
+        return out.astype(bool)
+
+    def future_collision_observers(self, horizon=5.0, n_samples=10, torch_out=False):
+        """FutureCollisionDetector._step (sensor/common.py:87-106) for every observer of set_observers at the current time of
+        its scenario (sg_future_collision_observers): bool [n], or with torch_out a torch uint8 tensor in HBM (waited for, as
+        in raster_map_observers)."""
+        out, ptr = self._obs_out((self._n_obs,), torch_out)
+        self._check(self.lib.sg_future_collision_observers(self.h, float(horizon), int(n_samples), ptr, int(bool(torch_out))),
+                    "sg_future_collision_observers")
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+            return out
+        return out.astype(bool)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

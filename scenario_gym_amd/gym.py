@@ -12,7 +12,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .agent import _create_agent
+from .agent import CombinedSensor, FutureCollisionDetector, RasterizedMapSensor, _create_agent
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_scenarios
@@ -49,6 +49,9 @@ class BatchedScenarioGym:
         self._rec = None
         self._fut = None
         self._rss_cache = None
+        self._observers: list = []   # (scenario index, entity slot) of the non-ego entities that carry a map / look-ahead sensor
+        self._observer_of: dict = {}  # ... -> position in the engine's observer list
+        self._observers_sent = 0     # how many of them the engine knows
 
     # ------------------------------------------------------------------ properties
     @property
@@ -188,6 +191,7 @@ class BatchedScenarioGym:
         self.engine.upload(packed)
         self._packed = packed
         self.scenarios, self.states, self._host_agents, self._policy_agents = [], [], [], []
+        self._observers, self._observer_of, self._observers_sent = [], {}, 0
         self._roads_set = True
         self.metrics = [list(self.metric_factory()) for _ in range(packed.n_scenarios)]
         if any(not isinstance(m, _DeviceMetric) for m in self.metrics[0]):
@@ -271,6 +275,22 @@ class BatchedScenarioGym:
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
+        # the observers of the batch: every map / look-ahead sensor of a non-ego entity (inside a CombinedSensor too), so that
+        # one device call per step and sensor configuration serves all of them; a sensor met later joins when it is first stepped
+        self._observers, self._observer_of, self._observers_sent = [], {}, 0
+
+        def leaves(sensor):
+            if isinstance(sensor, CombinedSensor):
+                for s in sensor.sensors:
+                    yield from leaves(s)
+            elif sensor is not None:
+                yield sensor
+
+        for i, sc in enumerate(self.scenarios):
+            for a in agents[i].values():
+                for s in leaves(getattr(a, "sensor", None)):
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector)) and s.entity is not sc.ego and s.entity in sc.entities:
+                        self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
     def engine_models(self) -> int:
@@ -309,6 +329,45 @@ class BatchedScenarioGym:
                 self._set_road_networks()
             self._fut = dict(self._fut or {})
             self._fut[key] = self.engine.raster_map(codes, width, height, nw, nh)
+        return self._fut[key]
+
+    def _observer(self, i: int, slot: int) -> int:
+        """Position of entity `slot` of scenario `i` in the observer list; a new observer joins the list (and what was
+        computed for the shorter list is dropped)."""
+        k = self._observer_of.get((i, slot))
+        if k is None:
+            k = self._observer_of[(i, slot)] = len(self._observers)
+            self._observers.append((i, slot))
+            if self._fut:
+                self._fut = {key: v for key, v in self._fut.items() if key[0] not in ("obs_map", "obs_fut")}
+        return k
+
+    def _send_observers(self):
+        if self._observers_sent != len(self._observers):
+            scen, slot = zip(*self._observers)
+            self.engine.set_observers(scen, slot)
+            self._observers_sent = len(self._observers)
+
+    def _raster_map_observers(self, layers, width, height, nw, nh):
+        """[n_observers][n_layers][nh][nw] of RasterizedMapSensor layers in the frame of every registered observer: one device
+        call per state and sensor configuration, cached like _raster_map."""
+        from .road_network import LAYER_CODES
+        codes = tuple(LAYER_CODES[l] for l in layers)
+        key = ("obs_map", codes, width, height, nw, nh)
+        if self._fut is None or key not in self._fut:
+            if any(codes):
+                self._set_road_networks()
+            self._send_observers()
+            self._fut = dict(self._fut or {})
+            self._fut[key] = self.engine.raster_map_observers(codes, width, height, nw, nh)
+        return self._fut[key]
+
+    def _future_observers(self, horizon: float, n_samples: int):
+        key = ("obs_fut", horizon, n_samples)
+        if self._fut is None or key not in self._fut:
+            self._send_observers()
+            self._fut = dict(self._fut or {})
+            self._fut[key] = self.engine.future_collision_observers(horizon, n_samples)
         return self._fut[key]
 
     def _road_info(self, cap: int = 32):

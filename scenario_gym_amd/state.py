@@ -178,17 +178,32 @@ class State:
     def get_entity_box_points(self, e: Entity) -> np.ndarray:
         return e.get_bounding_box_points(self.poses[e])
 
-    def future_collision(self, horizon: float = 5.0, n_samples: int = 10) -> bool:
-        """FutureCollisionDetector(ego, horizon) at the current time (sensor/common.py:87-106), computed on the device."""
+    def _observer(self, entity: Optional[Entity]) -> Optional[int]:
+        """None for the ego (the per-scenario device calls answer), else the entity's place in the gym's observer list."""
+        if entity is None or entity is self._scenario.ego:
+            return None
+        return self._gym._observer(self._i, self._scenario.entities.index(entity))
+
+    def future_collision(self, horizon: float = 5.0, n_samples: int = 10, entity: Optional[Entity] = None) -> bool:
+        """FutureCollisionDetector(entity, horizon) at the current time (sensor/common.py:87-106), computed on the device;
+        entity: any entity of the scenario (default: the ego)."""
+        k = self._observer(entity)
+        if k is not None:
+            return bool(self._gym._future_observers(float(horizon), int(n_samples))[k])
         return bool(self._gym._future(float(horizon), int(n_samples))[self._i])
 
     def entity_raster(self, width: float = 20.0, height: float = 20.0, nw: int = 20, nh: int = 20) -> np.ndarray:
         """RasterizedMapSensor "entity" layer around the ego (sensor/map.py:120-192), computed on the device: bool [nh, nw]."""
         return self._gym._raster(float(width), float(height), int(nw), int(nh))[self._i]
 
-    def raster_map(self, layers, width: float = 20.0, height: float = 20.0, nw: int = 20, nh: int = 20) -> np.ndarray:
-        """RasterizedMapSensor layers around the ego (sensor/map.py:136-271; names of its `_all_layers`), computed on the
-        device from the scenario's road network: bool [n_layers, nh, nw]."""
+    def raster_map(self, layers, width: float = 20.0, height: float = 20.0, nw: int = 20, nh: int = 20,
+                   entity: Optional[Entity] = None) -> np.ndarray:
+        """RasterizedMapSensor layers around `entity` -- any entity of the scenario, default the ego (sensor/map.py:136-271;
+        names of its `_all_layers`) -- computed on the device from the scenario's road network: bool [n_layers, nh, nw]; all
+        False for an entity that is not in `poses`."""
+        k = self._observer(entity)
+        if k is not None:
+            return self._gym._raster_map_observers(tuple(layers), float(width), float(height), int(nw), int(nh))[k]
         return self._gym._raster_map(tuple(layers), float(width), float(height), int(nw), int(nh))[self._i]
 
     def get_road_info_at_entity(self, e: Entity):

@@ -58,6 +58,7 @@ class VectorScenarioEnv:
             self._mask |= {"max_length": L.TERM_MAX_LENGTH, "collision": L.TERM_COLLISION,
                            "ego_collision": L.TERM_EGO_COLLISION, "ego_off_road": L.TERM_EGO_OFF_ROAD}[c]
         self.done = np.zeros(self.n_envs, bool)
+        self._obs_env, self._obs_slot = np.zeros(0, np.int32), np.zeros(0, np.int32)  # set_observers
 
     @property
     def observation_shape(self):
@@ -110,6 +111,28 @@ class VectorScenarioEnv:
             return count[r, e], geoms[r, e], layers[r, e]
         r = np.arange(self.n_envs)
         return count[r, self._ego], geoms[r, self._ego], layers[r, self._ego]
+
+    def set_observers(self, slots):
+        """Entities other than (or beside) the ego that observe_entities() reports for: slots[i] = the entity indices
+        (positions in scenarios[i].entities) of environment i.  Replaces the previous list; all lists empty clears it."""
+        if len(slots) != self.n_envs:
+            raise ValueError("set_observers: one list of entity indices per environment")
+        env = [i for i, ks in enumerate(slots) for _ in ks]
+        slot = [int(k) for ks in slots for k in ks]
+        self.engine.set_observers(env, slot)
+        self._obs_env, self._obs_slot = np.array(env, np.int32), np.array(slot, np.int32)
+
+    def observe_entities(self):
+        """The map observation of every observer of set_observers at the current state, with the environment's layers and
+        geometry (sg_raster_map_observers): (obs [n, n_layers, n_px, n_px], env_of_observer [n], slot [n]).  torch_obs: torch
+        tensors in HBM; else numpy arrays (obs bool)."""
+        env, slot = self._obs_env, self._obs_slot
+        obs = self.engine.raster_map_observers(self._codes, self.width, self.height, self.n, self.n, torch_out=self.torch_obs)
+        if self.torch_obs:
+            import torch
+
+            return obs, torch.as_tensor(env, device=obs.device), torch.as_tensor(slot, device=obs.device)
+        return obs, env, slot
 
     def close(self):
         self.engine.close()

@@ -32,6 +32,7 @@ GENERATORS = {
     "make_golden_json": ["json", "elevation"],
     "make_golden_long": ["long"],
     "make_golden_mixed_peds": ["mixed_peds"],
+    "make_golden_observers": ["observers"],
     "make_golden_ped_noise": ["ped_noise"],
     "make_golden_ped_roads": ["ped_roads"],
     "make_golden_random_walk": ["random_walk"],
