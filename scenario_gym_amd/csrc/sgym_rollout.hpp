@@ -259,6 +259,16 @@ __device__ __forceinline__ void rollout_body_l(
     // slope) do not exist.
     static_assert(!PLANAR || (TAB && WV == 1 && !SLICE), "planar: the table variant");
     constexpr bool planar = PLANAR;
+    // LATE (the table variants outside a sliced replay): nothing reads a state row while the call runs -- the pre-pass reads
+    // p.dyn before the first step only -- so the step loop does not store the pose, distance, presence and collision rows: the
+    // registers hold them, and they are stored once where the loop is left ("write back what lives in registers").  The
+    // velocity rows hold the velocity of the last step a lane committed WHILE PRESENT, which the registers do not keep: a step
+    // computes and stores them only if it can be that step (see vel_every_step and need_vel below).
+    constexpr bool LATE = TAB && !SLICE;
+    // PARK (the LATE entry points under the 168-register cap: one wavefront per tile, controlled lanes): the ego metric
+    // accumulators wait in the lane's column of lds.ctrl -- a table variant has no controller parameters there -- between their
+    // uses.  A table ego's come with its table and are never touched by a step; any other ego's are read and written once per step.
+    constexpr bool PARK = LATE && HAST && WV == 1;
     // register-resident across the time loop
     double pose[6], dist, t, prev_t;
     double velx = 0.0, vely = 0.0; // current velocity (social force input), PED only
@@ -390,6 +400,7 @@ __device__ __forceinline__ void rollout_body_l(
     }
     // (crowd variants -- one scenario, one ego per workgroup: the ego's accumulators live in LDS between their uses, see TileLds)
     auto ego_park = [&]() {
+        if (PARK) { lds.ctrl[0][sl] = m_avg; lds.ctrl[1][sl] = m_max; lds.ctrl[2][sl] = m_t; } // (own column: no barrier)
         if (CROWD && is_ego) {
             lds.ego_m[0] = m_avg; lds.ego_m[1] = m_max; lds.ego_m[2] = m_t;
 #pragma unroll
@@ -398,6 +409,7 @@ __device__ __forceinline__ void rollout_body_l(
         }
     };
     auto ego_fetch = [&]() {
+        if (PARK) { m_avg = lds.ctrl[0][sl]; m_max = lds.ctrl[1][sl]; m_t = lds.ctrl[2][sl]; }
         if (CROWD && is_ego) {
             m_avg = lds.ego_m[0]; m_max = lds.ego_m[1]; m_t = lds.ego_m[2];
 #pragma unroll
@@ -591,6 +603,33 @@ __device__ __forceinline__ void rollout_body_l(
     int k = 0;
     bool all_done = false;
     bool vel_clean_prev = false; // wave-uniform
+    // LATE, wave-uniform: every step's velocities are wanted -- an ego that is not a table lane takes its speed metrics from them
+    // step by step, and a terminal condition that is decided after the collision pass can make any step the scenario's last
+    const bool vel_every_step = !LATE || (p.term_mask & ~SG_TERM_MAX_LENGTH) != 0 || sg_any(is_ego && !tab_lane);
+    // LATE: the state rows are stored where few steps come by.  What only those places need is formed there again -- the
+    // addresses of the rows past the first eight (two additions), the scenario record's (one multiply-add), the table column
+    // (one load) -- instead of waiting in registers through every step: the 168 hold the step loop with nothing to spare.
+    auto rows_again = [](const LanePtr &o) {
+        LanePtr q = o;
+        if (LATE) {
+            asm volatile("" : "+v"(q.a[0]));
+            q.a[1] = q.a[0] + 8 * ROW;
+            q.a[2] = q.a[0] + 16 * ROW;
+        }
+        return q;
+    };
+    auto dy_again = [&]() { // (the block's first row as well: base + lane offset)
+        if (!LATE) return dy;
+        uint32_t voff_o = voff;
+        asm volatile("" : "+v"(voff_o));
+        return LanePtr(p.dyn + blk * ((size_t)(SG_F_COLL + WV) * 64), voff_o);
+    };
+    auto sd_again = [&]() -> sg_scenario_state & {
+        if (!LATE) return sd;
+        uint32_t r_o = r;
+        asm volatile("" : "+v"(r_o));
+        return p.sdyn[r_o];
+    };
     PhaseTimers ptm;
 #ifdef SG_PHASE_TIMERS
     ptm.start();
@@ -655,6 +694,7 @@ __device__ __forceinline__ void rollout_body_l(
 
         // ---- new poses: scenario_gym.py:233-245 ----
         bool npres = false;
+        bool need_vel = true; // wave-uniform (LATE): does this step compute and store its velocities?
         double fpx = 0.0, fpy = 0.0; // PedestrianAgent.force
         bool ped_go = false;
         double ped_fx = 0.0, ped_fy = 0.0, ped_vdes = 0.0;
@@ -749,6 +789,12 @@ __device__ __forceinline__ void rollout_body_l(
             const bool np_replay = replay_always | in_window;
             const bool np_agent = present | (min_t >= t);
             npres = (is_replay & np_replay) | (is_agent & np_agent);
+            if (LATE && !vel_every_step && k != n_steps - 1) { // can this step's velocities be seen?  (see the velocity phase)
+                const double next2_t = next_t + timestep;
+                const bool ends = (p.term_mask & SG_TERM_MAX_LENGTH) && (next_t + dt > length);
+                const bool leaves = is_replay & !(replay_always | ((next2_t >= min_t) & (next2_t <= max_t)));
+                need_vel = sg_any(run & npres & (ends | leaves));
+            }
             if (has_tab) {
                 const bool take = tab_lane & present & run;
 #pragma unroll
@@ -872,8 +918,16 @@ __device__ __forceinline__ void rollout_body_l(
         // are skipped -- and the state blocks already hold these pose rows (and, after one flat step, the +0 velocity
         // rows): they are not stored again.  Memory stays the exact step-materialised state; a steady step issues 9
         // row stores instead of 15.
-        bool flat;
-        {
+        // LATE: the velocity rows keep what the last step stored into them in which the lane ran and was present, so this
+        // step's velocities can be seen only if no such step follows it in this call: it is the call's last step, or it ends
+        // the lane's scenario (`done` by max_length is known here: the test below the collision pass, t + dt > length, is made
+        // on the clock this step commits; every other terminal condition sets vel_every_step), or the lane leaves the scene at
+        // the next step -- a replay lane outside its window at the next clock, formed by the additions of that step itself;
+        // agent lanes stay once present.  One vote per step; where nobody's velocity can be seen, the divisions, their range
+        // checks and the six row stores are skipped.  A step that stores without need stores the values the step has.
+        // (the vote itself: beside the presence rule above, where fewer registers are live)
+        bool flat = false;
+        if (need_vel) {
             RecipDiv rd(dt);
             if (planar) {
                 flat = !SLICE && sg_all(dt > 0.0);
@@ -933,7 +987,13 @@ __device__ __forceinline__ void rollout_body_l(
                                      (was_present && steps > 1) ? 1.0 - prev_t / t : __builtin_nan(""));
             }
             // ---- step-materialised state (everything except the collision row, see below) ----
-            if (!SLICE || (sa.mode == 1 && !warm)) {
+            if (LATE) { // every velocity row of the steps whose velocities can be seen; the other rows where the loop is left
+                if (need_vel && present) {
+                    const LanePtr dv = dy_again();
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) stf(dv, SG_F_VEL + c, vel[c]);
+                }
+            } else if (!SLICE || (sa.mode == 1 && !warm)) {
             stf(dy, SG_F_POSE + 0, pose[0]); stf(dy, SG_F_POSE + 1, pose[1]); stf(dy, SG_F_POSE + 3, pose[3]);
             if (!flat) { stf(dy, SG_F_POSE + 2, pose[2]); stf(dy, SG_F_POSE + 4, pose[4]); stf(dy, SG_F_POSE + 5, pose[5]); }
             if (present) {
@@ -959,17 +1019,19 @@ __device__ __forceinline__ void rollout_body_l(
 #pragma unroll
                 for (int c = 0; c < 6; ++c)
                     p.rec_pose[((size_t)steps * 6 + c) * p.R * p.EP + (size_t)r * p.EP + slot] = present ? pose[c] : absent;
-                if (slot == 0) { p.rec_t[(size_t)steps * p.R + r] = t; sd.rec_rows = steps + 1; }
+                if (slot == 0) { p.rec_t[(size_t)steps * p.R + r] = t; sd_again().rec_rows = steps + 1; }
             }
             // ---- ego metrics, scenario_gym.py:251-252 ----
             if (!SLICE && is_ego && present && !tab_lane) { // a controlled ego's metrics come with its table (control_kernel)
                 if (CROWD) { m_avg = lds.ego_m[0]; m_max = lds.ego_m[1]; m_t = lds.ego_m[2]; }
+                if (PARK) ego_fetch();
                 double speed = sg_norm3(vel[0], vel[1], vel[2]);
                 double w = m_t / t; // EgoAvgSpeed._step, metrics/trajectory.py:19-24
                 m_avg += (1.0 - w) * (speed - m_avg);
                 m_t = t;
                 m_max = __builtin_fmax(speed, m_max); // EgoMaxSpeed, :41-44
                 if (CROWD) { lds.ego_m[0] = m_avg; lds.ego_m[1] = m_max; lds.ego_m[2] = m_t; }
+                if (PARK) ego_park();
             }
         }
         PH(1);
@@ -980,8 +1042,9 @@ __device__ __forceinline__ void rollout_body_l(
         if (run) {
 #pragma unroll
             for (int w = 0; w < WV; ++w) {
-                // (likewise the collision row: stored when it differs from the stored one in some lane of the wavefront)
-                const bool row_moved = SLICE || sg_any(nrow[w] != row[w]);
+                // (likewise the collision row: stored when it differs from the stored one in some lane of the wavefront;
+                // LATE: where the loop is left)
+                const bool row_moved = !LATE && (SLICE || sg_any(nrow[w] != row[w]));
                 row[w] = nrow[w];
                 if ((!SLICE || (sa.mode == 1 && !warm)) && row_moved) stf(dy, SG_F_COLL + w, row[w]);
             }
@@ -1150,13 +1213,26 @@ __device__ __forceinline__ void rollout_body_l(
     if (RSSV && lane == 0) p.rssq_n[rss_wave] = min(rss_gn, p.rssq_cap);
     // ---- write back what lives in registers during the loop ----
     if (in_range) {
+        const LanePtr dx = dy_again();
+        sg_scenario_state &sx = sd_again();
         if (PED && kind == SG_KIND_AGENT_PEDESTRIAN) cs.e_lon_prev = (double)goal_idx;
+        if (LATE) {
+            // the rows the step loop left in registers, however it was left (all steps run, every scenario of the wavefront
+            // done -- each lane holds the state of ITS scenario's last step --, nothing run at all: the rows as they were loaded)
+            stf(dx, SG_F_POSE + 0, pose[0]); stf(dx, SG_F_POSE + 1, pose[1]); stf(dx, SG_F_POSE + 3, pose[3]);
+            if (!PLANAR) { stf(dx, SG_F_POSE + 2, pose[2]); stf(dx, SG_F_POSE + 4, pose[4]); stf(dx, SG_F_POSE + 5, pose[5]); }
+            stf(dx, SG_F_DIST, dist);
+            stf(dx, SG_F_PRESENT, (uint64_t)present);
+#pragma unroll
+            for (int w = 0; w < WV; ++w) stf(dx, SG_F_COLL + w, row[w]);
+        }
         if (TAB) {
             if (tab_lane && last_k >= 0) { // controller state after the last executed step
-                const double *lr = tab + (size_t)ctl_q * tab_lane_stride + (size_t)last_k * CT_W;
+                const int64_t ctl_x = fld<int64_t>(rows_again(st), ST_CTL); // (= ctl_q: loaded again, see rows_again)
+                const double *lr = tab + (size_t)ctl_x * tab_lane_stride + (size_t)last_k * CT_W;
                 const double *lr1 = lr + (size_t)p.n_ctl_pad * tab_lane_stride; // plane 1
-                stf(dy, SG_F_CTRL + 0, lr[CT_SPEED]); stf(dy, SG_F_CTRL + 1, lr1[CT_ELON]);
-                stf(dy, SG_F_CTRL + 2, lr1[CT_ELAT]); stf(dy, SG_F_CTRL + 3, lr1[CT_EINT]);
+                stf(dx, SG_F_CTRL + 0, lr[CT_SPEED]); stf(dx, SG_F_CTRL + 1, lr1[CT_ELON]);
+                stf(dx, SG_F_CTRL + 2, lr1[CT_ELAT]); stf(dx, SG_F_CTRL + 3, lr1[CT_EINT]);
                 if (is_ego) { // ego metrics after the last executed step
                     const double *lr2 = lr1 + (size_t)p.n_ctl_pad * tab_lane_stride; // plane 2
                     m_avg = lr2[CT_MAVG]; m_max = lr2[CT_MMAX]; m_t = lr2[CT_MT];
@@ -1166,14 +1242,14 @@ __device__ __forceinline__ void rollout_body_l(
             if (last_k >= 0 && (kind == SG_KIND_AGENT_PID || kind == SG_KIND_AGENT_VEHICLE)) { // controller state after the last executed step
                 const double *lr = rider_row + (size_t)last_k * CT_W;
                 const double *lr1 = lr + (size_t)p.n_ctl_pad * tab_lane_stride; // plane 1
-                stf(dy, SG_F_CTRL + 0, lr[CT_SPEED]); stf(dy, SG_F_CTRL + 1, lr1[CT_ELON]);
-                stf(dy, SG_F_CTRL + 2, lr1[CT_ELAT]); stf(dy, SG_F_CTRL + 3, lr1[CT_EINT]);
+                stf(dx, SG_F_CTRL + 0, lr[CT_SPEED]); stf(dx, SG_F_CTRL + 1, lr1[CT_ELON]);
+                stf(dx, SG_F_CTRL + 2, lr1[CT_ELAT]); stf(dx, SG_F_CTRL + 3, lr1[CT_EINT]);
             }
         } else {
-            stf(dy, SG_F_CTRL + 0, cs.speed); stf(dy, SG_F_CTRL + 1, cs.e_lon_prev);
-            stf(dy, SG_F_CTRL + 2, cs.e_lat_prev); stf(dy, SG_F_CTRL + 3, cs.e_lon_int);
+            stf(dx, SG_F_CTRL + 0, cs.speed); stf(dx, SG_F_CTRL + 1, cs.e_lon_prev);
+            stf(dx, SG_F_CTRL + 2, cs.e_lat_prev); stf(dx, SG_F_CTRL + 3, cs.e_lon_int);
         }
-        if (slot == 0) { sd.t = t; sd.prev_t = prev_t; sd.done = done; sd.n_steps = steps; if (PED) sd.noise_pos = noise_pos; }
+        if (slot == 0) { sx.t = t; sx.prev_t = prev_t; sx.done = done; sx.n_steps = steps; if (PED) sx.noise_pos = noise_pos; }
         if (RSSV) {
             if (slot < p.E) { // (markers in rss_st / rss_cd: rss_lines_kernel finishes them)
                 p.rss_state[rss_idx] = rss_st;
@@ -1186,11 +1262,11 @@ __device__ __forceinline__ void rollout_body_l(
             if (slot == 0 && rss_touched) p.rss_seen[r] = steps;
         }
         if (is_ego) {
-            sd.ego_avg_speed = m_avg; sd.ego_max_speed = m_max; sd.avg_t = m_t;
-            if (steps > 0 && present) sd.ego_distance_travelled = dist; // EgoDistanceTravelled, :60-62
+            sx.ego_avg_speed = m_avg; sx.ego_max_speed = m_max; sx.avg_t = m_t;
+            if (steps > 0 && present) sx.ego_distance_travelled = dist; // EgoDistanceTravelled, :60-62
 #pragma unroll
-            for (int w = 0; w < WV; ++w) (w < 4 ? sd.last_row[w & 3] : sd.last_row_hi[w & 3]) = last_row[w];
-            sd.n_events = n_ev;
+            for (int w = 0; w < WV; ++w) (w < 4 ? sx.last_row[w & 3] : sx.last_row_hi[w & 3]) = last_row[w];
+            sx.n_events = n_ev;
         }
     }
 }
