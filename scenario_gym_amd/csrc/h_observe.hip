@@ -1,0 +1,320 @@
+// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map and look-ahead observations of the
+// ego and of a list of observers.
+#include "sgym_host.hpp"
+
+using namespace sgh;
+
+// device scratch shared by the observation entry points: a tick of an RL loop calls them once per step, a hipMalloc /
+// hipFree pair per call would cost more than the kernels
+static int obs_scratch(sg_handle *h, size_t bytes, unsigned char **out)
+{
+    if (bytes > h->obs.cap) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (const int rc = h->obs.ensure(h, bytes)) return rc;
+        ++h->generation;
+    }
+    *out = h->obs.as<unsigned char>();
+    return SG_OK;
+}
+
+// the layer codes of a map observation: 0 (the entities) or one SG_LAYER_* bit each; *any_surface: some layer is a surface
+static int check_layers(sg_handle *h, const char *who, int32_t n_layers, const int32_t *layers, bool *any_surface)
+{
+    *any_surface = false;
+    for (int k = 0; k < n_layers; ++k) {
+        const uint32_t L = (uint32_t)layers[k];
+        if (layers[k] < 0 || L > 255u || (L & (L - 1))) return fail(h, SG_ERR_INVALID, "%s: layers[%d]=%d is not 0 or one SG_LAYER_* bit", who, k, layers[k]);
+        *any_surface = *any_surface || L != 0;
+    }
+    return SG_OK;
+}
+
+// The map layers of every scenario into d = [R][n_layers][nh][nw] on the handle's stream: the entity layers one by one
+// (raster_kernel), the surfaces in one launch (raster_surface_kernel; dl: the layer codes on the device), empty surfaces
+// without road networks.  Returns the first HIP error and enqueues nothing after it (sg_tick calls this while capturing).
+static hipError_t enqueue_map_layers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers, const int32_t *layers,
+                                     bool any_surface, const int32_t *dl, unsigned char *d)
+{
+    const size_t plane = (size_t)nw * nh, bytes = (size_t)h->R * n_layers * plane;
+    hipError_t e = hipSuccess;
+    if (any_surface && !h->has_road) e = hipMemsetAsync(d, 0, bytes, h->stream); // no networks: empty surfaces
+    for (int k = 0; k < n_layers && e == hipSuccess; ++k)
+        if (layers[k] == 0) {
+            sgl::raster(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, width, height, nw, nh, d + (size_t)k * plane,
+                        (int64_t)(n_layers * plane));
+            e = hipGetLastError();
+        }
+    if (any_surface && h->has_road && e == hipSuccess) {
+        sgl::raster_surface(dim3((unsigned)h->R), h->stream, h->p, h->road, width, height, nw, nh, n_layers, dl, d);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+// the raster kernels of sg_raster_map / sg_raster_map_device on the handle's stream; *d_out = [R][n_layers][nh][nw]
+static int raster_map_launch(sg_handle *h, const char *who, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                             const int32_t *layers, unsigned char **d_out, size_t *bytes_out)
+{
+    if (!layers || n_layers < 1 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+        return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    bool any_surface = false;
+    int rc = check_layers(h, who, n_layers, layers, &any_surface);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t bytes = (size_t)h->R * n_layers * nw * nh, lay_off = (bytes + 15) & ~(size_t)15;
+    unsigned char *d = nullptr;
+    rc = obs_scratch(h, lay_off + (size_t)n_layers * sizeof(int32_t), &d);
+    if (rc) return rc;
+    int32_t *dl = reinterpret_cast<int32_t *>(d + lay_off);
+    HIP_TRY(h, hipMemcpyAsync(dl, layers, (size_t)n_layers * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, any_surface, dl, d));
+    *d_out = d;
+    *bytes_out = bytes;
+    return SG_OK;
+}
+
+extern "C" int sg_raster_map(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                             const int32_t *layers, uint8_t *out)
+{
+    if (!h || !out) return h ? fail(h, SG_ERR_INVALID, "sg_raster_map: bad argument") : SG_ERR_INVALID;
+    unsigned char *d = nullptr;
+    size_t bytes = 0;
+    int rc = raster_map_launch(h, "sg_raster_map", width, height, nw, nh, n_layers, layers, &d, &bytes);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (const int rcq = check_queue(h)) return rcq; // (a persistent launch that gave up: sticky)
+    return SG_OK;
+}
+
+extern "C" int sg_raster_map_device(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                                    const int32_t *layers, const uint8_t **d_out)
+{
+    if (!h || !d_out) return h ? fail(h, SG_ERR_INVALID, "sg_raster_map_device: bad argument") : SG_ERR_INVALID;
+    unsigned char *d = nullptr;
+    size_t bytes = 0;
+    int rc = raster_map_launch(h, "sg_raster_map_device", width, height, nw, nh, n_layers, layers, &d, &bytes);
+    if (rc) return rc;
+    *d_out = d;
+    return SG_OK;
+}
+
+extern "C" int sg_raster_entities(sg_handle *h, double width, double height, int32_t nw, int32_t nh, uint8_t *out)
+{
+    if (!h || !out || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+        return h ? fail(h, SG_ERR_INVALID, "sg_raster_entities: bad argument") : SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_entities: no scenarios uploaded");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t bytes = (size_t)h->R * nw * nh;
+    unsigned char *d = nullptr;
+    int rc = obs_scratch(h, bytes, &d);
+    if (rc) return rc;
+    sgl::raster(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, width, height, nw, nh, d, (int64_t)nw * nh);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_raster_entities: %s", hipGetErrorString(e));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+// One tick of the RL loop (integrations/openaigym.py:171-226) as ONE graph launch: the step with the policy's actions, the
+// terminal conditions of the new state, the map observation.  Four short kernels whose launch and synchronisation
+// overheads exceed their run time when issued one by one; captured once per (batch, observation geometry) and replayed.
+extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_device, double width, double height, int32_t nw,
+                       int32_t nh, int32_t n_layers, const int32_t *layers, const uint8_t **d_obs, const uint32_t **d_flags)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_tick: no scenarios uploaded");
+    if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+        return fail(h, SG_ERR_INVALID, "sg_tick: bad observation geometry (1..8 layers)");
+    if (h->n_ext > 0) return fail(h, SG_ERR_STATE, "sg_tick: batches with caller-run agents are driven through sg_set_external_poses + sg_step");
+    bool any_surface = false, grew = false;
+    int rc = check_layers(h, "sg_tick", n_layers, layers, &any_surface);
+    if (rc) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // fixed device addresses for everything the graph's kernels read or write
+    const size_t n_act = (size_t)h->R * 2;
+    if ((rc = ensure_actions(h, n_act, &grew))) return rc;
+    if (grew) ++h->generation;
+    if ((rc = h->term_flags.ensure(h, (size_t)h->R * sizeof(uint32_t), &grew))) return rc;
+    if (grew) ++h->generation;
+    double *const d_actions = h->actions.as<double>();
+    uint32_t *const d_term_flags = h->term_flags.as<uint32_t>();
+    const size_t bytes = (size_t)h->R * n_layers * nw * nh, lay_off = (bytes + 15) & ~(size_t)15;
+    unsigned char *d = nullptr;
+    if ((rc = obs_scratch(h, lay_off + 8 * sizeof(int32_t), &d))) return rc;
+    int32_t *dl = reinterpret_cast<int32_t *>(d + lay_off);
+    // sg_set_rss: the callback runs after the step, inside the captured launch (like sg_step; without records of a reset --
+    // the callback was switched on after sg_upload -- through sg_rss_update after the graph)
+    if (h->wide && (rc = ensure_wide(h))) return rc;
+    bool rss_tick = false; // (allocations stay outside the capture)
+    if ((rc = rss_fused_call(h, true, &rss_tick))) return rc;
+    const bool same = h->tick_exec && h->tick_gen == h->generation && h->tick_w == width && h->tick_h == height &&
+                      h->tick_rss == rss_tick && h->tick_nw == nw && h->tick_nh == nh && h->tick_nl == n_layers &&
+                      std::equal(layers, layers + n_layers, h->tick_layers);
+    if (!same) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (const int rcq = check_queue(h)) return rcq; // (a persistent launch that gave up: sticky)
+        if (h->tick_exec) { HIP_TRY(h, hipGraphExecDestroy(h->tick_exec)); h->tick_exec = nullptr; }
+        HIP_TRY(h, hipMemcpy(dl, layers, (size_t)n_layers * sizeof(int32_t), hipMemcpyHostToDevice));
+        hipGraph_t graph = nullptr;
+        HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+        // the step as sg_step runs it, never on the table path (one step: not timed); launch_plan does not synchronise
+        rc = launch_plan(h, plan_call(h, 1, rss_tick, false), 1, 0, 1, d_actions);
+        hipError_t e = hipSuccess;
+        if (!rc && h->wide) {
+            // scenarios of more than 512 entities: the entity layers tile by tile (raster_kernel), empty surfaces (no road
+            // networks at this width), the terminal conditions by the kernel of sg_terminal_flags
+            e = enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, any_surface, dl, d);
+            if (e == hipSuccess) {
+                sgl::terminal_flags(dim3((unsigned)h->R), h->stream, h->p, h->cfg.timestep, d_term_flags);
+                e = hipGetLastError();
+            }
+        } else if (!rc) { // the whole observation (map layers + terminal flags) in one launch
+            sgl::observe(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, h->road, h->has_road ? 1 : 0, width, height, nw, nh,
+                         n_layers, dl, d, d_term_flags);
+            e = hipGetLastError();
+        }
+        hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess || e2 != hipSuccess) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return fail(h, SG_ERR_HIP, "sg_tick: capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        }
+        e = hipGraphInstantiate(&h->tick_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (e != hipSuccess) { h->tick_exec = nullptr; return fail(h, SG_ERR_HIP, "sg_tick: hipGraphInstantiate: %s", hipGetErrorString(e)); }
+        h->tick_gen = h->generation;
+        h->tick_rss = rss_tick;
+        h->tick_w = width; h->tick_h = height; h->tick_nw = nw; h->tick_nh = nh; h->tick_nl = n_layers;
+        std::copy(layers, layers + n_layers, h->tick_layers);
+    }
+    if (actions)
+        HIP_TRY(h, hipMemcpyAsync(d_actions, actions, n_act * sizeof(double), actions_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    else
+        HIP_TRY(h, hipMemsetAsync(d_actions, 0, n_act * sizeof(double), h->stream));
+    HIP_TRY(h, hipGraphLaunch(h->tick_exec, h->stream));
+    if (h->rss_enabled && !rss_tick && (rc = sg_rss_update(h, 0))) return rc;
+    h->timed = false;
+    if (d_obs) *d_obs = d;
+    if (d_flags) *d_flags = d_term_flags;
+    return SG_OK;
+}
+
+extern "C" int sg_terminal_flags(sg_handle *h, uint32_t *out, const uint32_t **d_out)
+{
+    if (!h || (!out && !d_out)) return h ? fail(h, SG_ERR_INVALID, "sg_terminal_flags: no output given") : SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_terminal_flags: no scenarios uploaded");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (const int rc = h->term_flags.ensure(h, (size_t)h->R * sizeof(uint32_t))) return rc;
+    uint32_t *const d_term_flags = h->term_flags.as<uint32_t>();
+    sgl::terminal_flags(dim3((unsigned)h->R), h->stream, h->p, h->cfg.timestep, d_term_flags);
+    HIP_TRY(h, hipGetLastError());
+    if (out) {
+        HIP_TRY(h, hipMemcpyAsync(out, d_term_flags, (size_t)h->R * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (const int rcq = check_queue(h)) return rcq; // (a persistent launch that gave up: sticky)
+    }
+    if (d_out) *d_out = d_term_flags;
+    return SG_OK;
+}
+
+extern "C" int sg_future_collision(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out)
+{
+    if (!h || !out || n_samples < 1 || !(horizon >= 0.0)) return h ? fail(h, SG_ERR_INVALID, "sg_future_collision: bad argument") : SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_future_collision: no scenarios uploaded");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    unsigned char *d = nullptr;
+    int rc = obs_scratch(h, (size_t)h->R, &d);
+    if (rc) return rc;
+    sgl::future(dim3((unsigned)h->R), h->stream, h->p, horizon, n_samples, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, (size_t)h->R, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_future_collision: %s", hipGetErrorString(e));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+// ---- observations for any entity: a list of observers (sgym_observers.hpp) -----------------------------------------------
+// the sticky give-up of check_queue for a call that does not wait for the stream: a launch still running is judged by the
+// next call that synchronises
+static int queue_gave_up(sg_handle *h) { return h->q_failed ? fail(h, SG_ERR_HIP, "%s", h->q_msg) : SG_OK; }
+
+// the observer list on the device: the scenarios in the first half of the buffer, the slots in the second
+static int32_t *observer_scenarios(const sg_handle *h) { return h->observers.as<int32_t>(); }
+static int32_t *observer_slots(const sg_handle *h) { return h->observers.as<int32_t>() + h->observers.cap / (2 * sizeof(int32_t)); }
+
+extern "C" int sg_set_observers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot)
+{
+    if (!h) return SG_ERR_INVALID;
+    h->n_obs = 0; // a refused call leaves the handle without observers
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_set_observers: no scenarios uploaded");
+    if (n < 0 || (n > 0 && (!scenario || !slot))) return fail(h, SG_ERR_INVALID, "sg_set_observers: n < 0 or null array");
+    if (n > 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "sg_set_observers: more than 2^31 - 1 observers (one workgroup each: the grid limit)");
+    for (int64_t k = 0; k < n; ++k) {
+        if (scenario[k] < 0 || scenario[k] >= h->R) return fail(h, SG_ERR_INVALID, "sg_set_observers: scenario[%lld]=%d out of range", (long long)k, scenario[k]);
+        if (slot[k] < 0 || slot[k] >= h->E) return fail(h, SG_ERR_INVALID, "sg_set_observers: slot[%lld]=%d out of range", (long long)k, slot[k]);
+        if (h->slot_empty[(size_t)scenario[k] * h->E + slot[k]])
+            return fail(h, SG_ERR_INVALID, "sg_set_observers: slot %d of scenario %d holds no entity (SG_KIND_NONE)", slot[k], scenario[k]);
+    }
+    if (n == 0) return SG_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued observation call may still read the previous list)
+    if (const int rc = h->observers.ensure(h, (size_t)n * 2 * sizeof(int32_t))) return rc;
+    HIP_TRY(h, hipMemcpy(observer_scenarios(h), scenario, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(observer_slots(h), slot, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->n_obs = n;
+    return SG_OK;
+}
+
+extern "C" int sg_raster_map_observers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                                       const int32_t *layers, uint8_t *out, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+        return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_map_observers: no scenarios uploaded");
+    bool any_surface = false;
+    if (const int rc = check_layers(h, "sg_raster_map_observers", n_layers, layers, &any_surface)) return rc;
+    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!out) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: null out");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
+    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
+        sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, out);
+        HIP_TRY(h, hipGetLastError());
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    const size_t bytes = (size_t)h->n_obs * n_layers * nw * nh;
+    unsigned char *d = nullptr;
+    if (int rc = obs_scratch(h, bytes, &d)) return rc;
+    sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, d);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    if (n_samples < 1 || !(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: bad argument");
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_future_collision_observers: no scenarios uploaded");
+    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!out) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: null out");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
+    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
+        sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, out);
+        HIP_TRY(h, hipGetLastError());
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    unsigned char *d = nullptr;
+    if (int rc = obs_scratch(h, (size_t)h->n_obs, &d)) return rc;
+    sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, d);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, d, (size_t)h->n_obs, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}

@@ -2,7 +2,8 @@
 //
 // libsgym_hip.so is linked from one object per kernel family (k_*.hip: `make -j` compiles them side by side, and an
 // experiment on one family rebuilds one object); every object includes sgym_device.hpp and instantiates only the entry
-// points its launcher names.  sgym_hip.hip (the C ABI + the setup / sensor / fix-up kernels) calls the launchers below.
+// points its launcher names.  The host units (sgym_hip.hip and h_*.hip: the C ABI, sgym_host.hpp) call the launchers below and
+// hold no kernel themselves; the setup / sensor / fix-up kernels are k_main.hip's.
 // Tile shapes: WV == 1 with G in {4, 8, 16, 32, 64} lanes per scenario, or G == 64 with WV in {2, 4} wavefronts per
 // scenario (the plain variant also 8).
 #pragma once
@@ -64,6 +65,26 @@ void rollout_slice(int G, dim3 grid, hipStream_t s, const sg::Params &p, double 
 enum { CTL_GENERAL = 0, CTL_RIDERS = 1, CTL_FAST = 2 };
 void control(int which, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int n_steps, int first, int k0,
              const double *actions, double *tab, int row0, int metrics);
+// k_main.hip: the setup / sensor / fix-up kernels, one launcher per kernel (the block is an argument where the call sites differ)
+void event_ego_pose(dim3 grid, hipStream_t s, const sg::Params &p, const sg::TabGroups &tg);
+void terminal_flags(dim3 grid, hipStream_t s, const sg::Params &p, double timestep, uint32_t *out);
+void classify_events(dim3 grid, hipStream_t s, const sg::Params &p, double c_tol);
+void rss(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, int reset, int32_t *rss_state, int32_t *code, double *safe, int32_t *seen);
+void ego_off_road(dim3 grid, hipStream_t s, const sg::Params &p);
+void replay_fixup(int G, dim3 grid, hipStream_t s, const sg::Params &p, const sg::SliceArgs &sa, const int *n_final);
+void replay_scenario_fixup(dim3 grid, hipStream_t s, const sg::Params &p, const sg::SliceArgs &sa, const int *n_final, const int *done_in);
+void slice_final(dim3 grid, hipStream_t s, const sg::Params &p, const sg::SliceArgs &sa, int *n_final, int *done_out);
+void clock(dim3 grid, hipStream_t s, const double *t0, int n_clocks, double timestep, int n_total, double *tt);
+void delay(hipStream_t s, long long ticks); // (tests) one wavefront that does nothing for `ticks` of the 100 MHz clock
+void build_grid(dim3 grid, hipStream_t s, const sg::Params &p, const int32_t *row_scen, int64_t row0, int64_t row_end);
+void raster(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, double width, double height, int nw, int nh, unsigned char *out,
+            int64_t stride);
+void raster_surface(dim3 grid, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, double width, double height, int nw, int nh,
+                    int n_layers, const int32_t *layers, unsigned char *out);
+void observe(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, int has_road, double width, double height,
+             int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out, uint32_t *flags);
+void future(dim3 grid, hipStream_t s, const sg::Params &p, double horizon, int n_samples, unsigned char *out);
+void trig32(dim3 grid, hipStream_t s, const double *h, float *sin_out, float *cos_out, int64_t n);
 
 } // namespace sgl
 

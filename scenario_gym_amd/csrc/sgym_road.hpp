@@ -11,7 +11,7 @@ namespace sg {
 // crosses the polygon's rings an odd number of times; a point ON a ring is not contained.  The orientation sign is
 // exact: fp64 determinant with Shewchuk's stage-A error bound, else the six products of the expanded determinant as
 // two-term expansions, summed exactly (grow-expansion); the sign of the sum is the sign of its largest component.
-// Host and device share these functions (the host uses them to classify the grid cells, sgym_hip.hip).
+// Host and device share these functions (the host uses them to classify the grid cells, h_road.hip).
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline void rn_two_sum(double a, double b, double &s, double &e)
 {

@@ -39,14 +39,14 @@ __device__ __forceinline__ Table lane_table(const Params &p, int kind, const Sce
 // TAB: the PID / vehicle agents were integrated by control_kernel; their lanes read (x, y, h) per step from
 // its table `tab` instead of running the controller with 1 of 64 lanes active.  TAB launches never reset.
 // Register budget of the one-wavefront-per-tile entry points (rollout_kernel_tab / _tab_planar): 168 VGPRs, three
-// wavefronts per SIMD; the pre-pass takes a wavefront slot of its own (sgym_hip.hip, launch_rollout).
+// wavefronts per SIMD; the pre-pass takes a wavefront slot of its own (h_queue.hip, launch_table).
 // HAST (TAB only): the batch has controlled lanes, i.e. there is a table to replay; without it the table code is
 // compiled out (batches of replay entities only: the C2 shape).
 // ROAD: the ego_off_road terminal condition is compiled in (its own entry point, rollout_kernel_road: the other
 // variants keep their register budgets).
 // RSSV: the RSSDistances callback (rss_entity) runs after the reset and after every step inside the kernel.
 // ------------------------------------------------------------------------------------------------
-// Time-sliced replay (launch_sliced in sgym_hip.hip): a batch whose lanes are all replay entities / replay agents is a
+// Time-sliced replay (launch_sliced in h_slice.hip): a batch whose lanes are all replay entities / replay agents is a
 // pure function of the clock -- pose_j = interpolant(t_j), presence_j = rule(t_j) -- except for three ORDERED sums
 // (State.distances, EgoAvgSpeed, the event list) and the step at which a terminal condition first holds.  A small batch
 // (BASELINE config 2: 64 wavefronts on a 1024-SIMD chip) therefore cuts the time axis: the clock t_j = t_{j-1} + dt is

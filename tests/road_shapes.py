@@ -1,5 +1,5 @@
 """The exact reference for "which polygons contain this point" and the adversarial road networks and query points that
-tests/test_road_index_adversarial.py aims at the device's cell index (build_road_network in csrc/sgym_hip.hip, rn_* in
+tests/test_road_index_adversarial.py aims at the device's cell index (build_road_network in csrc/h_road.hip, rn_* in
 csrc/sgym_road.hpp and sgym_geom.hpp).  A plain module, like standin_engine.py.
 
 The rule (README N6): a point is in a polygon iff it lies strictly inside its rings by the crossing number (ray
@@ -268,7 +268,7 @@ COARSE = ("square1600", "square3200", "strip")
 
 # ---------------------------------------------------------------------------------------------------- query points
 def grid_of(arrays):
-    """(x0, y0, cell side, nx, ny) of the uniform grid build_road_network lays over a network (csrc/sgym_hip.hip: 1 m cells,
+    """(x0, y0, cell side, nx, ny) of the uniform grid build_road_network lays over a network (csrc/h_road.hip: 1 m cells,
     doubled while there would be more than 2^21; one cell of margin).  Restated to AIM points at cell lines; no expected answer
     depends on it."""
     v = np.asarray(arrays["verts"], np.float64).reshape(-1, 2)
