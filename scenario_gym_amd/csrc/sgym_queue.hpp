@@ -1,4 +1,4 @@
-// sgym_queue.hpp -- the table path as ONE persistent launch: rollout_kernel_tabq<G, PLANAR>.
+// sgym_queue.hpp -- the table path as ONE persistent launch: rollout_kernel_tabq<G> / _tabq_planar<G>.
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_launch.hpp after sgym_device.hpp.
 //
 // ScenarioGym.rollout is deterministic (scenario_gym.py:256-267); so is this schedule.  Rounds 3-4 ran the table path as chunk
@@ -126,10 +126,12 @@ __device__ __forceinline__ void q_handoff_writethrough(const Params &p, unsigned
 // RSS: the RSSDistances callback runs inside the step loop (rollout_kernel_rss_tab's body: controlled lanes read the pre-pass
 // table with vector loads, the line tests are queued per wavefront); the queue of a work item is worked off by the same
 // wavefront right after its steps (rss_lines_block), and the entities' RSS state words travel with the block's state.
-template <int G, bool PLANAR, bool RSS = false>
+// F: the variant of the rollout role (sgym_rollout.hpp, V_*) -- V_TAB | V_HAST [| V_PLANAR], or V_RSS | V_CTAB.
+template <int G, unsigned F>
 __device__ __forceinline__ void tabq_body(const Params &p, double timestep, int force, const TabQueue &tq)
 {
-    using Tile = TileLds<64, false, false>;
+    constexpr bool RSS = (F & V_RSS) != 0;
+    using Tile = typename Variant<G, 1, F>::Lds;
     static_assert(sizeof(Tile) >= sizeof(CtlLds), "the pre-pass role lays its LDS over the tile");
     __shared__ Tile lds;
     __shared__ typename std::conditional<RSS, RssQueue, char>::type rssq_lds;
@@ -246,12 +248,7 @@ __device__ __forceinline__ void tabq_body(const Params &p, double timestep, int 
         const bool in_range = r_raw < p.R;
         const int r = in_range ? r_raw : p.R - 1;
         const int ev_before = p.ev_cap > 0 ? min(p.sdyn[r].n_events, p.ev_cap) : 0;
-        if (RSS)
-            rollout_body_l<G, 1, false, false, false, false, true, false, false, false, false, true>(lds, p, timestep, tq.k0[c + 1] - tq.k0[c], 0, force,
-                                                                                                    nullptr, tab, SliceArgs{}, b);
-        else
-            rollout_body_l<G, 1, false, true, true, false, false, false, false, PLANAR>(lds, p, timestep, tq.k0[c + 1] - tq.k0[c], 0, force, nullptr,
-                                                                                       tab, SliceArgs{}, b);
+        rollout_body_l<G, 1, F>(lds, p, timestep, tq.k0[c + 1] - tq.k0[c], 0, force, nullptr, tab, SliceArgs{}, b);
         trace(4);
         stamp(2);
         if (RSS) { // the line tests this item queued, over full wavefronts (rss_lines_kernel's body), then the state words
@@ -314,20 +311,20 @@ template <int G>
 __global__ __launch_bounds__(64, SG_TAB_WAVES) __attribute__((amdgpu_num_vgpr(SG_TAB_VGPR))) void rollout_kernel_tabq(
     Params p, double timestep, int force, TabQueue tq)
 {
-    tabq_body<G, false>(p, timestep, force, tq);
+    tabq_body<G, V_TAB | V_HAST>(p, timestep, force, tq);
 }
 template <int G>
 __global__ __launch_bounds__(64, SG_PLANAR_WAVES) __attribute__((amdgpu_num_vgpr(SG_PLANAR_VGPR))) void rollout_kernel_tabq_planar(
     Params p, double timestep, int force, TabQueue tq)
 {
-    tabq_body<G, true>(p, timestep, force, tq);
+    tabq_body<G, V_TAB | V_HAST | V_PLANAR>(p, timestep, force, tq);
 }
 
 // ... with the RSSDistances callback in the step loop (rollout_kernel_rss_tab's budget: two wavefronts per SIMD)
 template <int G>
 __global__ __launch_bounds__(64, SG_WAVES_PER_SIMD) void rollout_kernel_rss_tabq(Params p, double timestep, int force, TabQueue tq)
 {
-    tabq_body<G, false, true>(p, timestep, force, tq);
+    tabq_body<G, V_RSS | V_CTAB>(p, timestep, force, tq);
 }
 
 } // namespace sg

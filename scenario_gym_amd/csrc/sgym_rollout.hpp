@@ -1,4 +1,4 @@
-// sgym_rollout.hpp -- rollout_body and its entry points; the time-sliced replay (slices, clock, ordered sums).
+// sgym_rollout.hpp -- the variant flags of the rollout kernel, rollout_body and its entry points; the time-sliced replay (slices, clock, ordered sums).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
@@ -10,12 +10,99 @@ namespace sg {
 //   WV == 1: one 64-lane workgroup carries 64/G scenarios of up to G entities each (tiles of G lanes)
 //   WV  > 1: one workgroup of WV wavefronts carries ONE scenario of up to 64*WV entities
 // do_reset: State.reset first.  force: step done scenarios too (gym.step()); otherwise each scenario
-// stops at is_done (gym.rollout()).  PED: pedestrian agents (social force) are compiled in.
+// stops at is_done (gym.rollout()).  What a variant compiles in or out: the V_* flags below.
 //
 // Register-resident per lane across the time loop: pose, distance, the knot segment (x_lo, x_hi,
 // y_lo[6], slope[6]), the clock, controller state, ego metric accumulators.  Controller parameters
 // and box extents live in LDS; there is no global load in a steady-state step.
 // ------------------------------------------------------------------------------------------------
+// The variants of the rollout kernel.  Every entry point names the flags of its body: rollout_body<G, WV, V_TAB | V_HAST>.
+// What the flags imply, and which combinations exist: Variant below.  The entry points with their flags, units, register
+// budgets and launchers: DESIGN.md, "The rollout kernel's variants".
+// ------------------------------------------------------------------------------------------------
+enum : unsigned {
+    // PED: pedestrian agents (social force) are compiled in (rollout_kernel<G, WV, true, false>, rollout_kernel_rss_ped, the
+    // crowd entry points; their own launch bounds, SG_WAVES_PER_SIMD_PED).  Pedestrian scenarios run their controllers in the
+    // rollout kernel: never with TAB.
+    V_PED = 1,
+    // TAB: the PID / vehicle agents were integrated by control_kernel; their lanes read (x, y, h) per step from
+    // its table `tab` instead of running the controller with 1 of 64 lanes active.  TAB launches never reset.
+    // Register budget of the one-wavefront-per-tile entry points (rollout_kernel_tab / _tab_planar): 168 VGPRs, three
+    // wavefronts per SIMD; the pre-pass takes a wavefront slot of its own (h_queue.hip, launch_table).
+    V_TAB = 2,
+    // HAST (TAB only): the batch has controlled lanes, i.e. there is a table to replay; without it the table code is
+    // compiled out (batches of replay entities only: the C2 shape).  With one wavefront per tile the entry points
+    // without it are rollout_kernel<G, 1, false, true> and rollout_kernel_slice; rollout_kernel_tab / _tab_planar / _slice_tab
+    // and the persistent launch (sgym_queue.hpp) have it.
+    V_HAST = 4,
+    // ROAD: the ego_off_road terminal condition is compiled in (its own entry point, rollout_kernel_road: the other
+    // variants keep their register budgets).
+    V_ROAD = 8,
+    // RSSV: the RSSDistances callback (rss_entity) runs after the reset and after every step inside the kernel
+    // (rollout_kernel_rss / _rss_road / _rss_ped / _rss_tab and the RSS role of the persistent launch, sgym_queue.hpp).
+    V_RSS = 16,
+    // CROWD (PED only): every entity of the batch is a pedestrian agent (or padding), default head rotation, no road network:
+    // no knot segment, no vehicle / replay code, crowd_pairs for the neighbour sums (rollout_kernel_crowd, BASELINE config 5).
+    V_CROWD = 32,
+    // SLICE (TAB, one wavefront per tile): one slice of a time-sliced replay, see SliceArgs (rollout_kernel_slice / _slice_tab).
+    // With HAST the controlled lanes (PID / vehicle agents) replay a controller table that spans the WHOLE call -- row j - 1 =
+    // the lane after step j, written by control_kernel launches that run ahead of the slices -- so a slice that starts at step
+    // a finds its lanes' poses there like everything else it needs in the clock.
+    V_SLICE = 64,
+    // PLANAR (table variant, one wavefront per tile; its own entry point, rollout_kernel_tab_planar): every knot of the
+    // batch has z = pitch = roll = +0.0 (sg_upload checks the bit patterns).  Those three channels are then +0.0 in every
+    // pose, previous pose and velocity the batch ever holds -- absent lanes included, their rows are zeroed by the reset --
+    // so the step neither interpolates, subtracts, tests nor stores them, and their 18 registers (pose, segment base and
+    // slope) do not exist.
+    V_PLANAR = 128,
+    // RIDERS (crowd variant; its own entry point, rollout_kernel_crowd_riders): the batch also has lanes that are NOT pedestrian
+    // agents -- replay entities, replay agents, PID / vehicle agents (a car driving through the crowd, recorded pedestrians).
+    // None of them ever looks at another entity (batch.py:34-53, agent.py:125-148, controller.py:105-258), so a pre-pass
+    // (control_kernel_riders) has put their pose and presence after every step of the chunk into the controller table, and
+    // here they only read their row: the crowd kernel stays free of knot segments and vehicle code.
+    V_RIDERS = 256,
+    // CTAB (variants with in-kernel controllers whose registers are full -- the RSS callback: rollout_kernel_rss_tab): the PID /
+    // vehicle agents were integrated by control_kernel, their lanes read x, y, h of the step from the controller table with a
+    // vector load, and the controller code (sin / cos, PID, tangent: ~220 instructions per wavefront-step for one active
+    // lane in 64) is not compiled into this kernel at all.
+    V_CTAB = 512,
+    // MODELS: per-agent behaviour models (sg_set_ped_models), a pass of the force code per model.  Compiled in for every
+    // general pedestrian variant, and for the crowd variant as an entry point of its own -- rollout_kernel_crowd_models: the
+    // one-model crowd kernel has no register to spare for a second copy of the force code.  So only a crowd variant names
+    // the flag; Variant::MODELS holds for every other variant without it.
+    V_MODELS = 1024
+};
+
+// A variant: tile shape + flags.  The flags by name, what follows from them, the type of the LDS tile, and which combinations exist.
+template <int G, int WV, unsigned F>
+struct Variant {
+    static constexpr bool PED = (F & V_PED) != 0, TAB = (F & V_TAB) != 0, HAST = (F & V_HAST) != 0, ROAD = (F & V_ROAD) != 0,
+                          RSSV = (F & V_RSS) != 0, CROWD = (F & V_CROWD) != 0, SLICE = (F & V_SLICE) != 0, PLANAR = (F & V_PLANAR) != 0,
+                          RIDERS = (F & V_RIDERS) != 0, CTAB = (F & V_CTAB) != 0, MODELS = !CROWD || (F & V_MODELS) != 0;
+    static_assert(F < 2 * V_MODELS, "flags: V_* bits only");
+    static_assert(!SLICE || (TAB && WV == 1 && !PED && !ROAD && !RSSV), "slices: the table variant, one wavefront per tile");
+    static_assert(!(PED && TAB), "pedestrian scenarios run their controllers in the rollout kernel");
+    static_assert(!CROWD || (PED && G == 64 && !ROAD && !RSSV), "the crowd variant is a pedestrian variant with 64-lane tiles");
+    static_assert(!RIDERS || CROWD, "riders ride the crowd variant");
+    static_assert(!CTAB || (!TAB && !PED && !CROWD), "CTAB: table rows into an in-kernel-controller variant");
+    static_assert(!PLANAR || (TAB && WV == 1 && !SLICE), "planar: the table variant");
+    static constexpr int NS = 64 * WV;                   // LDS slots of the workgroup
+    static constexpr bool HAS_TAB = TAB && HAST;         // a controller table is replayed
+    static constexpr bool REFINE = CROWD ? RIDERS : PED; // the tile's largest bounding-circle radius and `hetero` are formed
+    // LATE (the table variants outside a sliced replay): nothing reads a state row while the call runs -- the pre-pass reads
+    // p.dyn before the first step only -- so the step loop does not store the pose, distance, presence and collision rows: the
+    // registers hold them, and they are stored once where the loop is left ("write back what lives in registers").  The
+    // velocity rows hold the velocity of the last step a lane committed WHILE PRESENT, which the registers do not keep: a step
+    // computes and stores them only if it can be that step (see vel_every_step and need_vel in rollout_body_l).
+    static constexpr bool LATE = TAB && !SLICE;
+    // PARK (the LATE entry points under the 168-register cap: one wavefront per tile, controlled lanes): the ego metric
+    // accumulators wait in the lane's column of lds.ctrl -- a table variant has no controller parameters there -- between their
+    // uses.  A table ego's come with its table and are never touched by a step; any other ego's are read and written once per step.
+    static constexpr bool PARK = LATE && HAST && WV == 1;
+    static constexpr int TL = SG_TAB_LANES(G, WV);       // controlled lanes of a wavefront whose table rows the step loop fetches
+    using Lds = TileLds<NS, PED, CROWD, CROWD && !RIDERS>; // the workgroup's LDS tile
+};
+
 __device__ __forceinline__ Table lane_table(const Params &p, int kind, const ScenStatic &ss, int slot,
                                             const LanePtr &st)
 {
@@ -35,16 +122,6 @@ __device__ __forceinline__ Table lane_table(const Params &p, int kind, const Sce
     return T;
 }
 
-//
-// TAB: the PID / vehicle agents were integrated by control_kernel; their lanes read (x, y, h) per step from
-// its table `tab` instead of running the controller with 1 of 64 lanes active.  TAB launches never reset.
-// Register budget of the one-wavefront-per-tile entry points (rollout_kernel_tab / _tab_planar): 168 VGPRs, three
-// wavefronts per SIMD; the pre-pass takes a wavefront slot of its own (h_queue.hip, launch_table).
-// HAST (TAB only): the batch has controlled lanes, i.e. there is a table to replay; without it the table code is
-// compiled out (batches of replay entities only: the C2 shape).
-// ROAD: the ego_off_road terminal condition is compiled in (its own entry point, rollout_kernel_road: the other
-// variants keep their register budgets).
-// RSSV: the RSSDistances callback (rss_entity) runs after the reset and after every step inside the kernel.
 // ------------------------------------------------------------------------------------------------
 // Time-sliced replay (launch_sliced in h_slice.hip): a batch whose lanes are all replay entities / replay agents is a
 // pure function of the clock -- pose_j = interpolant(t_j), presence_j = rule(t_j) -- except for three ORDERED sums
@@ -73,36 +150,20 @@ struct SliceArgs {
                          // slices group by group, each group as soon as the controller pre-pass has reached its last step
 };
 
-// CROWD (PED only): every entity of the batch is a pedestrian agent (or padding), default head rotation, no road network:
-// no knot segment, no vehicle / replay code, crowd_pairs for the neighbour sums (rollout_kernel_crowd, BASELINE config 5).
-// SLICE (TAB, one wavefront per tile): one slice of a time-sliced replay, see SliceArgs.  With HAST the controlled lanes
-// (PID / vehicle agents) replay a controller table that spans the WHOLE call -- row j - 1 = the lane after step j, written by
-// control_kernel launches that run ahead of the slices -- so a slice that starts at step a finds its lanes' poses there
-// like everything else it needs in the clock.
-template <int G, int WV, bool PED, bool TAB, bool HAST, bool ROAD = false, bool RSSV = false, bool CROWD = false, bool SLICE = false,
-          bool PLANAR = false, bool RIDERS = false, bool CTAB = false, bool MODELS = !CROWD>
+// The body of every rollout kernel.  F: the V_* flags of the variant (Variant<G, WV, F>).
+template <int G, int WV, unsigned F>
 __device__ __forceinline__ void rollout_body_l(
-    TileLds<64 * WV, PED, CROWD, CROWD && !RIDERS> &lds /* the workgroup's LDS tile: the entry point owns it (rollout_kernel_tabq shares it between roles) */,
+    typename Variant<G, WV, F>::Lds &lds /* the workgroup's LDS tile: the entry point owns it (rollout_kernel_tabq shares it between roles) */,
     const Params &p, double timestep, int n_steps, int do_reset, int force, const double *actions /*[n][R][2]*/,
     const double *tab /*controller table planes*/, const SliceArgs &sa = SliceArgs{},
     const unsigned bx_arg = ~0u /* the 64-slot block (WV == 1) / scenario of this workgroup when it is not bx: TabGroups */)
 {
     const unsigned bx = bx_arg == ~0u ? blockIdx.x : bx_arg;
-    static_assert(!SLICE || (TAB && WV == 1 && !PED && !ROAD && !RSSV), "slices: the table variant, one wavefront per tile");
-    static_assert(!(PED && TAB), "pedestrian scenarios run their controllers in the rollout kernel");
-    static_assert(!CROWD || (PED && G == 64 && !ROAD && !RSSV), "the crowd variant is a pedestrian variant with 64-lane tiles");
-    // RIDERS (crowd variant; its own entry point, rollout_kernel_crowd_riders): the batch also has lanes that are NOT pedestrian
-    // agents -- replay entities, replay agents, PID / vehicle agents (a car driving through the crowd, recorded pedestrians).
-    // None of them ever looks at another entity (batch.py:34-53, agent.py:125-148, controller.py:105-258), so a pre-pass
-    // (control_kernel_riders) has put their pose and presence after every step of the chunk into the controller table, and
-    // here they only read their row: the crowd kernel stays free of knot segments and vehicle code.
-    static_assert(!RIDERS || CROWD, "riders ride the crowd variant");
-    // CTAB (variants with in-kernel controllers whose registers are full -- the RSS callback: rollout_kernel_rss_tab): the PID /
-    // vehicle agents were integrated by control_kernel, their lanes read x, y, h of the step from the controller table with a
-    // vector load, and the controller code (sin / cos, PID, tangent: ~220 instructions per wavefront-step for one active
-    // lane in 64) is not compiled into this kernel at all.
-    static_assert(!CTAB || (!TAB && !PED && !CROWD), "CTAB: table rows into an in-kernel-controller variant");
-    constexpr int NS = 64 * WV;
+    using V = Variant<G, WV, F>;
+    constexpr bool PED = V::PED, TAB = V::TAB, ROAD = V::ROAD, RSSV = V::RSSV, CROWD = V::CROWD, SLICE = V::SLICE, PLANAR = V::PLANAR,
+                   RIDERS = V::RIDERS, CTAB = V::CTAB, MODELS = V::MODELS;
+    constexpr bool HAS_TAB = V::HAS_TAB, REFINE = V::REFINE, LATE = V::LATE, PARK = V::PARK;
+    constexpr int NS = V::NS, TL = V::TL;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t voff = lane * 8u;
     // one wavefront = one 64-slot block of the state arrays: wave-uniform block pointers
@@ -136,7 +197,6 @@ __device__ __forceinline__ void rollout_body_l(
     float rad_thr, trig_eps, nbr_thr = 0.0f;
     float rmax_tile = 0.0f;   // REFINE: the largest bounding-circle radius of the tile ...
     bool hetero = false;      // ... and whether some real entity's is less than two thirds of it
-    constexpr bool REFINE = CROWD ? RIDERS : PED;
     {
         const double bw = fld(st, ST_BW), bl = fld(st, ST_BL);
         float rad = (float)(0.5 * __builtin_sqrt(bl * bl + bw * bw)) * 1.000001f;
@@ -252,23 +312,6 @@ __device__ __forceinline__ void rollout_body_l(
         nwp = (int)(rt >> 48);
     }
 
-    // PLANAR (table variant, one wavefront per tile; its own entry point, rollout_kernel_tab_planar): every knot of the
-    // batch has z = pitch = roll = +0.0 (sg_upload checks the bit patterns).  Those three channels are then +0.0 in every
-    // pose, previous pose and velocity the batch ever holds -- absent lanes included, their rows are zeroed by the reset --
-    // so the step neither interpolates, subtracts, tests nor stores them, and their 18 registers (pose, segment base and
-    // slope) do not exist.
-    static_assert(!PLANAR || (TAB && WV == 1 && !SLICE), "planar: the table variant");
-    constexpr bool planar = PLANAR;
-    // LATE (the table variants outside a sliced replay): nothing reads a state row while the call runs -- the pre-pass reads
-    // p.dyn before the first step only -- so the step loop does not store the pose, distance, presence and collision rows: the
-    // registers hold them, and they are stored once where the loop is left ("write back what lives in registers").  The
-    // velocity rows hold the velocity of the last step a lane committed WHILE PRESENT, which the registers do not keep: a step
-    // computes and stores them only if it can be that step (see vel_every_step and need_vel below).
-    constexpr bool LATE = TAB && !SLICE;
-    // PARK (the LATE entry points under the 168-register cap: one wavefront per tile, controlled lanes): the ego metric
-    // accumulators wait in the lane's column of lds.ctrl -- a table variant has no controller parameters there -- between their
-    // uses.  A table ego's come with its table and are never touched by a step; any other ego's are read and written once per step.
-    constexpr bool PARK = LATE && HAST && WV == 1;
     // register-resident across the time loop
     double pose[6], dist, t, prev_t;
     double velx = 0.0, vely = 0.0; // current velocity (social force input), PED only
@@ -285,19 +328,18 @@ __device__ __forceinline__ void rollout_body_l(
     // The table rows are fetched with SCALAR loads, one controlled lane at a time (at most SG_TAB_LANES per
     // wavefront and wavefront of a wide scenario, checked by the host), one step ahead, and moved into the lane's registers at the end of the step.  A vector load inside the loop would share vmcnt with the state stores and make every
     // step wait for the stores of the previous one.
-    const int64_t ctl_q = (TAB && HAST) ? fld<int64_t>(st, ST_CTL) : -1;
-    const bool tab_lane = TAB && HAST && ctl_q >= 0 && (kind == SG_KIND_AGENT_PID || kind == SG_KIND_AGENT_VEHICLE);
+    const int64_t ctl_q = HAS_TAB ? fld<int64_t>(st, ST_CTL) : -1;
+    const bool tab_lane = HAS_TAB && ctl_q >= 0 && (kind == SG_KIND_AGENT_PID || kind == SG_KIND_AGENT_VEHICLE);
     const size_t tab_lane_stride = (size_t)(p.tab_steps + 1) * CT_W; // doubles per lane
     // RIDERS: this lane's column of the table (plane 0: x, y, h, speed; plane 2: z, pitch, roll, present)
     const bool rider = (RIDERS && kind != SG_KIND_NONE && kind != SG_KIND_AGENT_PEDESTRIAN) ||
                        (CTAB && (kind == SG_KIND_AGENT_PID || kind == SG_KIND_AGENT_VEHICLE));
     const double *rider_row = (RIDERS || CTAB) ? tab + (size_t)(rider ? fld<int64_t>(st, ST_CTL) : 0) * tab_lane_stride : nullptr;
     int last_k = -1;                                                 // last step of this launch the scenario executed
-    constexpr int TL = SG_TAB_LANES(G, WV);
     int cl[TL];                       // wave-uniform: the controlled lanes of this wavefront
     const double *cb[TL];             // wave-uniform: their table columns
     double sx[TL], sy[TL], sh[TL];    // wave-uniform: row of the coming step
-    if (TAB && HAST) {
+    if (HAS_TAB) {
         uint64_t cm = __ballot(tab_lane);
 #pragma unroll
         for (int j = 0; j < TL; ++j) {
@@ -437,7 +479,7 @@ __device__ __forceinline__ void rollout_body_l(
             for (int w = 0; w < WV; ++w) { last_row[w] = 0; row[w] = 0; }
         }
         n_steps = sa.mode == 0 ? 1 + min(sa.len, sa.n_total - slice_a) : 2;
-        if (TAB && HAST) {
+        if (HAS_TAB) {
             // a controlled lane that spawns (scenario_gym.py:240-244: absent at the reset, min_t >= t0) took all six channels
             // of its trajectory at the clock of step 1 and keeps z / pitch / roll from then on (controller.py:126-131)
             if (slice_a >= 2 && tab_lane && fld<uint64_t>(dy, SG_F_PRESENT) == 0 && min_t >= ss.t0) {
@@ -593,8 +635,7 @@ __device__ __forceinline__ void rollout_body_l(
 
     // The row of the coming step waits in SGPRs (sx, sy, sh); the step selects it into the controlled lane with
     // scalar-source v_cndmask and then issues the loads of the row after it.
-    constexpr bool has_tab = TAB && HAST;
-    if (has_tab && n_steps > 0) tab_issue(true);
+    if (HAS_TAB && n_steps > 0) tab_issue(true);
 
     // Two nested loops over the same step counter.  The inner one is the steady state and only READS the knot
     // segment S; when some lane's clock is about to cross a knot the wavefront drops to the outer loop, which
@@ -700,8 +741,6 @@ __device__ __forceinline__ void rollout_body_l(
         double ped_fx = 0.0, ped_fy = 0.0, ped_vdes = 0.0;
         PedMoveModel pmm = ped_move_model(p); // what ped_move reads of the behaviour model: this lane's, where the batch mixes models
         double nstd_lon = p.noise_std_lon, nstd_lat = p.noise_std_lat;
-        // (MODELS: compiled in for every general pedestrian variant, and for the crowd variant as an entry point of its own --
-        // rollout_kernel_crowd_models: the one-model crowd kernel has no register to spare for a second copy of the force code)
         if (PED && MODELS && p.n_ped_models > 1) {
             // Per-agent behaviour models (sg_set_ped_models; pedestrian/agent.py:18-41): the force on a pedestrian is computed with
             // ITS model's parameters from its neighbours' states, so the tile's pedestrians step model by model -- one pass of
@@ -795,7 +834,7 @@ __device__ __forceinline__ void rollout_body_l(
                 const bool leaves = is_replay & !(replay_always | ((next2_t >= min_t) & (next2_t <= max_t)));
                 need_vel = sg_any(run & npres & (ends | leaves));
             }
-            if (has_tab) {
+            if (HAS_TAB) {
                 const bool take = tab_lane & present & run;
 #pragma unroll
                 for (int j = 0; j < TL; ++j) { // wave-uniform table row into its lane: v_cndmask with scalar sources
@@ -804,7 +843,7 @@ __device__ __forceinline__ void rollout_body_l(
                     np_[1] = tj ? sy[j] : np_[1];
                     np_[3] = tj ? sh[j] : np_[3];
                 }
-                if (!planar) {
+                if (!PLANAR) {
                     np_[2] = take ? pose[2] : np_[2];
                     np_[4] = take ? pose[4] : np_[4];
                     np_[5] = take ? pose[5] : np_[5];
@@ -910,7 +949,7 @@ __device__ __forceinline__ void rollout_body_l(
                                 (int)(fld<int64_t>(st_o, ST_META) >> 32), t, prev);
 #pragma unroll
             for (int c = 0; c < 6; ++c) d[c] = np_[c] - prev[c];
-            if (planar) d[2] = d[4] = d[5] = 0.0; // (0 - 0: the extrapolated channels are +0.0 as well)
+            if (PLANAR) d[2] = d[4] = d[5] = 0.0; // (0 - 0: the extrapolated channels are +0.0 as well)
         }
         double vel[6];
         // z, pitch and roll rarely move.  `flat`: in every lane that commits a pose this step they keep their value
@@ -929,7 +968,7 @@ __device__ __forceinline__ void rollout_body_l(
         bool flat = false;
         if (need_vel) {
             RecipDiv rd(dt);
-            if (planar) {
+            if (PLANAR) {
                 flat = !SLICE && sg_all(dt > 0.0);
             } else {
                 const uint32_t zbits = (uint32_t)(__double2hiint(d[2]) | __double2hiint(d[4]) | __double2hiint(d[5])) |
@@ -1185,7 +1224,7 @@ __device__ __forceinline__ void rollout_body_l(
             }
         }
         if (RSSV) rss_call(run, t, vel[0], vel[1]); // State.step ends with update_callbacks(), state.py:165-171
-        if (has_tab) sg_lgkm_done();
+        if (HAS_TAB) sg_lgkm_done();
         PH(5);
     }
     }
@@ -1201,7 +1240,7 @@ __device__ __forceinline__ void rollout_body_l(
                 for (int w = 0; w < WV; ++w) (w < 4 ? sd.last_row[w & 3] : sd.last_row_hi[w & 3]) = last_row[w];
             }
         }
-        if (TAB && HAST && sa.mode == 1 && in_range && tab_lane) { // controller state after the last executed step
+        if (HAS_TAB && sa.mode == 1 && in_range && tab_lane) { // controller state after the last executed step
             const double *lr = tab + (size_t)ctl_q * tab_lane_stride + (size_t)(sa.n_final[r] - 1) * CT_W;
             const double *lr1 = lr + (size_t)p.n_ctl_pad * tab_lane_stride; // plane 1
             stf(dy, SG_F_CTRL + 0, lr[CT_SPEED]); stf(dy, SG_F_CTRL + 1, lr1[CT_ELON]);
@@ -1272,15 +1311,13 @@ __device__ __forceinline__ void rollout_body_l(
 }
 
 // the ordinary form: the LDS tile belongs to this call
-template <int G, int WV, bool PED, bool TAB, bool HAST, bool ROAD = false, bool RSSV = false, bool CROWD = false, bool SLICE = false,
-          bool PLANAR = false, bool RIDERS = false, bool CTAB = false, bool MODELS = !CROWD>
+template <int G, int WV, unsigned F>
 __device__ __forceinline__ void rollout_body(
     const Params &p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab,
     const SliceArgs &sa = SliceArgs{}, const unsigned bx_arg = ~0u)
 {
-    __shared__ TileLds<64 * WV, PED, CROWD, CROWD && !RIDERS> lds;
-    rollout_body_l<G, WV, PED, TAB, HAST, ROAD, RSSV, CROWD, SLICE, PLANAR, RIDERS, CTAB, MODELS>(lds, p, timestep, n_steps, do_reset, force, actions, tab,
-                                                                                       sa, bx_arg);
+    __shared__ typename Variant<G, WV, F>::Lds lds;
+    rollout_body_l<G, WV, F>(lds, p, timestep, n_steps, do_reset, force, actions, tab, sa, bx_arg);
 }
 
 // The blocks a launch of a table variant works on (launch_rollout): the 64-slot blocks of the batch are cut into groups of
@@ -1312,15 +1349,16 @@ __global__ __launch_bounds__(64 * WV, PED ? SG_WAVES_PER_SIMD_PED : (TAB ? SG_WA
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
     // one wavefront per tile: this entry point serves the batches WITHOUT controlled lanes (rollout_kernel_tab the others)
-    rollout_body<G, WV, PED, TAB, (TAB && WV > 1)>(p, timestep, n_steps, do_reset, force, actions, tab);
+    constexpr unsigned F = (PED ? V_PED : 0u) | (TAB ? V_TAB : 0u) | (TAB && WV > 1 ? V_HAST : 0u);
+    rollout_body<G, WV, F>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
-// All-pedestrian batches without road networks (BASELINE config 5): see rollout_body, CROWD
+// All-pedestrian batches without road networks (BASELINE config 5): see V_CROWD
 template <int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD_PED) void rollout_kernel_crowd(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<64, WV, true, false, false, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<64, WV, V_PED | V_CROWD>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
 // ... whose pedestrians follow up to four social-force models (sg_set_ped_models): a pass of the force code per model
@@ -1328,15 +1366,15 @@ template <int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD_PED) void rollout_kernel_crowd_models(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<64, WV, true, false, false, false, false, true, false, false, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<64, WV, V_PED | V_CROWD | V_MODELS>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
-// ... with riders: lanes of other kinds whose poses come from the pre-pass table (see rollout_body, RIDERS)
+// ... with riders: lanes of other kinds whose poses come from the pre-pass table (see V_RIDERS)
 template <int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD_PED) void rollout_kernel_crowd_riders(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<64, WV, true, false, false, false, false, true, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<64, WV, V_PED | V_CROWD | V_RIDERS>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
 // terminal_conditions with "ego_off_road": controllers in the kernel, road index lookups for slot 0
@@ -1344,7 +1382,7 @@ template <int G, int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD) void rollout_kernel_road(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<G, WV, false, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<G, WV, V_ROAD>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
 // state_callbacks=[RSSDistances()]: controllers and the RSS callback in the kernel, any number of steps per launch
@@ -1352,7 +1390,7 @@ template <int G, int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD) void rollout_kernel_rss(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<G, WV, false, false, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<G, WV, V_RSS>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
 // ... with the PID / vehicle agents on the controller pre-pass's table (CTAB): one wavefront per tile
@@ -1364,8 +1402,7 @@ __global__ __launch_bounds__(64, SG_WAVES_PER_SIMD) void rollout_kernel_rss_tab(
     const double *tab;
     const unsigned blk = tg.map(blockIdx.x);
     if (!tg.pick(blk, n_steps, tab)) return;
-    rollout_body<G, 1, false, false, false, false, true, false, false, false, false, true>(p, timestep, n_steps, 0, force, nullptr, tab,
-                                                                                             SliceArgs{}, blk);
+    rollout_body<G, 1, V_RSS | V_CTAB>(p, timestep, n_steps, 0, force, nullptr, tab, SliceArgs{}, blk);
 }
 
 // ... with the ego_off_road terminal condition / with pedestrian agents (RSSDistances treats every entity alike)
@@ -1373,13 +1410,13 @@ template <int G, int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD) void rollout_kernel_rss_road(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<G, WV, false, false, false, true, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<G, WV, V_ROAD | V_RSS>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 template <int G, int WV>
 __global__ __launch_bounds__(64 * WV, SG_WAVES_PER_SIMD_PED) void rollout_kernel_rss_ped(
     Params p, double timestep, int n_steps, int do_reset, int force, const double *actions, const double *tab)
 {
-    rollout_body<G, WV, true, false, false, false, true>(p, timestep, n_steps, do_reset, force, actions, tab);
+    rollout_body<G, WV, V_PED | V_RSS>(p, timestep, n_steps, do_reset, force, actions, tab);
 }
 
 // The table variant with one wavefront per tile (C2 / C3 shapes) under a 168-VGPR cap: three wavefronts per SIMD.  A
@@ -1399,7 +1436,7 @@ __global__ __launch_bounds__(64, SG_TAB_WAVES) __attribute__((amdgpu_num_vgpr(SG
     const double *tab;
     const unsigned blk = tg.map(blockIdx.x);
     if (!tg.pick(blk, n_steps, tab)) return;
-    rollout_body<G, 1, false, true, true>(p, timestep, n_steps, 0, force, nullptr, tab, SliceArgs{}, blk);
+    rollout_body<G, 1, V_TAB | V_HAST>(p, timestep, n_steps, 0, force, nullptr, tab, SliceArgs{}, blk);
 }
 // ... for batches whose knots all have z = pitch = roll = +0.0 (PLANAR)
 // Three wavefronts per SIMD (168 VGPRs): the kernel issues ~0.73 of the peak with two, ~0.85 with three.  The pre-pass does
@@ -1416,20 +1453,20 @@ __global__ __launch_bounds__(64, SG_PLANAR_WAVES) __attribute__((amdgpu_num_vgpr
     const double *tab;
     const unsigned blk = tg.map(blockIdx.x);
     if (!tg.pick(blk, n_steps, tab)) return;
-    rollout_body<G, 1, false, true, true, false, false, false, false, true>(p, timestep, n_steps, 0, force, nullptr, tab, SliceArgs{}, blk);
+    rollout_body<G, 1, V_TAB | V_HAST | V_PLANAR>(p, timestep, n_steps, 0, force, nullptr, tab, SliceArgs{}, blk);
 }
 
 // One slice of a time-sliced replay (grid.y = slices; SliceArgs), or its last step with the full state stores
 template <int G>
 __global__ __launch_bounds__(64, SG_WAVES_PER_SIMD_TAB) void rollout_kernel_slice(Params p, double timestep, SliceArgs sa)
 {
-    rollout_body<G, 1, false, true, false, false, false, false, true>(p, timestep, 0, 0, 0, nullptr, nullptr, sa);
+    rollout_body<G, 1, V_TAB | V_SLICE>(p, timestep, 0, 0, 0, nullptr, nullptr, sa);
 }
 // ... of a batch with controlled lanes: `tab` = the controller table of the whole call (p.tab_steps = sa.n_total)
 template <int G>
 __global__ __launch_bounds__(64, SG_WAVES_PER_SIMD_TAB) void rollout_kernel_slice_tab(Params p, double timestep, SliceArgs sa, const double *tab)
 {
-    rollout_body<G, 1, false, true, true, false, false, false, true>(p, timestep, 0, 0, 0, nullptr, tab, sa);
+    rollout_body<G, 1, V_TAB | V_HAST | V_SLICE>(p, timestep, 0, 0, 0, nullptr, tab, sa);
 }
 
 // The clocks of a sliced replay: tt[c][j] = State.t after j steps = t0_c + dt + dt + ... (scenario_gym.py:229), the

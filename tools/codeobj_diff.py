@@ -6,6 +6,9 @@ kernel (disassembly with addresses relative to the kernel's start, and the regis
     python tools/codeobj_diff.py OLD_OBJ_DIR NEW_OBJ_DIR [--moved old_unit:new_unit ...]
 
 Prints a table of unit or kernel against identical / differs / no kernels; exit status 1 when anything differs.
+Build both trees in the SAME directory with the same OUT, one after the other (move the first build's obj/ away): the toolchain's
+per-unit id depends on the path and the command line and goes into the code object, so builds at two paths differ byte for byte
+in every unit that has a kernel.
 """
 import argparse
 import hashlib
