@@ -17,58 +17,47 @@ static int obs_scratch(sg_handle *h, size_t bytes, unsigned char **out)
     return SG_OK;
 }
 
-// the layer codes of a map observation: 0 (the entities) or one SG_LAYER_* bit each; *any_surface: some layer is a surface
-static int check_layers(sg_handle *h, const char *who, int32_t n_layers, const int32_t *layers, bool *any_surface)
+// the layer codes of a map observation: 0 (the entities) or one SG_LAYER_* bit each
+static int check_layers(sg_handle *h, const char *who, int32_t n_layers, const int32_t *layers)
 {
-    *any_surface = false;
     for (int k = 0; k < n_layers; ++k) {
         const uint32_t L = (uint32_t)layers[k];
         if (layers[k] < 0 || L > 255u || (L & (L - 1))) return fail(h, SG_ERR_INVALID, "%s: layers[%d]=%d is not 0 or one SG_LAYER_* bit", who, k, layers[k]);
-        *any_surface = *any_surface || L != 0;
     }
     return SG_OK;
 }
 
-// The map layers of every scenario into d = [R][n_layers][nh][nw] on the handle's stream: the entity layers one by one
-// (raster_kernel), the surfaces in one launch (raster_surface_kernel; dl: the layer codes on the device), empty surfaces
-// without road networks.  Returns the first HIP error and enqueues nothing after it (sg_tick calls this while capturing).
+// The map layers of every scenario's ego into d = [R][n_layers][nh][nw] on the handle's stream: one launch per group of at
+// most eight layers (the kernel takes the codes by value), each writing every byte of its planes.  Returns the first HIP error
+// and enqueues nothing after it (sg_tick calls this while capturing).
 static hipError_t enqueue_map_layers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers, const int32_t *layers,
-                                     bool any_surface, const int32_t *dl, unsigned char *d)
+                                     unsigned char *d)
 {
-    const size_t plane = (size_t)nw * nh, bytes = (size_t)h->R * n_layers * plane;
+    const size_t plane = (size_t)nw * nh;
     hipError_t e = hipSuccess;
-    if (any_surface && !h->has_road) e = hipMemsetAsync(d, 0, bytes, h->stream); // no networks: empty surfaces
-    for (int k = 0; k < n_layers && e == hipSuccess; ++k)
-        if (layers[k] == 0) {
-            sgl::raster(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, width, height, nw, nh, d + (size_t)k * plane,
-                        (int64_t)(n_layers * plane));
-            e = hipGetLastError();
-        }
-    if (any_surface && h->has_road && e == hipSuccess) {
-        sgl::raster_surface(dim3((unsigned)h->R), h->stream, h->p, h->road, width, height, nw, nh, n_layers, dl, d);
+    for (int32_t l0 = 0; l0 < n_layers && e == hipSuccess; l0 += 8) {
+        sgl::map_raster(h->stream, h->p, h->road, h->has_road, nullptr, nullptr, h->R, width, height, nw, nh, std::min(n_layers - l0, 8), layers + l0,
+                        d + (size_t)l0 * plane, (int64_t)(n_layers * plane));
         e = hipGetLastError();
     }
     return e;
 }
 
-// the raster kernels of sg_raster_map / sg_raster_map_device on the handle's stream; *d_out = [R][n_layers][nh][nw]
+// the raster launches of sg_raster_map / sg_raster_map_device on the handle's stream; *d_out = [R][n_layers][nh][nw]
 static int raster_map_launch(sg_handle *h, const char *who, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
                              const int32_t *layers, unsigned char **d_out, size_t *bytes_out)
 {
     if (!layers || n_layers < 1 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
         return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    bool any_surface = false;
-    int rc = check_layers(h, who, n_layers, layers, &any_surface);
+    int rc = check_layers(h, who, n_layers, layers);
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = (size_t)h->R * n_layers * nw * nh, lay_off = (bytes + 15) & ~(size_t)15;
+    const size_t bytes = (size_t)h->R * n_layers * nw * nh;
     unsigned char *d = nullptr;
-    rc = obs_scratch(h, lay_off + (size_t)n_layers * sizeof(int32_t), &d);
+    rc = obs_scratch(h, bytes, &d);
     if (rc) return rc;
-    int32_t *dl = reinterpret_cast<int32_t *>(d + lay_off);
-    HIP_TRY(h, hipMemcpyAsync(dl, layers, (size_t)n_layers * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, any_surface, dl, d));
+    HIP_TRY(h, enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, d));
     *d_out = d;
     *bytes_out = bytes;
     return SG_OK;
@@ -110,8 +99,8 @@ extern "C" int sg_raster_entities(sg_handle *h, double width, double height, int
     unsigned char *d = nullptr;
     int rc = obs_scratch(h, bytes, &d);
     if (rc) return rc;
-    sgl::raster(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, width, height, nw, nh, d, (int64_t)nw * nh);
-    hipError_t e = hipGetLastError();
+    const int32_t entity_layer = 0;
+    hipError_t e = enqueue_map_layers(h, width, height, nw, nh, 1, &entity_layer, d);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_raster_entities: %s", hipGetErrorString(e));
@@ -129,8 +118,8 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
     if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
         return fail(h, SG_ERR_INVALID, "sg_tick: bad observation geometry (1..8 layers)");
     if (h->n_ext > 0) return fail(h, SG_ERR_STATE, "sg_tick: batches with caller-run agents are driven through sg_set_external_poses + sg_step");
-    bool any_surface = false, grew = false;
-    int rc = check_layers(h, "sg_tick", n_layers, layers, &any_surface);
+    bool grew = false;
+    int rc = check_layers(h, "sg_tick", n_layers, layers);
     if (rc) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     // fixed device addresses for everything the graph's kernels read or write
@@ -141,10 +130,8 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
     if (grew) ++h->generation;
     double *const d_actions = h->actions.as<double>();
     uint32_t *const d_term_flags = h->term_flags.as<uint32_t>();
-    const size_t bytes = (size_t)h->R * n_layers * nw * nh, lay_off = (bytes + 15) & ~(size_t)15;
     unsigned char *d = nullptr;
-    if ((rc = obs_scratch(h, lay_off + 8 * sizeof(int32_t), &d))) return rc;
-    int32_t *dl = reinterpret_cast<int32_t *>(d + lay_off);
+    if ((rc = obs_scratch(h, (size_t)h->R * n_layers * nw * nh, &d))) return rc;
     // sg_set_rss: the callback runs after the step, inside the captured launch (like sg_step; without records of a reset --
     // the callback was switched on after sg_upload -- through sg_rss_update after the graph)
     if (h->wide && (rc = ensure_wide(h))) return rc;
@@ -157,23 +144,22 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (const int rcq = check_queue(h)) return rcq; // (a persistent launch that gave up: sticky)
         if (h->tick_exec) { HIP_TRY(h, hipGraphExecDestroy(h->tick_exec)); h->tick_exec = nullptr; }
-        HIP_TRY(h, hipMemcpy(dl, layers, (size_t)n_layers * sizeof(int32_t), hipMemcpyHostToDevice));
         hipGraph_t graph = nullptr;
         HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
         // the step as sg_step runs it, never on the table path (one step: not timed); launch_plan does not synchronise
         rc = launch_plan(h, plan_call(h, 1, rss_tick, false), 1, 0, 1, d_actions);
         hipError_t e = hipSuccess;
         if (!rc && h->wide) {
-            // scenarios of more than 512 entities: the entity layers tile by tile (raster_kernel), empty surfaces (no road
-            // networks at this width), the terminal conditions by the kernel of sg_terminal_flags
-            e = enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, any_surface, dl, d);
+            // scenarios of more than 512 entities: the map layers (the entity layer tile by tile), the terminal conditions by
+            // the kernel of sg_terminal_flags
+            e = enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, d);
             if (e == hipSuccess) {
                 sgl::terminal_flags(dim3((unsigned)h->R), h->stream, h->p, h->cfg.timestep, d_term_flags);
                 e = hipGetLastError();
             }
-        } else if (!rc) { // the whole observation (map layers + terminal flags) in one launch
-            sgl::observe(dim3((unsigned)h->R), dim3(h->EP > 256 ? 512 : 256), h->stream, h->p, h->road, h->has_road ? 1 : 0, width, height, nw, nh,
-                         n_layers, dl, d, d_term_flags);
+        } else if (!rc) { // the whole observation (map layers + terminal flags) in one launch: every scenario fits one tile
+            sgl::map_raster(h->stream, h->p, h->road, h->has_road, nullptr, nullptr, h->R, width, height, nw, nh, n_layers, layers, d,
+                            (int64_t)n_layers * nw * nh, d_term_flags);
             e = hipGetLastError();
         }
         hipError_t e2 = hipStreamEndCapture(h->stream, &graph);
@@ -228,7 +214,7 @@ extern "C" int sg_future_collision(sg_handle *h, double horizon, int32_t n_sampl
     unsigned char *d = nullptr;
     int rc = obs_scratch(h, (size_t)h->R, &d);
     if (rc) return rc;
-    sgl::future(dim3((unsigned)h->R), h->stream, h->p, horizon, n_samples, d);
+    sgl::look_ahead(h->stream, h->p, nullptr, nullptr, h->R, horizon, n_samples, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, (size_t)h->R, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -275,21 +261,21 @@ extern "C" int sg_raster_map_observers(sg_handle *h, double width, double height
     if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
         return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_map_observers: no scenarios uploaded");
-    bool any_surface = false;
-    if (const int rc = check_layers(h, "sg_raster_map_observers", n_layers, layers, &any_surface)) return rc;
+    if (const int rc = check_layers(h, "sg_raster_map_observers", n_layers, layers)) return rc;
     if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
     if (!out) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: null out");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
+    const size_t bytes_each = (size_t)n_layers * nw * nh;
     if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
-        sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, out);
+        sgl::map_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, out, (int64_t)bytes_each);
         HIP_TRY(h, hipGetLastError());
         return queue_gave_up(h); // (not waited for: what is known so far)
     }
-    const size_t bytes = (size_t)h->n_obs * n_layers * nw * nh;
+    const size_t bytes = (size_t)h->n_obs * bytes_each;
     unsigned char *d = nullptr;
     if (int rc = obs_scratch(h, bytes, &d)) return rc;
-    sgl::observers_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, d);
+    sgl::map_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, d, (int64_t)bytes_each);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -306,13 +292,13 @@ extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
     if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
-        sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, out);
+        sgl::look_ahead(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, out);
         HIP_TRY(h, hipGetLastError());
         return queue_gave_up(h); // (not waited for: what is known so far)
     }
     unsigned char *d = nullptr;
     if (int rc = obs_scratch(h, (size_t)h->n_obs, &d)) return rc;
-    sgl::observers_future(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, d);
+    sgl::look_ahead(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, d);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out, d, (size_t)h->n_obs, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -1,4 +1,4 @@
-// k_main.hip -- the setup / sensor / fix-up kernels (sgym_grid.hpp, sgym_sensors.hpp, the fix-ups of sgym_rollout.hpp): one
+// k_main.hip -- the setup / read-out / fix-up kernels (sgym_grid.hpp, sgym_sensors.hpp, the fix-ups of sgym_rollout.hpp): one
 // launcher per kernel.  Grid and block sizes are the callers'; so is the error handling (hipGetLastError after the call).
 #define SG_UNIT_MAIN
 #include "sgym_launch.hpp"
@@ -55,29 +55,6 @@ void delay(hipStream_t s, long long ticks) { delay_kernel<<<dim3(1), dim3(64), 0
 void build_grid(dim3 grid, hipStream_t s, const sg::Params &p, const int32_t *row_scen, int64_t row0, int64_t row_end)
 {
     sg::build_grid_kernel<<<grid, dim3(256), 0, s>>>(p, row_scen, row0, row_end);
-}
-
-void raster(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, double width, double height, int nw, int nh, unsigned char *out,
-            int64_t stride)
-{
-    sg::raster_kernel<<<grid, block, 0, s>>>(p, width, height, nw, nh, out, stride);
-}
-
-void raster_surface(dim3 grid, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, double width, double height, int nw, int nh,
-                    int n_layers, const int32_t *layers, unsigned char *out)
-{
-    sg::raster_surface_kernel<<<grid, dim3(256), 0, s>>>(p, R, width, height, nw, nh, n_layers, layers, out);
-}
-
-void observe(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, int has_road, double width, double height,
-             int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out, uint32_t *flags)
-{
-    sg::observe_kernel<<<grid, block, 0, s>>>(p, R, has_road, width, height, nw, nh, n_layers, layers, out, flags);
-}
-
-void future(dim3 grid, hipStream_t s, const sg::Params &p, double horizon, int n_samples, unsigned char *out)
-{
-    sg::future_kernel<<<grid, dim3(256), 0, s>>>(p, horizon, n_samples, out);
 }
 
 void trig32(dim3 grid, hipStream_t s, const double *h, float *sin_out, float *cos_out, int64_t n)

@@ -1,23 +1,27 @@
-// k_obs.hip -- observers_raster_kernel / observers_future_kernel: the map and look-ahead observations of a list of
-// observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
+// k_obs.hip -- map_raster_kernel / look_ahead_kernel: the map and look-ahead observations of the ego of every scenario or of
+// a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
 namespace sgl {
-void observers_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool has_road, const int32_t *scen, const int32_t *slot,
-                      int64_t n, double width, double height, int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out)
+void map_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool has_road, const int32_t *scen, const int32_t *slot, int64_t n,
+                double width, double height, int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out, int64_t stride,
+                uint32_t *flags)
 {
     if (n <= 0) return;
     sg::ObsLayers lay{};
     for (int k = 0; k < n_layers && k < 8; ++k) lay.code[k] = layers[k];
-    sg::observers_raster_kernel<<<dim3((unsigned)n), dim3(p.EP > 256 ? 512 : 256), 0, s>>>(p, R, has_road ? 1 : 0, scen, slot, width, height, nw, nh,
-                                                                                         n_layers, lay, out);
+    const dim3 grid((unsigned)n), block(p.EP > 256 ? 512 : 256);
+    if (flags)
+        sg::map_raster_kernel<true><<<grid, block, 0, s>>>(p, R, has_road ? 1 : 0, nullptr, nullptr, width, height, nw, nh, n_layers, lay, out, stride, flags);
+    else
+        sg::map_raster_kernel<false><<<grid, block, 0, s>>>(p, R, has_road ? 1 : 0, scen, slot, width, height, nw, nh, n_layers, lay, out, stride, nullptr);
 }
 
-void observers_future(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
-                      unsigned char *out)
+void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
+                unsigned char *out)
 {
     if (n <= 0) return;
-    sg::observers_future_kernel<<<dim3((unsigned)n), dim3(256), 0, s>>>(p, scen, slot, horizon, n_samples, out);
+    sg::look_ahead_kernel<<<dim3((unsigned)n), dim3(256), 0, s>>>(p, scen, slot, horizon, n_samples, out);
 }
 } // namespace sgl

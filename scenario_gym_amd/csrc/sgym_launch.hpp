@@ -3,7 +3,7 @@
 // libsgym_hip.so is linked from one object per kernel family (k_*.hip: `make -j` compiles them side by side, and an
 // experiment on one family rebuilds one object); every object includes sgym_device.hpp and instantiates only the entry
 // points its launcher names.  The host units (sgym_hip.hip and h_*.hip: the C ABI, sgym_host.hpp) call the launchers below and
-// hold no kernel themselves; the setup / sensor / fix-up kernels are k_main.hip's.
+// hold no kernel themselves; the setup / read-out / fix-up kernels are k_main.hip's.
 // Tile shapes: WV == 1 with G in {4, 8, 16, 32, 64} lanes per scenario, or G == 64 with WV in {2, 4} wavefronts per
 // scenario (the plain variant also 8).
 #pragma once
@@ -45,12 +45,15 @@ void rollout_road(int G, int WV, dim3 grid, hipStream_t s, const RolloutArgs &a)
 // caller-supplied points; all pointers DEVICE
 void road_info(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, const sg::RoadGeom &G, bool has_road, const int32_t *scen,
                const double *xy, int64_t n, int cap, int32_t *count, int32_t *geoms, uint32_t *layers);
-// k_obs.hip (sgym_observers.hpp): observers_raster_kernel / observers_future_kernel, one workgroup per observer (scen[k], slot[k]);
-// scen / slot / out DEVICE, layers HOST (1..8 codes of sg_raster_map); out [n][n_layers][nh][nw] resp. [n] bytes
-void observers_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool has_road, const int32_t *scen, const int32_t *slot,
-                      int64_t n, double width, double height, int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out);
-void observers_future(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
-                      unsigned char *out);
+// k_obs.hip (sgym_observers.hpp): map_raster_kernel / look_ahead_kernel, one workgroup per observer k < n: (scen[k], slot[k]), or
+// -- scen == nullptr, n = p.R -- the ego of scenario k.  scen / slot / out / flags DEVICE, layers HOST (1..8 codes of
+// sg_raster_map).  Layer l of observer k goes to out + k * stride + l * nh * nw; look_ahead: out [n] bytes.
+// flags != nullptr (egos only, scenarios of at most 512 entities): the TICK instantiation, which also writes the SG_TERM_* bits.
+void map_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool has_road, const int32_t *scen, const int32_t *slot, int64_t n,
+                double width, double height, int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out, int64_t stride,
+                uint32_t *flags = nullptr);
+void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
+                unsigned char *out);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch
@@ -65,7 +68,7 @@ void rollout_slice(int G, dim3 grid, hipStream_t s, const sg::Params &p, double 
 enum { CTL_GENERAL = 0, CTL_RIDERS = 1, CTL_FAST = 2 };
 void control(int which, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int n_steps, int first, int k0,
              const double *actions, double *tab, int row0, int metrics);
-// k_main.hip: the setup / sensor / fix-up kernels, one launcher per kernel (the block is an argument where the call sites differ)
+// k_main.hip: the setup / read-out / fix-up kernels, one launcher per kernel (the block is an argument where the call sites differ)
 void event_ego_pose(dim3 grid, hipStream_t s, const sg::Params &p, const sg::TabGroups &tg);
 void terminal_flags(dim3 grid, hipStream_t s, const sg::Params &p, double timestep, uint32_t *out);
 void classify_events(dim3 grid, hipStream_t s, const sg::Params &p, double c_tol);
@@ -77,13 +80,6 @@ void slice_final(dim3 grid, hipStream_t s, const sg::Params &p, const sg::SliceA
 void clock(dim3 grid, hipStream_t s, const double *t0, int n_clocks, double timestep, int n_total, double *tt);
 void delay(hipStream_t s, long long ticks); // (tests) one wavefront that does nothing for `ticks` of the 100 MHz clock
 void build_grid(dim3 grid, hipStream_t s, const sg::Params &p, const int32_t *row_scen, int64_t row0, int64_t row_end);
-void raster(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, double width, double height, int nw, int nh, unsigned char *out,
-            int64_t stride);
-void raster_surface(dim3 grid, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, double width, double height, int nw, int nh,
-                    int n_layers, const int32_t *layers, unsigned char *out);
-void observe(dim3 grid, dim3 block, hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, int has_road, double width, double height,
-             int nw, int nh, int n_layers, const int32_t *layers, unsigned char *out, uint32_t *flags);
-void future(dim3 grid, hipStream_t s, const sg::Params &p, double horizon, int n_samples, unsigned char *out);
 void trig32(dim3 grid, hipStream_t s, const double *h, float *sin_out, float *cos_out, int64_t n);
 
 } // namespace sgl

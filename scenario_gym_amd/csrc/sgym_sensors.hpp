@@ -1,20 +1,13 @@
-// sgym_sensors.hpp -- Observation and read-out kernels: future collisions, rasters, collision classification, RSS per tick, the observe kernel, terminal flags.
+// sgym_sensors.hpp -- Read-out kernels: collision classification, RSS per tick, terminal flags (the map and look-ahead observations: sgym_observers.hpp).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
 
 namespace sg {
 
-// ------------------------------------------------------------------------------------------------
-// FutureCollisionDetector._step (sensor/common.py:87-106), SURVEY 8f N2: does the ego's box, moved along its
-// trajectory to n sample times in [t, t + horizon] (np.linspace), overlap any other entity's box at that entity's own
-// trajectory position (clamped outside the trajectory; presence is not consulted)?  One workgroup per scenario, one
-// thread per entity slot, exact fp64 predicate (the operation sequence of the oracle), geometry equal to the ego's
-// never counts (utils.py:59).
-// ------------------------------------------------------------------------------------------------
+// Trajectory.position_at_t with the default extrapolate=(False, False): trajectory.py:185-196
 __device__ __forceinline__ void own_position_clamped(const double *kn, int n, double t, double (&out)[6])
 {
-    // Trajectory.position_at_t with the default extrapolate=(False, False): trajectory.py:185-196
     const double *last = kn + (size_t)(n - 1) * 7;
     if (t < kn[0]) {
 #pragma unroll
@@ -26,190 +19,6 @@ __device__ __forceinline__ void own_position_clamped(const double *kn, int n, do
         own_position_extrap(kn, n, t, out);
     }
 }
-
-// One workgroup per scenario; the (entity, sample) pairs are spread over its 256 threads (the binary searches over the
-// knots are chains of dependent loads: 10 samples one after the other per entity thread took 250 us for 4096 x 64).
-// Pass 1: the ego's corners at every sample time into LDS; pass 2: every other pair against them.
-#define SG_FUT_MAX_SAMPLES 64
-#ifdef SG_UNIT_MAIN // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
-static __global__ __launch_bounds__(256) void future_kernel(Params p, double horizon, int n_samples, unsigned char *out /*[R]*/)
-{
-    __shared__ double ego_c[SG_FUT_MAX_SAMPLES][8];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const ScenStatic &ss = p.sstat[r];
-    const double start = p.sdyn[r].t, stop = start + horizon;
-    const double step = n_samples > 1 ? (stop - start) / (double)(n_samples - 1) : 0.0; // np.linspace
-    auto corners_at = [&](int e, int j, double *C) -> bool {
-        const uint32_t idx = (uint32_t)r * p.EP + e;
-        const LanePtr st(p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64), (idx & 63) * 8u);
-        const int64_t meta = fld<int64_t>(st, ST_META);
-        if ((int)(meta & 0xff) == SG_KIND_NONE) return false;
-        double tj = (double)j * step + start;
-        if (n_samples > 1 && j == n_samples - 1) tj = stop;
-        double pose[6], s, c;
-        own_position_clamped(p.knots + fld<int64_t>(st, ST_KNOT_OFF) * 7, (int)(meta >> 32), tj, pose);
-        sg_sincos(pose[3], s, c);
-        sg_corners(pose[0], pose[1], s, c, fld(st, ST_BW), fld(st, ST_BL), fld(st, ST_BCX), fld(st, ST_BCY), C);
-        return true;
-    };
-    bool hit = false;
-    for (int j0 = 0; j0 < n_samples; j0 += SG_FUT_MAX_SAMPLES) { // more samples than the LDS table holds: in rounds
-        const int nj = min(SG_FUT_MAX_SAMPLES, n_samples - j0);
-        if (tid < nj) {
-            double C[8];
-            corners_at(ss.ego, j0 + tid, C); // the ego is an entity of the scenario: never SG_KIND_NONE
-#pragma unroll
-            for (int k = 0; k < 8; ++k) ego_c[tid][k] = C[k];
-        }
-        __syncthreads();
-        for (int w = tid; w < nj * p.E; w += 256) {
-            const int j = w / p.E, e = w - j * p.E;
-            double C[8];
-            if (e == ss.ego || !corners_at(e, j0 + j, C)) continue;
-            double A[8];
-            bool same = true;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { A[k] = ego_c[j][k]; same = same && (A[k] == C[k]); }
-            if (!same && sg_quads_intersect(A, C)) hit = true;
-        }
-        __syncthreads();
-    }
-    const int any = __syncthreads_or(hit);
-    if (tid == 0) out[r] = (unsigned char)(any != 0);
-}
-#endif // SG_UNIT_MAIN
-
-// ------------------------------------------------------------------------------------------------
-// RasterizedMapSensor, "entity" layer (sensor/map.py:120-192), SURVEY 8f N2: for the ego of every scenario an
-// nh x nw occupancy grid in the ego's frame (rotated by heading + pi/2): cell = 1 iff the grid point lies strictly inside
-// the bounding box of a present entity (the ego included).  One workgroup per scenario: the boxes' corners (fp64, the
-// oracle's operation sequence) are staged in LDS once, then the threads stride over the grid points; the output
-// [R][nh][nw] bytes is written coalesced.  np.linspace / numpy matmul arithmetic as probed (see the oracle).
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sg_linspace_at(double start, double stop, int n, int j)
-{
-    if (n > 1 && j == n - 1) return stop;
-    const double step = n > 1 ? (stop - start) / (double)(n - 1) : 0.0;
-    return (double)j * step + start;
-}
-
-#ifdef SG_UNIT_MAIN // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
-static __global__ __launch_bounds__(512) void raster_kernel(Params p, double width, double height, int nw, int nh,
-                                                     unsigned char *out /*[R][nh][nw] at stride bytes per scenario*/,
-                                                     int64_t stride)
-{
-    __shared__ double cor[8][512]; // (one thread per entity slot of a tile: 256 threads, 512 for scenarios of more than 256)
-    __shared__ double ego_pose[4]; // x, y, sin(theta), cos(theta)
-    __shared__ int ego_pres;
-    __shared__ int near_n;
-    const int r = blockIdx.x, tid = threadIdx.x, nthr = (int)blockDim.x;
-    const ScenStatic &ss = p.sstat[r];
-    if (tid == 0) {
-        const uint32_t idx = (uint32_t)r * p.EP + (uint32_t)ss.ego;
-        const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-        double s, c;
-        sg_sincos(fld(dy, SG_F_POSE + 3) + 3.14159265358979311600e+00 / 2, s, c); // pose[3] + math.pi / 2
-        ego_pose[0] = fld(dy, SG_F_POSE + 0); ego_pose[1] = fld(dy, SG_F_POSE + 1);
-        ego_pose[2] = s; ego_pose[3] = c;
-        ego_pres = fld<uint64_t>(dy, SG_F_PRESENT) != 0;
-    }
-    __syncthreads();
-    const double ex = ego_pose[0], ey = ego_pose[1], s = ego_pose[2], c = ego_pose[3];
-    const bool ego_present = ego_pres != 0;
-    unsigned char *o = out + (size_t)r * stride;
-    // scenarios of more entities than the workgroup has threads go tile by tile; a grid point that an earlier tile's box
-    // covers stays covered (its byte is this thread's own: written and read back by the same thread)
-    for (int e0 = 0; e0 < p.E || e0 == 0; e0 += nthr) {
-        const int e = e0 + tid;
-        if (tid == 0) near_n = 0;
-        __syncthreads();
-        const uint32_t idx = (uint32_t)r * p.EP + (e < p.EP ? e : 0);
-        const LanePtr st(p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64), (idx & 63) * 8u);
-        const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-        const bool present = e < p.E && fld<uint64_t>(dy, SG_F_PRESENT) != 0;
-        if (present) {
-            double C[8];
-            const double x = fld(dy, SG_F_POSE + 0), y = fld(dy, SG_F_POSE + 1), h = fld(dy, SG_F_POSE + 3);
-            double sh, ch;
-            sg_sincos(h, sh, ch);
-            sg_corners(x, y, sh, ch, fld(st, ST_BW), fld(st, ST_BL), fld(st, ST_BCX), fld(st, ST_BCY), C);
-            // only boxes that can reach the grid are tested per cell: every grid point lies within `reach` of the ego (the
-            // grid's half diagonal, generously rounded up), every point of a box within the largest corner distance of its
-            // first corner
-            const double reach = 0.5 * (__builtin_fabs(width) + __builtin_fabs(height)) * 1.0000001 + 1e-6;
-            double far = 0.0;
-#pragma unroll
-            for (int k = 1; k < 4; ++k) far = __builtin_fmax(far, __builtin_fabs(C[2 * k] - C[0]) + __builtin_fabs(C[2 * k + 1] - C[1]));
-            const double dx = C[0] - ex, dyy = C[1] - ey, lim = reach + far * 1.0000001 + 1e-6 * (1.0 + __builtin_fabs(ex) + __builtin_fabs(ey));
-            if (!(dx * dx + dyy * dyy > lim * lim)) { // NaN-safe: keeps the box
-                const int q = atomicAdd(&near_n, 1);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) cor[k][q] = C[k];
-            }
-        }
-        __syncthreads();
-        const int nn = near_n;
-        for (int q = tid; q < nw * nh; q += nthr) {
-            bool hit = e0 > 0 && o[q] != 0;
-            if (!hit && ego_present) {
-                const int i = q / nw, j = q - i * nw;
-                const double x0 = sg_linspace_at(-width / 2, width / 2, nw, j), x1 = sg_linspace_at(-height / 2, height / 2, nh, i);
-                const double px = __builtin_fma(x1, -s, x0 * c) + ex, py = __builtin_fma(x1, c, x0 * s) + ey;
-                for (int k = 0; k < nn && !hit; ++k) {
-                    const double ax = cor[0][k], ay = cor[1][k], bx = cor[2][k], by = cor[3][k];
-                    const double cx = cor[4][k], cy = cor[5][k], dx = cor[6][k], dyy = cor[7][k];
-                    const double orient = (cx - ax) * (dyy - by) - (cy - ay) * (dx - bx);
-                    const double c0 = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-                    const double c1 = (cx - bx) * (py - by) - (cy - by) * (px - bx);
-                    const double c2 = (dx - cx) * (py - cy) - (dyy - cy) * (px - cx);
-                    const double c3 = (ax - dx) * (py - dyy) - (ay - dyy) * (px - dx);
-                    hit = orient > 0 ? (c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0)
-                                     : (orient < 0 && c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0);
-                }
-            }
-            o[q] = ego_present ? (unsigned char)hit : 0; // the reference sensor needs state.poses[entity]
-        }
-        __syncthreads();
-    }
-}
-#endif // SG_UNIT_MAIN
-
-// The road-surface layers of RasterizedMapSensor (sensor/map.py:194-271) on the same grid: one thread per grid point
-// looks its cell up once for all requested layers; out[r][k] for the layers[k] != 0 (the entity layer is raster_kernel's).
-#ifdef SG_UNIT_MAIN // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
-static __global__ __launch_bounds__(256) void raster_surface_kernel(Params p, RoadIndex R, double width, double height, int nw, int nh,
-                                                             int n_layers, const int32_t *layers,
-                                                             unsigned char *out /*[R][n_layers][nh][nw]*/)
-{
-    __shared__ double ego_pose[4];
-    __shared__ int ego_present;
-    const int r = blockIdx.x;
-    const ScenStatic &ss = p.sstat[r];
-    if (threadIdx.x == 0) {
-        const uint32_t idx = (uint32_t)r * p.EP + ss.ego;
-        const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-        double s, c;
-        sg_sincos(fld(dy, SG_F_POSE + 3) + 3.14159265358979311600e+00 / 2, s, c);
-        ego_pose[0] = fld(dy, SG_F_POSE + 0); ego_pose[1] = fld(dy, SG_F_POSE + 1);
-        ego_pose[2] = s; ego_pose[3] = c;
-        ego_present = fld<uint64_t>(dy, SG_F_PRESENT) != 0;
-    }
-    __syncthreads();
-    const double ex = ego_pose[0], ey = ego_pose[1], s = ego_pose[2], c = ego_pose[3];
-    uint32_t want = 0;
-    for (int k = 0; k < n_layers; ++k) want |= (uint32_t)layers[k];
-    const int net = R.net_of_scen ? R.net_of_scen[r] : -1;
-    unsigned char *o = out + (size_t)r * n_layers * nw * nh;
-    for (int q = threadIdx.x; q < nw * nh; q += 256) {
-        const int i = q / nw, j = q - i * nw;
-        const double x0 = sg_linspace_at(-width / 2, width / 2, nw, j), x1 = sg_linspace_at(-height / 2, height / 2, nh, i);
-        const double px = __builtin_fma(x1, -s, x0 * c) + ex, py = __builtin_fma(x1, c, x0 * s) + ey;
-        const uint32_t in = ego_present ? rn_layers_at(R, net, want, px, py) : 0u;
-        for (int k = 0; k < n_layers; ++k)
-            if (layers[k]) o[(size_t)k * nw * nh + q] = (in & (uint32_t)layers[k]) != 0;
-    }
-}
-#endif // SG_UNIT_MAIN
 
 // ------------------------------------------------------------------------------------------------
 // CollisionMetric.record_collision / get_collision_point / angle_between (metrics/collision.py:13-22, 81-203) for the
@@ -484,101 +293,23 @@ static __global__ __launch_bounds__(64) void rss_lines_kernel(Params p, TabGroup
 }
 #endif // SG_UNIT_RSS_LINES
 
-// The observation of one RL tick in ONE launch (sg_tick): every requested map layer -- the entity layer of raster_kernel and
-// the surface layers of raster_surface_kernel, same arithmetic, the grid point computed once -- and the terminal flags of
-// terminal_flags_kernel.  One workgroup per scenario.  has_road: road networks are set (else the surface layers are empty).
-#ifdef SG_UNIT_MAIN // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
-static __global__ __launch_bounds__(512) void observe_kernel(Params p, RoadIndex R, int has_road, double width, double height, int nw,
-                                                      int nh, int n_layers, const int32_t *layers,
-                                                      unsigned char *out /*[R][n_layers][nh][nw]*/, uint32_t *flags /*[R]*/)
+// TERMINAL_CONDITIONS of entities[0] = slot 0 (state/state.py:397-408) on the current state of scenario r: max_length,
+// ego_collision, ego_off_road, from its presence, whether its collision row has a bit set, and its position.  SG_TERM_COLLISION
+// is the caller's: it needs every entity's row.
+__device__ __forceinline__ uint32_t sg_terminal_bits_of_entity0(const Params &p, int r, bool present, bool collides, double x, double y)
 {
-    __shared__ double cor[8][512]; // (one thread per entity slot: 256 threads, 512 for scenarios of 257..512 entities)
-    __shared__ double ego_pose[4]; // x, y, sin(theta), cos(theta)
-    __shared__ int near_n, ego_present, any_coll;
-    const int r = blockIdx.x, e = threadIdx.x;
-    const ScenStatic &ss = p.sstat[r];
-    const uint32_t idx = (uint32_t)r * p.EP + (e < p.EP ? e : 0);
-    const LanePtr st(p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64), (idx & 63) * 8u);
-    const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-    const bool present = e < p.E && fld<uint64_t>(dy, SG_F_PRESENT) != 0;
-    if (e == 0) { near_n = 0; ego_present = 0; any_coll = 0; }
-    __syncthreads();
-    double C[8], x = 0.0, y = 0.0;
-    bool mine = false;
-    if (e < p.E) {
-        const int W = p.FROWS - SG_F_COLL;
-        for (int w = 0; w < W; ++w) mine = mine || fld<uint64_t>(dy, SG_F_COLL + w) != 0;
-        if (present && mine) any_coll = 1;
+    const sg_scenario_state &sd = p.sdyn[r];
+    uint32_t bits = 0;
+    if (sd.t + (sd.t - sd.prev_t) > p.sstat[r].length) bits |= SG_TERM_MAX_LENGTH; // s.t + s.dt > length, State.dt = t - prev_t
+    if (present && collides) bits |= SG_TERM_EGO_COLLISION;
+    bool on_road = false;
+    if (present && p.road) {
+        const RoadIndex RI = *p.road;
+        on_road = (rn_layers_at(RI, RI.net_of_scen[r], SG_LAYER_DRIVEABLE, x, y) & SG_LAYER_DRIVEABLE) != 0;
     }
-    if (present) {
-        x = fld(dy, SG_F_POSE + 0); y = fld(dy, SG_F_POSE + 1);
-        const double h = fld(dy, SG_F_POSE + 3);
-        double s, c;
-        sg_sincos(h, s, c);
-        sg_corners(x, y, s, c, fld(st, ST_BW), fld(st, ST_BL), fld(st, ST_BCX), fld(st, ST_BCY), C);
-    }
-    if (e == ss.ego) {
-        double s, c;
-        sg_sincos(fld(dy, SG_F_POSE + 3) + 3.14159265358979311600e+00 / 2, s, c); // pose[3] + math.pi / 2
-        ego_pose[0] = fld(dy, SG_F_POSE + 0); ego_pose[1] = fld(dy, SG_F_POSE + 1);
-        ego_pose[2] = s; ego_pose[3] = c;
-        ego_present = present;
-    }
-    const int net = (has_road && R.net_of_scen) ? R.net_of_scen[r] : -1;
-    if (e == 0 && flags) { // TERMINAL_CONDITIONS of entities[0], state/state.py:397-408 (terminal_flags_kernel)
-        const sg_scenario_state &sd = p.sdyn[r];
-        uint32_t bits = 0;
-        if (sd.t + (sd.t - sd.prev_t) > ss.length) bits |= SG_TERM_MAX_LENGTH;
-        if (present && mine) bits |= SG_TERM_EGO_COLLISION;
-        bool on_road = false;
-        if (present && has_road) on_road = (rn_layers_at(R, net, SG_LAYER_DRIVEABLE, x, y) & SG_LAYER_DRIVEABLE) != 0;
-        if (!on_road) bits |= SG_TERM_EGO_OFF_ROAD;
-        flags[r] = bits; // SG_TERM_COLLISION joins below, once every entity has reported
-    }
-    __syncthreads();
-    if (e == 0 && flags && any_coll) flags[r] |= SG_TERM_COLLISION;
-    const double ex = ego_pose[0], ey = ego_pose[1], s = ego_pose[2], c = ego_pose[3];
-    bool want_entity = false;
-    uint32_t want = 0;
-    for (int k = 0; k < n_layers; ++k) { want_entity = want_entity || layers[k] == 0; want |= (uint32_t)layers[k]; }
-    if (present && want_entity) { // the boxes that can reach the grid (raster_kernel)
-        const double reach = 0.5 * (__builtin_fabs(width) + __builtin_fabs(height)) * 1.0000001 + 1e-6;
-        double far = 0.0;
-#pragma unroll
-        for (int k = 1; k < 4; ++k) far = __builtin_fmax(far, __builtin_fabs(C[2 * k] - C[0]) + __builtin_fabs(C[2 * k + 1] - C[1]));
-        const double dx = C[0] - ex, dyy = C[1] - ey, lim = reach + far * 1.0000001 + 1e-6 * (1.0 + __builtin_fabs(ex) + __builtin_fabs(ey));
-        if (!(dx * dx + dyy * dyy > lim * lim)) {
-            const int q = atomicAdd(&near_n, 1);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) cor[k][q] = C[k];
-        }
-    }
-    __syncthreads();
-    const int nn = near_n;
-    const bool ego_pres = ego_present != 0;
-    unsigned char *o = out + (size_t)r * n_layers * nw * nh;
-    for (int q = e; q < nw * nh; q += (int)blockDim.x) {
-        const int i = q / nw, j = q - i * nw;
-        const double x0 = sg_linspace_at(-width / 2, width / 2, nw, j), x1 = sg_linspace_at(-height / 2, height / 2, nh, i);
-        const double px = __builtin_fma(x1, -s, x0 * c) + ex, py = __builtin_fma(x1, c, x0 * s) + ey;
-        bool hit = false;
-        for (int k = 0; k < nn && !hit; ++k) {
-            const double ax = cor[0][k], ay = cor[1][k], bx = cor[2][k], by = cor[3][k];
-            const double cx = cor[4][k], cy = cor[5][k], dx = cor[6][k], dyy = cor[7][k];
-            const double orient = (cx - ax) * (dyy - by) - (cy - ay) * (dx - bx);
-            const double c0 = (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-            const double c1 = (cx - bx) * (py - by) - (cy - by) * (px - bx);
-            const double c2 = (dx - cx) * (py - cy) - (dyy - cy) * (px - cx);
-            const double c3 = (ax - dx) * (py - dyy) - (ay - dyy) * (px - dx);
-            hit = orient > 0 ? (c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0)
-                             : (orient < 0 && c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0);
-        }
-        const uint32_t in = (ego_pres && want && has_road) ? rn_layers_at(R, net, want, px, py) : 0u;
-        for (int k = 0; k < n_layers; ++k)
-            o[(size_t)k * nw * nh + q] = layers[k] == 0 ? (unsigned char)(ego_pres && hit) : (unsigned char)((in & (uint32_t)layers[k]) != 0);
-    }
+    if (!on_road) bits |= SG_TERM_EGO_OFF_ROAD;
+    return bits;
 }
-#endif // SG_UNIT_MAIN
 
 // TERMINAL_CONDITIONS (state/state.py:397-408), all four evaluated on the CURRENT state of every scenario, whatever the
 // handle's terminal mask says: out[r] = SG_TERM_* bits.  The reward of the reference's RL agent asks exactly this of a
@@ -587,9 +318,8 @@ static __global__ __launch_bounds__(512) void observe_kernel(Params p, RoadIndex
 static __global__ __launch_bounds__(64) void terminal_flags_kernel(Params p, double timestep, uint32_t *out)
 {
     const int r = blockIdx.x, lane = threadIdx.x;
-    const sg_scenario_state &sd = p.sdyn[r];
     const int W = p.FROWS - SG_F_COLL;
-    bool any_coll = false, ego_coll = false, e0_present = false;
+    bool any_coll = false, e0_coll = false, e0_present = false;
     double x0 = 0.0, y0 = 0.0;
     for (int e = lane; e < p.E; e += 64) {
         const uint32_t idx = (uint32_t)r * p.EP + e;
@@ -600,24 +330,13 @@ static __global__ __launch_bounds__(64) void terminal_flags_kernel(Params p, dou
         any_coll = any_coll || (present && mine);
         if (e == 0) {
             e0_present = present;
-            ego_coll = present && mine;
+            e0_coll = mine;
             x0 = fld(dy, SG_F_POSE + 0);
             y0 = fld(dy, SG_F_POSE + 1);
         }
     }
-    uint32_t bits = 0;
-    if (sd.t + (sd.t - sd.prev_t) > p.sstat[r].length) bits |= SG_TERM_MAX_LENGTH; // s.t + s.dt > length, State.dt = t - prev_t
-    if (sg_any(any_coll)) bits |= SG_TERM_COLLISION;
-    if (lane == 0) {
-        if (ego_coll) bits |= SG_TERM_EGO_COLLISION;
-        bool on_road = false;
-        if (e0_present && p.road) {
-            const RoadIndex RI = *p.road;
-            on_road = (rn_layers_at(RI, RI.net_of_scen[r], SG_LAYER_DRIVEABLE, x0, y0) & SG_LAYER_DRIVEABLE) != 0;
-        }
-        if (!on_road) bits |= SG_TERM_EGO_OFF_ROAD;
-        out[r] = bits;
-    }
+    const bool any = sg_any(any_coll);
+    if (lane == 0) out[r] = sg_terminal_bits_of_entity0(p, r, e0_present, e0_coll, x0, y0) | (any ? SG_TERM_COLLISION : 0u);
 }
 #endif // SG_UNIT_MAIN
 

@@ -303,6 +303,57 @@ def test_ego_list_equals_the_ego_calls(sga):
 
 
 @gpu
+@pytest.mark.parametrize("E", [5, 300, 560])
+def test_ego_calls_with_layer_lists_of_any_order_and_length_match_the_oracle(sga, oracle, E):
+    """The ego calls on layer lists that only the one-pass raster serves in a single body: sg_raster_map with the entity layer
+    not first and twice ([2, 0, 1, 0]) and with nine layers (two launches of at most eight), sg_tick with [2, 0, 1] -- at 5
+    entity slots (a tile of less than a wavefront in a 256-thread block), 300 (the 512-thread block) and 560 (tile by tile, the
+    multi-kernel step; sg_tick's branch of two launches).  After the reset and after 25 steps every byte equals
+    oracle.raster_map on the state's poses; the flags of sg_tick equal sg_terminal_flags of a twin handle stepped by sg_step.
+    The ego of the synthetic family (an agent in slot 0) is in the scene throughout, so scenario 1 gets a late spawner as its
+    ego: not in the scene at the reset.  Seeds chosen with the oracle on the CPU so that every layer has set bytes."""
+    R, (w, h, nw, nh) = 3, GRIDS[1]
+    eng, packed, nets, net_of = _batch_with_networks(sga, R, E, seed={5: 5, 300: 1, 560: 1}[E])
+    first, n_knots = packed.knots[packed.knot_off[E:2 * E], 0], np.diff(packed.knot_off[E:2 * E + 1])
+    packed.ego[1] = np.nonzero((n_knots > 1) & (first > 0.2) & (first <= 2.0))[0][0]
+    twin = sga.RolloutEngine(R, E, timestep=0.1)
+    for e in (eng, twin):
+        e.upload(packed)
+        e.set_road_networks(nets, net_of)
+    onets = [oracle.RoadNetworkArrays(a) for a in nets]
+    ones = dict.fromkeys(ALL_LAYERS, 0)
+    absent = 0
+
+    def expected(st, layers):
+        want = np.stack([oracle.raster_map(st["poses"][r], packed.bbox[r * E:(r + 1) * E], int(packed.ego[r]),
+                                           onets[net_of[r]] if net_of[r] >= 0 else None, layers, width=w, height=h, nw=nw, nh=nh)
+                         for r in range(R)])
+        for l, code in enumerate(layers):
+            ones[code] += int(want[:, l].sum())
+        return want
+
+    for advance in (0, 24):  # the states after 0 and 25 steps for sg_raster_map, sg_tick from each of them
+        eng.step(advance)
+        twin.step(advance)
+        st = eng.state()
+        assert int(st["n_steps"].max()) == (25 if advance else 0)
+        absent += sum(not st["present"][r, packed.ego[r]] for r in range(R))
+        for layers in ([2, 0, 1, 0], ALL_LAYERS + [0]):
+            got, want = eng.raster_map(layers, w, h, nw, nh), expected(st, layers)
+            assert got.shape == want.shape == (R, len(layers), nh, nw)
+            assert np.array_equal(got, want), (advance, layers, int((got != want).sum()))
+        obs, flags = eng.tick(None, [2, 0, 1], w, h, nw, nh)
+        twin.step(1)
+        want = expected(eng.state(), [2, 0, 1])
+        assert np.array_equal(obs, want), (advance, int((obs != want).sum()))
+        assert np.array_equal(flags, twin.terminal_flags()), (advance, flags)
+    eng.close()
+    twin.close()
+    assert all(n > 0 for n in ones.values()), ones
+    assert absent > 0
+
+
+@gpu
 def test_device_outputs(sga):
     """Device outputs (torch tensors the kernels write directly) equal the host outputs; a device-output call queued right
     behind sg_step, without a synchronize in between, sees the stepped state."""
