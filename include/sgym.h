@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers) */
 
 typedef enum {
     SG_OK = 0,
@@ -427,6 +427,33 @@ int sg_raster_map_observers(sg_handle *h, double width, double height, int32_t n
  * consulted and a box equal to the observer's never counts, as in sg_future_collision, whose answer the observer
  * (r, ego of r) reproduces.  out: [n_observers] bytes, HOST or DEVICE as in sg_raster_map_observers. */
 int sg_future_collision_observers(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device);
+
+/* The vector observation: the k nearest entities around the ego of every scenario (n = n_scenarios observers), in the ego's
+ * frame.  The reference has no such sensor (its State.get_entities_in_radius answers for one scenario on the host); this is
+ * the policy input driving-RL code uses in place of a map image.  For observer o = slot so of scenario r with pose
+ * (xo, yo, ho), velocity (vxo, vyo) and (s, c) = sin, cos of ho, every OTHER slot e of r that is in State.poses gives
+ * dx = xe - xo, dy = ye - yo, d2 = dx * dx + dy * dy (plain fp64).  e is a candidate iff d2 is finite and
+ * d2 <= radius * radius (inclusive; radius = +inf: every present entity).  The candidates are ordered by ascending (d2, slot)
+ * -- ties in d2 go to the lower slot -- and the first k give, with (se, ce) = sin, cos of he:
+ *   feat[o][j][0..7]  dx*c + dy*s (along the observer's heading), dy*c - dx*s (left positive), ce*c + se*s and se*c - ce*s
+ *                     (cos, sin of the relative heading), dvx*c + dvy*s and dvy*c - dvx*s (dvx = vxe - vxo, dvy = vye - vyo),
+ *                     the neighbour's box length, its box width; rows behind the last neighbour are +0.0
+ *   slots[o][j]       the neighbour's slot, -1 behind the last.  May be NULL
+ *   count[o]          the number of candidates within the radius (it may exceed k).  May be NULL
+ * An observer that is not in State.poses gets count -1, slots -1 and features 0.0 (as sg_road_info answers for such a slot).
+ * Every byte of the outputs given is written.  feat: [n][k][8] doubles, slots: [n][k], count: [n]; HOST (outputs_device == 0,
+ * synchronous, through the observation scratch) or DEVICE (queued on sg_stream(h), not waited for), as in
+ * sg_raster_map_observers, and a persistent rollout launch that gave up is reported as there.  SG_ERR_INVALID: k < 1, k > 32,
+ * radius NaN or negative, feat NULL.  SG_ERR_STATE before sg_upload.  One wavefront per observer keeps the keys of up to 512
+ * slots in registers and selects in k rounds of a cross-lane minimum; wider scenarios take one workgroup per observer.  Not
+ * part of the sg_tick graph: queue it behind sg_tick with device outputs. */
+int sg_nearest_entities(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_nearest_entities for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_nearest_entities_observers(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count,
+                                  int32_t outputs_device);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

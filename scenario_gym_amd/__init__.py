@@ -8,6 +8,7 @@ from .agent import (  # noqa: F401
     ExternalVehicleAgent,
     FutureCollisionDetector,
     GlobalCollisionDetector,
+    NearestEntitiesSensor,
     PIDController,
     RasterizedMapSensor,
     ReplayTrajectoryController,
@@ -26,7 +27,8 @@ from .agent import (  # noqa: F401
 )
 from .engine import PackedScenarios, RolloutEngine  # noqa: F401
 from .observation import (  # noqa: F401
-    CollisionObservation, FutureCollisionObservation, MapObservation, Observation, SingleEntityObservation, combine_observations,
+    CollisionObservation, FutureCollisionObservation, MapObservation, NearestEntitiesObservation, Observation, SingleEntityObservation,
+    combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401
 from .gym import BatchedScenarioGym, ScenarioGym  # noqa: F401

@@ -34,6 +34,7 @@ SYMBOLS = (
     "sg_group_create", "sg_group_destroy", "sg_group_size", "sg_group_handle", "sg_group_upload", "sg_group_rollout",
     "sg_group_read_metrics", "sg_group_last_error", "sg_host_alloc", "sg_host_free", "sg_road_info", "sg_road_info_points",
     "sg_set_observers", "sg_raster_map_observers", "sg_future_collision_observers",
+    "sg_nearest_entities", "sg_nearest_entities_observers",
 )
 
 
@@ -198,6 +199,8 @@ def load():
     lib.sg_set_observers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sg_raster_map_observers.argtypes = [H, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_future_collision_observers.argtypes = [H, C.c_double, C.c_int32, C.c_void_p, C.c_int32]
+    lib.sg_nearest_entities.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_nearest_entities_observers.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_debug_trig32.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

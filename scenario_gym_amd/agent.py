@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _lib as L
 from .entity import Entity
-from .observation import (CollisionObservation, FutureCollisionObservation, MapObservation, SingleEntityObservation,
-                          combine_observations)
+from .observation import (CollisionObservation, FutureCollisionObservation, MapObservation, NearestEntitiesObservation,
+                          SingleEntityObservation, combine_observations)
 from .scenario import Scenario
 
 
@@ -137,6 +137,24 @@ class RasterizedMapSensor(Sensor):
     def _step(self, state):
         m = state.raster_map(self.layers, self.width, self.height, self.nw, self.nh, entity=self.entity)
         return MapObservation(self.entity, *state.get_entity_data(self.entity), m if self.channels_first else m.transpose(1, 2, 0))
+
+
+class NearestEntitiesSensor(Sensor):
+    """The vector observation most driving policies take in place of a map image (no counterpart in the reference): the k
+    nearest entities within `radius` of the sensor's entity, in that entity's frame, computed on the device for the whole
+    batch: sg_nearest_entities for the egos, one sg_nearest_entities_observers call for the sensors of all other entities."""
+
+    def __init__(self, entity: Entity, k: int = 8, radius: float = float("inf")):
+        super().__init__(entity)
+        self.k, self.radius = int(k), float(radius)
+
+    @property
+    def output_shape(self):
+        return (self.k, 8)
+
+    def _step(self, state):
+        neighbours, features = state.nearest_entities(self.k, self.radius, entity=self.entity)
+        return NearestEntitiesObservation(self.entity, *state.get_entity_data(self.entity), neighbours, features)
 
 
 class GlobalCollisionDetector(Sensor):

@@ -1,5 +1,5 @@
-// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map and look-ahead observations of the
-// ego and of a list of observers.
+// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead and nearest-entity
+// observations of the ego and of a list of observers.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -303,4 +303,51 @@ extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32
     HIP_TRY(h, hipMemcpyAsync(out, d, (size_t)h->n_obs, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+// ---- the nearest-entity vector observation (nearest_kernel, sgym_observers.hpp) -------------------------------------------
+// n observers: the ego of every scenario (observers == false) or the list of sg_set_observers.  Host outputs pass through the
+// observation scratch: [n][k][8] doubles, then [n][k] slots, then [n] counts (the last two only when asked for).
+static int nearest_call(sg_handle *h, const char *who, bool observers, int32_t k, double radius, double *feat, int32_t *slots,
+                        int32_t *count, int32_t outputs_device)
+{
+    if (k < 1 || k > SG_NEAR_MAX_K) return fail(h, SG_ERR_INVALID, "%s: k=%d outside 1..%d", who, k, SG_NEAR_MAX_K);
+    if (!(radius >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: radius is negative or NaN", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
+        sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, feat, slots, count);
+        HIP_TRY(h, hipGetLastError());
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    const size_t feat_bytes = (size_t)n * k * 8 * sizeof(double), slot_bytes = (size_t)n * k * sizeof(int32_t), count_bytes = (size_t)n * sizeof(int32_t);
+    unsigned char *d = nullptr;
+    if (int rc = obs_scratch(h, feat_bytes + slot_bytes + count_bytes, &d)) return rc;
+    double *const d_feat = reinterpret_cast<double *>(d);
+    int32_t *const d_slots = slots ? reinterpret_cast<int32_t *>(d + feat_bytes) : nullptr;
+    int32_t *const d_count = count ? reinterpret_cast<int32_t *>(d + feat_bytes + slot_bytes) : nullptr;
+    sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, d_feat, d_slots, d_count);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(feat, d_feat, feat_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (slots) HIP_TRY(h, hipMemcpyAsync(slots, d_slots, slot_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (count) HIP_TRY(h, hipMemcpyAsync(count, d_count, count_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+extern "C" int sg_nearest_entities(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return nearest_call(h, "sg_nearest_entities", false, k, radius, feat, slots, count, outputs_device);
+}
+
+extern "C" int sg_nearest_entities_observers(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count,
+                                             int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return nearest_call(h, "sg_nearest_entities_observers", true, k, radius, feat, slots, count, outputs_device);
 }

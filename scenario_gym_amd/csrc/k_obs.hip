@@ -1,5 +1,5 @@
-// k_obs.hip -- map_raster_kernel / look_ahead_kernel: the map and look-ahead observations of the ego of every scenario or of
-// a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
+// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel: the map, look-ahead and nearest-entity observations of
+// the ego of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -23,5 +23,18 @@ void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const i
 {
     if (n <= 0) return;
     sg::look_ahead_kernel<<<dim3((unsigned)n), dim3(256), 0, s>>>(p, scen, slot, horizon, n_samples, out);
+}
+
+void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int k, double radius, double *feat,
+             int32_t *slots, int32_t *count)
+{
+    if (n <= 0) return;
+    const double r2 = radius * radius; // (+inf for an infinite radius: every finite distance passes)
+    const dim3 per_wave((unsigned)((n + 3) / 4)), block(256);
+    if (p.E > 512) sg::nearest_kernel<0><<<dim3((unsigned)n), block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+    else if (p.E > 256) sg::nearest_kernel<8><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+    else if (p.E > 128) sg::nearest_kernel<4><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+    else if (p.E > 64) sg::nearest_kernel<2><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+    else sg::nearest_kernel<1><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
 }
 } // namespace sgl

@@ -54,6 +54,11 @@ void map_raster(hipStream_t s, const sg::Params &p, const sg::RoadIndex &R, bool
                 uint32_t *flags = nullptr);
 void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, int n_samples,
                 unsigned char *out);
+// nearest_kernel<NB>: the k <= 32 nearest present entities within `radius` of observer o < n (the same two lists), ascending
+// (squared distance, slot).  feat [n][k][8], slots [n][k] (or nullptr), count [n] (or nullptr), all DEVICE.  One wavefront per
+// observer for scenarios of at most 512 entities (NB = 1, 2, 4, 8 blocks of 64 slots), one workgroup beyond (NB = 0).
+void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int k, double radius, double *feat,
+             int32_t *slots, int32_t *count);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -1,5 +1,5 @@
-// sgym_observers.hpp -- The map and look-ahead observations: one raster kernel and one look-ahead kernel for the ego of every
-// scenario and for a caller-given list of observers (any entity).
+// sgym_observers.hpp -- The map, look-ahead and nearest-entity observations: one raster kernel, one look-ahead kernel and one
+// nearest-entity kernel for the ego of every scenario and for a caller-given list of observers (any entity).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
@@ -224,6 +224,195 @@ static __global__ __launch_bounds__(256) void look_ahead_kernel(Params p, const 
     }
     const int any = __syncthreads_or(hit);
     if (tid == 0) out[k] = (unsigned char)(any != 0);
+}
+#endif // SG_UNIT_OBS
+
+// ------------------------------------------------------------------------------------------------
+// The vector observation: the k nearest entities around an observer, in the observer's frame (no counterpart in the
+// reference, whose State.get_entities_in_radius answers for one scenario on the host).  Candidates are the other present
+// entities of the observer's scenario with a finite squared distance d2 = dx * dx + dy * dy <= radius * radius (plain fp64,
+// unfused); the order is ascending (d2, slot).  A non-negative finite double orders as its bit pattern does, so the key of
+// the selection is d2 as a 64-bit integer and "no candidate" is the all-ones word, above every finite key.
+// ------------------------------------------------------------------------------------------------
+#define SG_NEAR_MAX_K 32
+constexpr uint64_t NEAR_NONE = ~0ull;
+constexpr int NEAR_NO_SLOT = 0x7fffffff;
+
+// the first dynamic / static row of padded entity index idx = r * EP + slot: field f is at [f * 64]
+__device__ __forceinline__ const double *near_dyn(const Params &p, uint32_t idx)
+{
+    return p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64) + (idx & 63);
+}
+__device__ __forceinline__ const double *near_stat(const Params &p, uint32_t idx)
+{
+    return p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64) + (idx & 63);
+}
+
+// the observer: scenario, slot, position, velocity, sin / cos of its heading, presence (the same for every lane of its wavefronts)
+struct NearObserver {
+    double x, y, vx, vy, s, c;
+    int r, slot, present;
+};
+
+__device__ __forceinline__ NearObserver near_observer(const Params &p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t o)
+{
+    NearObserver f;
+    f.r = obs_scen ? obs_scen[o] : (int)o;
+    f.slot = obs_scen ? obs_slot[o] : p.sstat[o].ego;
+    const double *d = near_dyn(p, (uint32_t)f.r * p.EP + (uint32_t)f.slot);
+    f.present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
+    f.x = d[(SG_F_POSE + 0) * 64]; f.y = d[(SG_F_POSE + 1) * 64];
+    f.vx = d[(SG_F_VEL + 0) * 64]; f.vy = d[(SG_F_VEL + 1) * 64];
+    sg_sincos(d[(SG_F_POSE + 3) * 64], f.s, f.c);
+    return f;
+}
+
+// the key of slot e of the observer's scenario.  A lane without a slot (e >= E) reads the observer's own rows, which are
+// there, and gets NEAR_NONE like the observer itself.
+__device__ __forceinline__ uint64_t near_key(const Params &p, const NearObserver &f, int e, double r2)
+{
+    const bool other = e < p.E && e != f.slot;
+    const double *d = near_dyn(p, (uint32_t)f.r * p.EP + (uint32_t)(other ? e : f.slot));
+    const bool present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
+    const double dx = d[(SG_F_POSE + 0) * 64] - f.x, dy = d[(SG_F_POSE + 1) * 64] - f.y;
+    const double d2 = dx * dx + dy * dy;
+    const bool in = other && present && d2 <= r2 && d2 < __builtin_inf(); // (a NaN fails both)
+    return in ? (uint64_t)__double_as_longlong(d2) : NEAR_NONE;
+}
+
+// the smallest (key, slot) of the wavefront, in every lane: a butterfly of cross-lane reads, no LDS
+__device__ __forceinline__ void near_wave_min(uint64_t &key, int &slot)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const uint64_t ok = __shfl_xor(key, m, 64);
+        const int os = __shfl_xor(slot, m, 64);
+        const bool take = ok < key || (ok == key && os < slot);
+        key = take ? ok : key;
+        slot = take ? os : slot;
+    }
+}
+
+// k rounds over the N register entries of every lane: the wavefront's minimum, which its owner retires (slots are unique;
+// an entry that holds nothing has slot NEAR_NO_SLOT).  Lane j returns the slot of round j, -1 once the candidates ran out.
+template <int N>
+__device__ __forceinline__ int near_select(uint64_t (&key)[N], const int (&slot)[N], int k, int lane)
+{
+    int mine = -1;
+    for (int j = 0; j < k; ++j) {
+        uint64_t bk = NEAR_NONE;
+        int bs = NEAR_NO_SLOT;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const bool take = key[i] < bk || (key[i] == bk && slot[i] < bs);
+            bk = take ? key[i] : bk;
+            bs = take ? slot[i] : bs;
+        }
+        near_wave_min(bk, bs);
+        if (bk == NEAR_NONE) break; // (the same in every lane)
+#pragma unroll
+        for (int i = 0; i < N; ++i) key[i] = slot[i] == bs ? NEAR_NONE : key[i];
+        if (lane == j) mine = bs;
+    }
+    return mine;
+}
+
+// row `lane` of observer o: the eight features of neighbour nb (zeros for nb < 0), its slot, and the observer's count
+__device__ __forceinline__ void near_store(const Params &p, const NearObserver &f, int64_t o, int k, int lane, int nb, int total,
+                                           double *feat, int32_t *slots, int32_t *count)
+{
+    if (lane == 0 && count) count[o] = total;
+    if (lane >= k) return;
+    double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (nb >= 0) {
+        const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)nb;
+        const double *d = near_dyn(p, idx), *st = near_stat(p, idx);
+        const double dx = d[(SG_F_POSE + 0) * 64] - f.x, dy = d[(SG_F_POSE + 1) * 64] - f.y;
+        const double dvx = d[(SG_F_VEL + 0) * 64] - f.vx, dvy = d[(SG_F_VEL + 1) * 64] - f.vy;
+        double se, ce;
+        sg_sincos(d[(SG_F_POSE + 3) * 64], se, ce);
+        v[0] = dx * f.c + dy * f.s;
+        v[1] = dy * f.c - dx * f.s;
+        v[2] = ce * f.c + se * f.s;
+        v[3] = se * f.c - ce * f.s;
+        v[4] = dvx * f.c + dvy * f.s;
+        v[5] = dvy * f.c - dvx * f.s;
+        v[6] = st[ST_BL * 64];
+        v[7] = st[ST_BW * 64];
+    }
+    double *row = feat + ((size_t)o * k + lane) * 8; // (64 bytes per lane, consecutive lanes consecutive rows)
+#pragma unroll
+    for (int m = 0; m < 8; ++m) row[m] = v[m];
+    if (slots) slots[(size_t)o * k + lane] = nb;
+}
+
+// Observer o < n: (obs_scen[o], obs_slot[o]), or -- obs_scen == nullptr -- the ego of scenario o.  feat [n][k][8] fp64, slots
+// [n][k] (-1 behind the last neighbour; may be nullptr), count [n] (candidates within the radius, it may exceed k; -1 for an
+// observer that is not present, whose rows are zeros; may be nullptr).  Every byte of the three is written.  1 <= k <= 32.
+// NB > 0 (scenarios of at most NB * 64 <= 512 entities): one wavefront per observer, four observers per workgroup.  Lane l owns
+// the slots l, l + 64, ... of the scenario's NB blocks -- a load is one 512-byte row per block -- and keeps their keys in
+// registers; the selection is near_select; then lane j computes and stores the features of neighbour j.
+// NB == 0 (the wide path, up to 16384 entities): one workgroup of four wavefronts per observer.  Wavefront w takes the
+// blocks w, w + 4, ...: round j rescans them for the smallest (key, slot) above the one round j - 1 found (the keys of up to 64
+// slots per lane do not fit registers; the rows come from the caches).  The <= 4 * k finalists go through LDS to wavefront 0,
+// which selects among them as the narrow path does.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+template <int NB>
+static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n, int k,
+                                                             double r2, double *feat, int32_t *slots, int32_t *count)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t o = NB ? (int64_t)blockIdx.x * 4 + w : (int64_t)blockIdx.x;
+    if (o >= n) return; // (NB > 0: the whole wavefront, which meets no barrier)
+    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    if (!f.present) { // (the whole workgroup on the wide path)
+        if (NB || w == 0) near_store(p, f, o, k, lane, -1, -1, feat, slots, count);
+        return;
+    }
+    if constexpr (NB > 0) {
+        uint64_t key[NB];
+        int slot[NB], total = 0;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            slot[j] = lane + 64 * j;
+            key[j] = near_key(p, f, slot[j], r2);
+            total += __popcll(__ballot(key[j] != NEAR_NONE));
+        }
+        const int nb = near_select<NB>(key, slot, k, lane);
+        near_store(p, f, o, k, lane, nb, total, feat, slots, count);
+    } else {
+        __shared__ uint64_t fin_key[4 * SG_NEAR_MAX_K];
+        __shared__ int fin_slot[4 * SG_NEAR_MAX_K];
+        __shared__ int fin_total[4];
+        const int n_blocks = (p.E + 63) >> 6;
+        uint64_t last_key = 0, my_key = NEAR_NONE;
+        int last_slot = -1, my_slot = NEAR_NO_SLOT, total = 0;
+        for (int j = 0; j < k; ++j) {
+            uint64_t bk = NEAR_NONE;
+            int bs = NEAR_NO_SLOT;
+            for (int b = w; b < n_blocks; b += 4) {
+                const int e = b * 64 + lane;
+                const uint64_t ke = near_key(p, f, e, r2);
+                if (j == 0) total += __popcll(__ballot(ke != NEAR_NONE));
+                const bool after = ke > last_key || (ke == last_key && e > last_slot);
+                const bool take = after && (ke < bk || (ke == bk && e < bs));
+                bk = take ? ke : bk;
+                bs = take ? e : bs;
+            }
+            near_wave_min(bk, bs);
+            if (bk == NEAR_NONE) break; // (the same in every lane: the stripe has run out)
+            if (lane == j) { my_key = bk; my_slot = bs; }
+            last_key = bk; last_slot = bs;
+        }
+        if (lane < SG_NEAR_MAX_K) { fin_key[w * SG_NEAR_MAX_K + lane] = my_key; fin_slot[w * SG_NEAR_MAX_K + lane] = my_slot; }
+        if (lane == 0) fin_total[w] = total;
+        __syncthreads();
+        if (w != 0) return;
+        uint64_t key[2] = {fin_key[lane], fin_key[lane + 64]};
+        const int slot[2] = {fin_slot[lane], fin_slot[lane + 64]};
+        const int nb = near_select<2>(key, slot, k, lane);
+        near_store(p, f, o, k, lane, nb, fin_total[0] + fin_total[1] + fin_total[2] + fin_total[3], feat, slots, count);
+    }
 }
 #endif // SG_UNIT_OBS
 

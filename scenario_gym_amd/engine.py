@@ -344,7 +344,7 @@ class RolloutEngine:
             cap = int(count.max())
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -392,6 +392,40 @@ class RolloutEngine:
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
             return out
         return out.astype(bool)
+
+    def _nearest(self, call, n, k, radius, torch_out):
+        k = int(k)
+        if torch_out:
+            import torch
+
+            dev = f"cuda:{self.cfg.device}"
+            feat = torch.empty((n, k, 8), dtype=torch.float64, device=dev)
+            slots = torch.empty((n, k), dtype=torch.int32, device=dev)
+            count = torch.empty((n,), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(feat.device).synchronize()  # (the allocator's work before the handle's stream writes)
+            ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+        else:
+            feat, slots, count = np.empty((n, k, 8), np.float64), np.empty((n, k), np.int32), np.empty(n, np.int32)
+            ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        name = call.__name__
+        self._check(call(self.h, k, float(radius), ptr(feat), ptr(slots), ptr(count), int(bool(torch_out))), name)
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return feat, slots, count
+
+    def nearest_entities(self, k, radius=float("inf"), torch_out=False):
+        """The vector observation of the ego of every scenario (sg_nearest_entities): the k <= 32 nearest other entities that are
+        in the scene and within `radius` of the ego (inclusive), by ascending (squared distance, slot).  Returns (feat [R, k, 8]
+        float64, slots [R, k] int32, count [R] int32): per neighbour the longitudinal and lateral offset in the ego's frame, cos
+        and sin of the relative heading, the relative velocity in that frame, box length and width; slots -1 and features 0
+        behind the last neighbour; count = the candidates within the radius (it may exceed k), -1 for an ego that is not in the
+        scene.  torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
+        return self._nearest(self.lib.sg_nearest_entities, self.R, k, radius, torch_out)
+
+    def nearest_entities_observers(self, k, radius=float("inf"), torch_out=False):
+        """nearest_entities for every observer of set_observers (sg_nearest_entities_observers): (feat [n, k, 8], slots [n, k],
+        count [n]); empty arrays when no observers are set."""
+        return self._nearest(self.lib.sg_nearest_entities_observers, self._n_obs, k, radius, torch_out)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

@@ -12,7 +12,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .agent import CombinedSensor, FutureCollisionDetector, RasterizedMapSensor, _create_agent
+from .agent import CombinedSensor, FutureCollisionDetector, NearestEntitiesSensor, RasterizedMapSensor, _create_agent
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_scenarios
@@ -49,7 +49,7 @@ class BatchedScenarioGym:
         self._rec = None
         self._fut = None
         self._rss_cache = None
-        self._observers: list = []   # (scenario index, entity slot) of the non-ego entities that carry a map / look-ahead sensor
+        self._observers: list = []   # (scenario index, entity slot) of the non-ego entities that carry a map / look-ahead / nearest-entity sensor
         self._observer_of: dict = {}  # ... -> position in the engine's observer list
         self._observers_sent = 0     # how many of them the engine knows
 
@@ -275,7 +275,7 @@ class BatchedScenarioGym:
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
-        # the observers of the batch: every map / look-ahead sensor of a non-ego entity (inside a CombinedSensor too), so that
+        # the observers of the batch: every map / look-ahead / nearest-entity sensor of a non-ego entity (inside a CombinedSensor too), so that
         # one device call per step and sensor configuration serves all of them; a sensor met later joins when it is first stepped
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
 
@@ -289,7 +289,7 @@ class BatchedScenarioGym:
         for i, sc in enumerate(self.scenarios):
             for a in agents[i].values():
                 for s in leaves(getattr(a, "sensor", None)):
-                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector)) and s.entity is not sc.ego and s.entity in sc.entities:
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
                         self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
@@ -339,7 +339,7 @@ class BatchedScenarioGym:
             k = self._observer_of[(i, slot)] = len(self._observers)
             self._observers.append((i, slot))
             if self._fut:
-                self._fut = {key: v for key, v in self._fut.items() if key[0] not in ("obs_map", "obs_fut")}
+                self._fut = {key: v for key, v in self._fut.items() if key[0] not in ("obs_map", "obs_fut", "obs_near")}
         return k
 
     def _send_observers(self):
@@ -368,6 +368,24 @@ class BatchedScenarioGym:
             self._send_observers()
             self._fut = dict(self._fut or {})
             self._fut[key] = self.engine.future_collision_observers(horizon, n_samples)
+        return self._fut[key]
+
+    def _nearest_observers(self, k: int, radius: float):
+        """(feat [n_observers, k, 8], slots [n_observers, k], count [n_observers]) of NearestEntitiesSensor for every registered
+        observer: one device call per state and sensor configuration, cached like _raster_map_observers."""
+        key = ("obs_near", k, radius)
+        if self._fut is None or key not in self._fut:
+            self._send_observers()
+            self._fut = dict(self._fut or {})
+            self._fut[key] = self.engine.nearest_entities_observers(k, radius)
+        return self._fut[key]
+
+    def _nearest(self, k: int, radius: float):
+        """The same for the ego of every scenario ([R, ...]), cached per state."""
+        key = ("near", k, radius)
+        if self._fut is None or key not in self._fut:
+            self._fut = dict(self._fut or {})
+            self._fut[key] = self.engine.nearest_entities(k, radius)
         return self._fut[key]
 
     def _road_info(self, cap: int = 32):

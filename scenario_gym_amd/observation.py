@@ -48,6 +48,17 @@ class MapObservation(SingleEntityObservation):
     map: np.ndarray
 
 
+@dataclass
+class NearestEntitiesObservation(SingleEntityObservation):
+    """The vector observation (no counterpart in the reference): `neighbours`, the nearest entities within the sensor's radius
+    by ascending (squared distance, position in the scenario), at most k of them, and `features` [k, 8] -- per neighbour the
+    longitudinal and lateral offset in the observer's frame, cos and sin of the relative heading, the relative velocity in
+    that frame, box length and width; rows behind the last neighbour are zero."""
+
+    neighbours: list
+    features: np.ndarray
+
+
 def combine_observations(*classes, prefixes: Optional[Sequence[Optional[str]]] = None):
     """observation.py:31-84: a dataclass holding the fields of all `classes` in order.  A field name that an earlier class
     already contributed is skipped -- or, with `prefixes` (one per class), taken as "<prefix>_<name>"; a name that is still

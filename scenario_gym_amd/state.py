@@ -206,6 +206,20 @@ class State:
             return self._gym._raster_map_observers(tuple(layers), float(width), float(height), int(nw), int(nh))[k]
         return self._gym._raster_map(tuple(layers), float(width), float(height), int(nw), int(nh))[self._i]
 
+    def nearest_entities(self, k: int = 8, radius: float = float("inf"), entity: Optional[Entity] = None):
+        """NearestEntitiesSensor(entity, k, radius) at the current state, computed on the device: (neighbours, features) -- the
+        at most k nearest other entities in `poses` within `radius` of `entity` (any entity of the scenario, default the ego)
+        by ascending (squared distance, position in the scenario), and their [k, 8] feature rows in the entity's frame (zeros
+        behind the last).  ([], zeros) for an entity that is not in `poses`."""
+        o = self._observer(entity)
+        if o is not None:
+            feat, slots, _ = self._gym._nearest_observers(int(k), float(radius))
+        else:
+            feat, slots, _ = self._gym._nearest(int(k), float(radius))
+            o = self._i
+        ents = self._scenario.entities
+        return [ents[j] for j in slots[o] if j >= 0], feat[o].copy()
+
     def get_road_info_at_entity(self, e: Entity):
         """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's
         position -- "Road", "Intersection", "Lane", "Pavement", "Crossing", "Building", the objects the scenario's RoadNetwork

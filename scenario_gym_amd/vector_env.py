@@ -134,5 +134,22 @@ class VectorScenarioEnv:
             return obs, torch.as_tensor(env, device=obs.device), torch.as_tensor(slot, device=obs.device)
         return obs, env, slot
 
+    def nearest_entities(self, k: int = 8, radius: float = float("inf")):
+        """The vector observation of the ego of every environment at the current state (sg_nearest_entities): (feat [R, k, 8],
+        slots [R, k] positions in scenarios[i].entities or -1, count [R]).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        return self.engine.nearest_entities(k, radius, torch_out=self.torch_obs)
+
+    def observe_entities_nearest(self, k: int = 8, radius: float = float("inf")):
+        """The vector observation of every observer of set_observers at the current state (sg_nearest_entities_observers):
+        (feat [n, k, 8], slots [n, k], count [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy
+        arrays."""
+        env, slot = self._obs_env, self._obs_slot
+        feat, slots, count = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
+        if self.torch_obs:
+            import torch
+
+            return feat, slots, count, torch.as_tensor(env, device=feat.device), torch.as_tensor(slot, device=feat.device)
+        return feat, slots, count, env, slot
+
     def close(self):
         self.engine.close()
