@@ -43,23 +43,30 @@ static hipError_t enqueue_map_layers(sg_handle *h, double width, double height, 
     return e;
 }
 
-// the raster launches of sg_raster_map / sg_raster_map_device on the handle's stream; *d_out = [R][n_layers][nh][nw]
-static int raster_map_launch(sg_handle *h, const char *who, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
-                             const int32_t *layers, unsigned char **d_out, size_t *bytes_out)
+// what every map observation refuses first (sg_tick and sg_raster_map_observers take at most eight layers on top of it)
+static bool bad_map_geometry(double width, double height, int32_t nw, int32_t nh, int32_t n_layers, const int32_t *layers)
 {
-    if (!layers || n_layers < 1 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
-        return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
+    return !layers || n_layers < 1 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0);
+}
+
+// The map layers of every scenario's ego, [R][n_layers][nh][nw], through the observation scratch: into the host array `out` (waited
+// for), or with out == nullptr left in the scratch for *d_out (on the handle's stream, not waited for)
+static int raster_map_launch(sg_handle *h, const char *who, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
+                             const int32_t *layers, uint8_t *out, const uint8_t **d_out)
+{
+    if (bad_map_geometry(width, height, nw, nh, n_layers, layers)) return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    int rc = check_layers(h, who, n_layers, layers);
-    if (rc) return rc;
+    if (const int rc = check_layers(h, who, n_layers, layers)) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t bytes = (size_t)h->R * n_layers * nw * nh;
+    if (out)
+        return deliver(h, who, false, obs_scratch, {{out, bytes}}, 0, [&](void *const *d) {
+            return enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, static_cast<unsigned char *>(d[0]));
+        });
     unsigned char *d = nullptr;
-    rc = obs_scratch(h, bytes, &d);
-    if (rc) return rc;
+    if (const int rc = obs_scratch(h, bytes, &d)) return rc;
     HIP_TRY(h, enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, d));
     *d_out = d;
-    *bytes_out = bytes;
     return SG_OK;
 }
 
@@ -67,44 +74,21 @@ extern "C" int sg_raster_map(sg_handle *h, double width, double height, int32_t 
                              const int32_t *layers, uint8_t *out)
 {
     if (!h || !out) return h ? fail(h, SG_ERR_INVALID, "sg_raster_map: bad argument") : SG_ERR_INVALID;
-    unsigned char *d = nullptr;
-    size_t bytes = 0;
-    int rc = raster_map_launch(h, "sg_raster_map", width, height, nw, nh, n_layers, layers, &d, &bytes);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (const int rcq = check_queue(h)) return rcq; // (a persistent launch that gave up: sticky)
-    return SG_OK;
+    return raster_map_launch(h, "sg_raster_map", width, height, nw, nh, n_layers, layers, out, nullptr);
 }
 
 extern "C" int sg_raster_map_device(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
                                     const int32_t *layers, const uint8_t **d_out)
 {
     if (!h || !d_out) return h ? fail(h, SG_ERR_INVALID, "sg_raster_map_device: bad argument") : SG_ERR_INVALID;
-    unsigned char *d = nullptr;
-    size_t bytes = 0;
-    int rc = raster_map_launch(h, "sg_raster_map_device", width, height, nw, nh, n_layers, layers, &d, &bytes);
-    if (rc) return rc;
-    *d_out = d;
-    return SG_OK;
+    return raster_map_launch(h, "sg_raster_map_device", width, height, nw, nh, n_layers, layers, nullptr, d_out);
 }
 
 extern "C" int sg_raster_entities(sg_handle *h, double width, double height, int32_t nw, int32_t nh, uint8_t *out)
 {
-    if (!h || !out || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
-        return h ? fail(h, SG_ERR_INVALID, "sg_raster_entities: bad argument") : SG_ERR_INVALID;
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_entities: no scenarios uploaded");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t bytes = (size_t)h->R * nw * nh;
-    unsigned char *d = nullptr;
-    int rc = obs_scratch(h, bytes, &d);
-    if (rc) return rc;
+    if (!h || !out) return h ? fail(h, SG_ERR_INVALID, "sg_raster_entities: bad argument") : SG_ERR_INVALID;
     const int32_t entity_layer = 0;
-    hipError_t e = enqueue_map_layers(h, width, height, nw, nh, 1, &entity_layer, d);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_raster_entities: %s", hipGetErrorString(e));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
+    return raster_map_launch(h, "sg_raster_entities", width, height, nw, nh, 1, &entity_layer, out, nullptr);
 }
 
 // One tick of the RL loop (integrations/openaigym.py:171-226) as ONE graph launch: the step with the policy's actions, the
@@ -115,7 +99,7 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
 {
     if (!h) return SG_ERR_INVALID;
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_tick: no scenarios uploaded");
-    if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
+    if (bad_map_geometry(width, height, nw, nh, n_layers, layers) || n_layers > 8)
         return fail(h, SG_ERR_INVALID, "sg_tick: bad observation geometry (1..8 layers)");
     if (h->n_ext > 0) return fail(h, SG_ERR_STATE, "sg_tick: batches with caller-run agents are driven through sg_set_external_poses + sg_step");
     bool grew = false;
@@ -206,27 +190,7 @@ extern "C" int sg_terminal_flags(sg_handle *h, uint32_t *out, const uint32_t **d
     return SG_OK;
 }
 
-extern "C" int sg_future_collision(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out)
-{
-    if (!h || !out || n_samples < 1 || !(horizon >= 0.0)) return h ? fail(h, SG_ERR_INVALID, "sg_future_collision: bad argument") : SG_ERR_INVALID;
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_future_collision: no scenarios uploaded");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    unsigned char *d = nullptr;
-    int rc = obs_scratch(h, (size_t)h->R, &d);
-    if (rc) return rc;
-    sgl::look_ahead(h->stream, h->p, nullptr, nullptr, h->R, horizon, n_samples, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, (size_t)h->R, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(h, SG_ERR_HIP, "sg_future_collision: %s", hipGetErrorString(e));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
-}
-
 // ---- observations for any entity: a list of observers (sgym_observers.hpp) -----------------------------------------------
-// the sticky give-up of check_queue for a call that does not wait for the stream: a launch still running is judged by the
-// next call that synchronises
-static int queue_gave_up(sg_handle *h) { return h->q_failed ? fail(h, SG_ERR_HIP, "%s", h->q_msg) : SG_OK; }
-
 // the observer list on the device: the scenarios in the first half of the buffer, the slots in the second
 static int32_t *observer_scenarios(const sg_handle *h) { return h->observers.as<int32_t>(); }
 static int32_t *observer_slots(const sg_handle *h) { return h->observers.as<int32_t>() + h->observers.cap / (2 * sizeof(int32_t)); }
@@ -258,51 +222,47 @@ extern "C" int sg_raster_map_observers(sg_handle *h, double width, double height
                                        const int32_t *layers, uint8_t *out, int32_t outputs_device)
 {
     if (!h) return SG_ERR_INVALID;
-    if (!layers || n_layers < 1 || n_layers > 8 || nw < 1 || nh < 1 || !(width >= 0.0) || !(height >= 0.0))
-        return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
+    if (bad_map_geometry(width, height, nw, nh, n_layers, layers) || n_layers > 8) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_map_observers: no scenarios uploaded");
     if (const int rc = check_layers(h, "sg_raster_map_observers", n_layers, layers)) return rc;
     if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
     if (!out) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: null out");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
     const size_t bytes_each = (size_t)n_layers * nw * nh;
-    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
-        sgl::map_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, out, (int64_t)bytes_each);
-        HIP_TRY(h, hipGetLastError());
-        return queue_gave_up(h); // (not waited for: what is known so far)
-    }
-    const size_t bytes = (size_t)h->n_obs * bytes_each;
-    unsigned char *d = nullptr;
-    if (int rc = obs_scratch(h, bytes, &d)) return rc;
-    sgl::map_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, h->n_obs, width, height, nw, nh, n_layers, layers, d, (int64_t)bytes_each);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
+    return deliver(h, "sg_raster_map_observers", outputs_device, obs_scratch, {{out, (size_t)h->n_obs * bytes_each}}, 0, [&](void *const *d) {
+        sgl::map_raster(h->stream, h->p, h->road, h->has_road, observer_scenarios(h), observer_slots(h), h->n_obs, width, height, nw, nh, n_layers,
+                        layers, static_cast<unsigned char *>(d[0]), (int64_t)bytes_each);
+        return hipGetLastError();
+    });
+}
+
+// ---- the look-ahead (look_ahead_kernel, sgym_observers.hpp) ---------------------------------------------------------------
+// n observers: the ego of every scenario (observers == false) or the list of sg_set_observers; one byte each
+static int future_call(sg_handle *h, const char *who, bool observers, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device)
+{
+    if (n_samples < 1 || !(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!out) return fail(h, SG_ERR_INVALID, "%s: null out", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    return deliver(h, who, outputs_device, obs_scratch, {{out, (size_t)n}}, 0, [&](void *const *d) {
+        sgl::look_ahead(h->stream, h->p, d_scen, d_slot, n, horizon, n_samples, static_cast<unsigned char *>(d[0]));
+        return hipGetLastError();
+    });
+}
+
+extern "C" int sg_future_collision(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out)
+{
+    if (!h || !out) return h ? fail(h, SG_ERR_INVALID, "sg_future_collision: bad argument") : SG_ERR_INVALID;
+    return future_call(h, "sg_future_collision", false, horizon, n_samples, out, 0);
 }
 
 extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device)
 {
     if (!h) return SG_ERR_INVALID;
-    if (n_samples < 1 || !(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: bad argument");
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_future_collision_observers: no scenarios uploaded");
-    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!out) return fail(h, SG_ERR_INVALID, "sg_future_collision_observers: null out");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observer_scenarios(h), *d_slot = observer_slots(h);
-    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
-        sgl::look_ahead(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, out);
-        HIP_TRY(h, hipGetLastError());
-        return queue_gave_up(h); // (not waited for: what is known so far)
-    }
-    unsigned char *d = nullptr;
-    if (int rc = obs_scratch(h, (size_t)h->n_obs, &d)) return rc;
-    sgl::look_ahead(h->stream, h->p, d_scen, d_slot, h->n_obs, horizon, n_samples, d);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, d, (size_t)h->n_obs, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
+    return future_call(h, "sg_future_collision_observers", true, horizon, n_samples, out, outputs_device);
 }
 
 // ---- the nearest-entity vector observation (nearest_kernel, sgym_observers.hpp) -------------------------------------------
@@ -319,24 +279,13 @@ static int nearest_call(sg_handle *h, const char *who, bool observers, int32_t k
     if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    if (outputs_device) { // stream-ordered, not synchronised (sg_road_info)
-        sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, feat, slots, count);
-        HIP_TRY(h, hipGetLastError());
-        return queue_gave_up(h); // (not waited for: what is known so far)
-    }
-    const size_t feat_bytes = (size_t)n * k * 8 * sizeof(double), slot_bytes = (size_t)n * k * sizeof(int32_t), count_bytes = (size_t)n * sizeof(int32_t);
-    unsigned char *d = nullptr;
-    if (int rc = obs_scratch(h, feat_bytes + slot_bytes + count_bytes, &d)) return rc;
-    double *const d_feat = reinterpret_cast<double *>(d);
-    int32_t *const d_slots = slots ? reinterpret_cast<int32_t *>(d + feat_bytes) : nullptr;
-    int32_t *const d_count = count ? reinterpret_cast<int32_t *>(d + feat_bytes + slot_bytes) : nullptr;
-    sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, d_feat, d_slots, d_count);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(feat, d_feat, feat_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (slots) HIP_TRY(h, hipMemcpyAsync(slots, d_slots, slot_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (count) HIP_TRY(h, hipMemcpyAsync(count, d_count, count_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
+    const size_t nk = (size_t)n * k;
+    return deliver(h, who, outputs_device, obs_scratch, {{feat, nk * 8 * sizeof(double)}, {slots, nk * sizeof(int32_t)}, {count, (size_t)n * sizeof(int32_t)}}, 0,
+                   [&](void *const *d) {
+                       sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, static_cast<double *>(d[0]), static_cast<int32_t *>(d[1]),
+                                    static_cast<int32_t *>(d[2]));
+                       return hipGetLastError();
+                   });
 }
 
 extern "C" int sg_nearest_entities(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count, int32_t outputs_device)

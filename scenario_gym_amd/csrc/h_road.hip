@@ -301,21 +301,25 @@ static int road_info_scratch(sg_handle *h, size_t bytes, unsigned char **out)
     return SG_OK;
 }
 
-// n queries on the handle's stream (behind whatever rollout work is pending there) with HOST outputs; d_scen / d_xy: the points
-// already in the scratch behind the outputs' room (nullptr: the entity slots)
-static int road_info_host(sg_handle *h, unsigned char *d, int64_t n, const int32_t *d_scen, const double *d_xy, int32_t cap, int32_t *count,
+// n queries on the handle's stream (behind whatever rollout work is pending there) with HOST outputs, through the scratch as
+// [count][layers][geoms]; scen / xy: the n points on the host, which go into the scratch behind the outputs' room -- [n][2]
+// doubles, then [n] scenarios -- in front of the kernel (nullptr: the entity slots)
+static int road_info_host(sg_handle *h, const char *who, int64_t n, const int32_t *scen, const double *xy, int32_t cap, int32_t *count,
                           int32_t *geoms, uint32_t *layers)
 {
-    int32_t *d_count = reinterpret_cast<int32_t *>(d);
-    uint32_t *d_layers = reinterpret_cast<uint32_t *>(d + (size_t)n * 4);
-    int32_t *d_geoms = reinterpret_cast<int32_t *>(d + (size_t)n * 8);
-    sgl::road_info(h->stream, h->p, h->road, h->geom, h->has_road, d_scen, d_xy, n, cap, d_count, geoms ? d_geoms : nullptr, layers ? d_layers : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (layers) HIP_TRY(h, hipMemcpyAsync(layers, d_layers, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (geoms && cap > 0) HIP_TRY(h, hipMemcpyAsync(geoms, d_geoms, (size_t)n * cap * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return check_queue(h); // (a persistent launch that gave up: sticky)
+    const size_t nb = (size_t)n * 4;
+    return deliver(h, who, false, road_info_scratch, {{count, nb}, {layers, nb}, {geoms, nb * cap}}, xy ? nb * 5 : 0, [&](void *const *d) {
+        double *const d_xy = static_cast<double *>(d[3]);
+        int32_t *const d_scen = xy ? reinterpret_cast<int32_t *>(d_xy + 2 * n) : nullptr;
+        if (xy) {
+            hipError_t e = hipMemcpyAsync(d_xy, xy, nb * 4, hipMemcpyHostToDevice, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_scen, scen, nb, hipMemcpyHostToDevice, h->stream);
+            if (e != hipSuccess) return e;
+        }
+        sgl::road_info(h->stream, h->p, h->road, h->geom, h->has_road, d_scen, d_xy, n, cap, static_cast<int32_t *>(d[0]), static_cast<int32_t *>(d[2]),
+                       static_cast<uint32_t *>(d[1]));
+        return hipGetLastError();
+    });
 }
 
 extern "C" int sg_road_info(sg_handle *h, int32_t cap, int32_t *count, int32_t *geoms, uint32_t *layers, int32_t outputs_device)
@@ -331,9 +335,7 @@ extern "C" int sg_road_info(sg_handle *h, int32_t cap, int32_t *count, int32_t *
         HIP_TRY(h, hipGetLastError());
         return SG_OK;
     }
-    unsigned char *d = nullptr;
-    if (int rc = road_info_scratch(h, (size_t)n * 4 * (2 + (size_t)cap), &d)) return rc;
-    return road_info_host(h, d, n, nullptr, nullptr, cap, count, geoms, layers);
+    return road_info_host(h, "sg_road_info", n, nullptr, nullptr, cap, count, geoms, layers);
 }
 
 extern "C" int sg_road_info_points(sg_handle *h, int64_t n, const int32_t *scenario_of_point, const double *xy, int32_t cap, int32_t *count,
@@ -348,12 +350,5 @@ extern "C" int sg_road_info_points(sg_handle *h, int64_t n, const int32_t *scena
             return fail(h, SG_ERR_INVALID, "sg_road_info_points: scenario_of_point[%lld]=%d out of range", (long long)i, scenario_of_point[i]);
     if (n == 0) return SG_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const size_t out_bytes = (size_t)n * 4 * (2 + (size_t)cap), xy_off = (out_bytes + 15) & ~(size_t)15;
-    unsigned char *d = nullptr;
-    if (int rc = road_info_scratch(h, xy_off + (size_t)n * 20, &d)) return rc;
-    double *d_xy = reinterpret_cast<double *>(d + xy_off);
-    int32_t *d_scen = reinterpret_cast<int32_t *>(d + xy_off + (size_t)n * 16);
-    HIP_TRY(h, hipMemcpyAsync(d_xy, xy, (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_scen, scenario_of_point, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    return road_info_host(h, d, n, d_scen, d_xy, cap, count, geoms, layers);
+    return road_info_host(h, "sg_road_info_points", n, scenario_of_point, xy, cap, count, geoms, layers);
 }

@@ -8,7 +8,9 @@
 
 #include <algorithm>
 #include <functional>
+#include <initializer_list>
 #include <atomic>
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -397,5 +399,54 @@ int launch_wide(sg_handle *h, int n_steps, int do_reset, int force, const double
 int ensure_rss(sg_handle *h, bool *fresh);
 int ensure_rssq(sg_handle *h);
 void launch_rss_alone(sg_handle *h, int reset);
+
+// ---- delivery of an observation (h_observe.hip, h_road.hip) ----
+// the sticky give-up of check_queue for a call that does not wait for the stream: a launch still running is judged by the
+// next call that synchronises
+inline int queue_gave_up(sg_handle *h) { return h->q_failed ? fail(h, SG_ERR_HIP, "%s", h->q_msg) : SG_OK; }
+
+// One output array of an observation call: the caller's pointer (null: an optional array that was not asked for) and its bytes.
+struct OutPart {
+    void *out;
+    size_t bytes;
+};
+
+// Runs `launch(d)` -- hipError_t(void *const d[4]), the launches on the handle's stream -- with d[i] where part i is to be
+// written, and delivers the (at most three) parts.  outputs_device: d[i] is the caller's pointer; stream-ordered, not waited for, what is
+// known of the queue so far.  Else the parts lie one behind the other, in their order, from the start of the scratch that
+// `scratch(h, bytes, &base)` hands out (a part that was not asked for keeps its room and gets d[i] = null), with `tail` more bytes
+// for the launch's own use behind them at the next multiple of 16, d[3]; one copy per part asked for, the wait for the stream,
+// check_queue.  A failure of the HIP runtime reads "<who>: <step> failed: <error string>".
+template <typename Launch>
+int deliver(sg_handle *h, const char *who, bool outputs_device, int (*scratch)(sg_handle *, size_t, unsigned char **),
+            std::initializer_list<OutPart> parts, size_t tail, Launch launch)
+{
+    assert(parts.size() <= 3 && (tail == 0 || !outputs_device));
+    const auto hip = [&](hipError_t e, const char *step) {
+        return e == hipSuccess ? SG_OK : fail(h, SG_ERR_HIP, "%s: %s failed: %s", who, step, hipGetErrorString(e));
+    };
+    void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t n = 0, bytes = 0;
+    for (const OutPart &p : parts) { d[n++] = p.out; bytes += p.bytes; }
+    if (outputs_device) {
+        if (const int rc = hip(launch(d), "the launch")) return rc;
+        return queue_gave_up(h); // (not waited for: what is known so far)
+    }
+    const size_t tail_off = (bytes + 15) & ~(size_t)15;
+    unsigned char *base = nullptr;
+    if (const int rc = scratch(h, tail ? tail_off + tail : bytes, &base)) return rc;
+    if (tail) d[3] = base + tail_off;
+    n = 0;
+    for (const OutPart &p : parts) { if (p.out) d[n] = base; ++n; base += p.bytes; }
+    if (const int rc = hip(launch(d), "the launch")) return rc;
+    n = 0;
+    for (const OutPart &p : parts) {
+        if (p.out && p.bytes)
+            if (const int rc = hip(hipMemcpyAsync(p.out, d[n], p.bytes, hipMemcpyDeviceToHost, h->stream), "hipMemcpyAsync")) return rc;
+        ++n;
+    }
+    if (const int rc = hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) return rc;
+    return check_queue(h); // (a persistent launch that gave up: sticky)
+}
 
 } // namespace sgh

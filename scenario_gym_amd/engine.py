@@ -86,6 +86,25 @@ def terminal_mask(conditions):
     return mask
 
 
+# SocialForceParameters (pedestrian/social_force.py:16-30): the model parameters of set_social_force / of a set_ped_models row
+SOCIAL_FORCE_DEFAULTS = dict(relaxation_time=1.5, ped_repulse_V=1.0, ped_repulse_sigma=1.0, ped_attract_C=0.0, sight_weight=0.5,
+                             sight_weight_use=True, sight_angle=200, max_speed_factor=1.3, bias_lon=0.0, bias_lat=0.0,
+                             imp_boundary_repulse_U=2.0, imp_boundary_repulse_R=0.1)
+_SF = SOCIAL_FORCE_DEFAULTS
+PED_BEHAVIOURS = {"social_force": L.PED_SOCIAL_FORCE, "random_walk": L.PED_RANDOM_WALK}
+
+
+def _social_force(who, params):
+    """sg_social_force from set_social_force()'s parameter names; what `params` leaves out takes that method's default."""
+    unknown = set(params) - set(SOCIAL_FORCE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"{who}: unknown parameters {sorted(unknown)}")
+    d = {**SOCIAL_FORCE_DEFAULTS, **params}
+    d["sight_weight_use"] = float(bool(d["sight_weight_use"]))
+    d["cos_sight"] = float(np.cos(d.pop("sight_angle") / 2 * np.pi / 180))
+    return L.SgSocialForce(**d)
+
+
 class RolloutEngine:
     """ScenarioGym's step loop for a whole batch, resident on one MI355X."""
 
@@ -111,18 +130,21 @@ class RolloutEngine:
         elif social_force is not None:
             self.set_social_force(**social_force)
 
-    def set_social_force(self, relaxation_time=1.5, ped_repulse_V=1.0, ped_repulse_sigma=1.0, ped_attract_C=0.0,
-                         sight_weight=0.5, sight_weight_use=True, sight_angle=200, max_speed_factor=1.3,
-                         bias_lon=0.0, bias_lat=0.0, imp_boundary_repulse_U=2.0, imp_boundary_repulse_R=0.1,
+    def set_social_force(self, relaxation_time=_SF["relaxation_time"], ped_repulse_V=_SF["ped_repulse_V"],
+                         ped_repulse_sigma=_SF["ped_repulse_sigma"], ped_attract_C=_SF["ped_attract_C"], sight_weight=_SF["sight_weight"],
+                         sight_weight_use=_SF["sight_weight_use"], sight_angle=_SF["sight_angle"], max_speed_factor=_SF["max_speed_factor"],
+                         bias_lon=_SF["bias_lon"], bias_lat=_SF["bias_lat"], imp_boundary_repulse_U=_SF["imp_boundary_repulse_U"],
+                         imp_boundary_repulse_R=_SF["imp_boundary_repulse_R"],
                          std_lon=0.0, std_lat=0.0, noise=None, noise_seed=0, normals=None, behaviour="social_force"):
         """SocialForceParameters of every pedestrian agent on this handle (pedestrian/social_force.py:16-30);
         call before upload().  behaviour="random_walk": the pedestrians follow RandomWalk (pedestrian/random_walk.py:22-44)
         instead, which reads bias_lon / bias_lat / std_lon / std_lat only.  std_lon / std_lat with noise="device" (counter-based generator on the GPU, the default when
         a std is non-zero) or noise="stream" + normals[R, n] (the variates numpy's legacy generator would hand out:
         np.random.RandomState(k).standard_normal(n) per scenario) are the random fluctuations of :106-108."""
-        sf = L.SgSocialForce(relaxation_time, ped_repulse_V, ped_repulse_sigma, ped_attract_C, sight_weight,
-                             float(bool(sight_weight_use)), float(np.cos(sight_angle / 2 * np.pi / 180)),
-                             max_speed_factor, bias_lon, bias_lat, imp_boundary_repulse_U, imp_boundary_repulse_R)
+        sf = _social_force("set_social_force", dict(
+            relaxation_time=relaxation_time, ped_repulse_V=ped_repulse_V, ped_repulse_sigma=ped_repulse_sigma, ped_attract_C=ped_attract_C,
+            sight_weight=sight_weight, sight_weight_use=sight_weight_use, sight_angle=sight_angle, max_speed_factor=max_speed_factor,
+            bias_lon=bias_lon, bias_lat=bias_lat, imp_boundary_repulse_U=imp_boundary_repulse_U, imp_boundary_repulse_R=imp_boundary_repulse_R))
         self._check(self.lib.sg_set_social_force(self.h, C.byref(sf)), "sg_set_social_force")
         self.set_ped_behaviour(behaviour)
         if noise is None:
@@ -142,18 +164,8 @@ class RolloutEngine:
             std_lon, std_lat = float(m.pop("std_lon", 0.0)), float(m.pop("std_lat", 0.0))
             for k in ("noise", "noise_seed", "normals"):
                 m.pop(k, None)
-            d = dict(relaxation_time=1.5, ped_repulse_V=1.0, ped_repulse_sigma=1.0, ped_attract_C=0.0, sight_weight=0.5,
-                     sight_weight_use=True, sight_angle=200, max_speed_factor=1.3, bias_lon=0.0, bias_lat=0.0,
-                     imp_boundary_repulse_U=2.0, imp_boundary_repulse_R=0.1)
-            unknown = set(m) - set(d)
-            if unknown:
-                raise TypeError(f"set_ped_models: unknown parameters {sorted(unknown)}")
-            d.update(m)
-            rows[i].behaviour = {"social_force": L.PED_SOCIAL_FORCE, "random_walk": L.PED_RANDOM_WALK}[beh]
-            rows[i].params = L.SgSocialForce(d["relaxation_time"], d["ped_repulse_V"], d["ped_repulse_sigma"], d["ped_attract_C"],
-                                             d["sight_weight"], float(bool(d["sight_weight_use"])),
-                                             float(np.cos(d["sight_angle"] / 2 * np.pi / 180)), d["max_speed_factor"], d["bias_lon"],
-                                             d["bias_lat"], d["imp_boundary_repulse_U"], d["imp_boundary_repulse_R"])
+            rows[i].params = _social_force("set_ped_models", m)
+            rows[i].behaviour = PED_BEHAVIOURS[beh]
             rows[i].std_lon, rows[i].std_lat = std_lon, std_lat
             any_std = any_std or std_lon != 0 or std_lat != 0
         if noise is None:
@@ -169,8 +181,7 @@ class RolloutEngine:
 
     def set_ped_behaviour(self, behaviour="social_force"):
         """sg_set_ped_behaviour: "social_force" or "random_walk" for every pedestrian agent of the handle; before upload()."""
-        code = {"social_force": L.PED_SOCIAL_FORCE, "random_walk": L.PED_RANDOM_WALK}[behaviour]
-        self._check(self.lib.sg_set_ped_behaviour(self.h, code), "sg_set_ped_behaviour")
+        self._check(self.lib.sg_set_ped_behaviour(self.h, PED_BEHAVIOURS[behaviour]), "sg_set_ped_behaviour")
 
     def set_ped_noise(self, mode="off", std_lon=0.0, std_lat=0.0, normals=None, seed=0):
         """sg_set_ped_noise: "off", "stream" (normals[R, n] standard normal variates per scenario) or "device"."""
@@ -188,6 +199,43 @@ class RolloutEngine:
     def _check(self, rc, what):
         if rc != L.SG_OK:
             raise RuntimeError(f"{what} failed ({rc}): {self.lib.sg_last_error(self.h).decode()}")
+
+    def _outputs(self, torch_out, *specs):
+        """One uninitialised output array per (shape, dtype name): numpy arrays, or with torch_out torch tensors in HBM that
+        the handle's stream may write at once.  Returns (arrays, their addresses for the C side -- None for an empty array)."""
+        if torch_out:
+            import torch
+
+            dev = f"cuda:{self.cfg.device}"
+            arrs = tuple(torch.empty(shape, dtype=getattr(torch, dt), device=dev) for shape, dt in specs)
+            torch.cuda.current_stream(arrs[0].device).synchronize()  # (the allocator's work before the handle's stream writes)
+            return arrs, tuple(a.data_ptr() if a.numel() else None for a in arrs)
+        arrs = tuple(np.empty(shape, dt) for shape, dt in specs)
+        return arrs, tuple(a.ctypes.data if a.size else None for a in arrs)
+
+    def _actions(self, actions, n):
+        """The actions of n ticks ([n, R, 2]: numpy, a float64 torch tensor on the device, or None) for sg_step / sg_tick:
+        (the array the pointer points into, pointer, on_device)."""
+        if actions is None:
+            return None, None, 0
+        if hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
+            # a torch tensor on this GPU (fp64, contiguous): its device pointer goes down as it is
+            import torch
+
+            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * self.R * 2
+            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
+            return actions, actions.data_ptr(), 1
+        actions = np.ascontiguousarray(actions, np.float64).reshape(n, self.R, 2)
+        return actions, actions.ctypes.data, 0
+
+    def _device_view(self, ptr, shape, typestr):
+        """Zero-copy torch tensor over device memory of the handle."""
+        import torch
+
+        class _Arr:
+            __cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(ptr), False), version=2)
+
+        return torch.as_tensor(_Arr(), device=f"cuda:{self.cfg.device}")
 
     def close(self):
         if getattr(self, "h", None):
@@ -230,17 +278,7 @@ class RolloutEngine:
 
     def step(self, n_steps=1, actions=None):
         """n x ScenarioGym.step(); actions [n, R, 2] (accel, steer) for external-action slots."""
-        ptr, on_device = None, 0
-        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
-            # a torch tensor on this GPU (fp64, contiguous): its device pointer goes down as it is
-            import torch
-
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n_steps * self.R * 2
-            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
-            ptr, on_device = actions.data_ptr(), 1
-        elif actions is not None:
-            actions = np.ascontiguousarray(actions, np.float64).reshape(n_steps, self.R, 2)
-            ptr = actions.ctypes.data
+        _keep, ptr, on_device = self._actions(actions, n_steps)
         self._check(self.lib.sg_step(self.h, int(n_steps), ptr, on_device), "sg_step")
 
     def set_external_poses(self, poses):
@@ -305,24 +343,26 @@ class RolloutEngine:
         their LAYER_* bits.  Host form: numpy arrays; when some entity lies in more than `cap` geometries the query is
         repeated once with cap = count.max(), so no list comes back truncated.  torch_out: torch tensors in HBM (int32;
         layers as int32 bit patterns) the kernel writes directly, ordered after it; lists stop at `cap` there, count tells."""
-        R, E, cap = self.R, self.E, int(cap)
-        if torch_out:
-            import torch
+        R, E = self.R, self.E
 
-            dev = f"cuda:{self.cfg.device}"
-            count = torch.empty((R, E), dtype=torch.int32, device=dev)
-            geoms = torch.empty((R, E, cap), dtype=torch.int32, device=dev)
-            layers = torch.empty((R, E), dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(count.device).synchronize()  # (the allocator's work before the handle's stream writes)
-            self._check(self.lib.sg_road_info(self.h, cap, count.data_ptr(), geoms.data_ptr() if cap > 0 else None,
-                                              layers.data_ptr(), 1), "sg_road_info")
+        def call(cap, *ptrs):
+            self._check(self.lib.sg_road_info(self.h, cap, *ptrs, int(bool(torch_out))), "sg_road_info")
+
+        if torch_out:
+            (count, geoms, layers), (p_count, p_geoms, p_layers) = self._outputs(
+                True, ((R, E), "int32"), ((R, E, int(cap)), "int32"), ((R, E), "int32"))
+            call(int(cap), p_count, p_geoms, p_layers)
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
             return count, geoms, layers
+        return self._road_query((R, E), cap, call)
+
+    def _road_query(self, shape, cap, call):
+        """(count [shape], geoms [shape, cap], layers [shape]) as numpy arrays filled by call(cap, count, geoms, layers -- their
+        addresses); asked once more with cap = count.max() when some list did not fit."""
+        cap = int(cap)
         while True:
-            count, layers = np.empty((R, E), np.int32), np.empty((R, E), np.uint32)
-            geoms = np.empty((R, E, cap), np.int32)
-            self._check(self.lib.sg_road_info(self.h, cap, count.ctypes.data, geoms.ctypes.data if cap > 0 else None,
-                                              layers.ctypes.data, 0), "sg_road_info")
+            (count, geoms, layers), (_, p_geoms, _) = self._outputs(False, (shape, "int32"), (shape + (cap,), "int32"), (shape, "uint32"))
+            call(cap, count.ctypes.data, p_geoms, layers.ctypes.data)  # (count is never null: no points is a valid question)
             if count.size == 0 or int(count.max()) <= cap:
                 return count, geoms, layers
             cap = int(count.max())
@@ -333,15 +373,11 @@ class RolloutEngine:
         as road_info does, re-queried once when a list would not fit."""
         xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
         scen = np.ascontiguousarray(np.broadcast_to(np.asarray(scenario_of_point, np.int32), (len(xy),)))
-        n, cap = len(xy), int(cap)
-        while True:
-            count, layers = np.empty(n, np.int32), np.empty(n, np.uint32)
-            geoms = np.empty((n, cap), np.int32)
-            self._check(self.lib.sg_road_info_points(self.h, n, scen.ctypes.data, xy.ctypes.data, cap, count.ctypes.data,
-                                                     geoms.ctypes.data if cap > 0 else None, layers.ctypes.data), "sg_road_info_points")
-            if n == 0 or int(count.max()) <= cap:
-                return count, geoms, layers
-            cap = int(count.max())
+
+        def call(cap, *ptrs):
+            self._check(self.lib.sg_road_info_points(self.h, len(xy), scen.ctypes.data, xy.ctypes.data, cap, *ptrs), "sg_road_info_points")
+
+        return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
         """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers -- observer k is entity slot
@@ -357,23 +393,13 @@ class RolloutEngine:
                                               slot.ctypes.data if len(scen) else None), "sg_set_observers")
         self._n_obs = len(scen)
 
-    def _obs_out(self, shape, torch_out):
-        if torch_out:
-            import torch
-
-            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.cfg.device}")
-            torch.cuda.current_stream(out.device).synchronize()  # (the allocator's work before the handle's stream writes)
-            return out, out.data_ptr() if out.numel() else None
-        out = np.empty(shape, np.uint8)
-        return out, out.ctypes.data if out.size else None
-
     def raster_map_observers(self, layers, width=20.0, height=20.0, nw=20, nh=20, torch_out=False):
         """RasterizedMapSensor._step (sensor/map.py:136-271) in the frame of every observer of set_observers
         (sg_raster_map_observers): bool [n, n_layers, nh, nw]; layers as in raster_map.  An observer that is not in the scene
         gets zeros.  torch_out: a torch uint8 tensor in HBM the kernel writes directly; this wrapper waits for the kernel
         (sg_synchronize) before it returns, so the tensor can be used on any torch stream -- the C call itself does not wait."""
         lay = np.ascontiguousarray(layers, np.int32)
-        out, ptr = self._obs_out((self._n_obs, len(lay), int(nh), int(nw)), torch_out)
+        (out,), (ptr,) = self._outputs(torch_out, ((self._n_obs, len(lay), int(nh), int(nw)), "uint8"))
         self._check(self.lib.sg_raster_map_observers(self.h, float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data,
                                                      ptr, int(bool(torch_out))), "sg_raster_map_observers")
         if torch_out:
@@ -385,7 +411,7 @@ class RolloutEngine:
         """FutureCollisionDetector._step (sensor/common.py:87-106) for every observer of set_observers at the current time of
         its scenario (sg_future_collision_observers): bool [n], or with torch_out a torch uint8 tensor in HBM (waited for, as
         in raster_map_observers)."""
-        out, ptr = self._obs_out((self._n_obs,), torch_out)
+        (out,), (ptr,) = self._outputs(torch_out, ((self._n_obs,), "uint8"))
         self._check(self.lib.sg_future_collision_observers(self.h, float(horizon), int(n_samples), ptr, int(bool(torch_out))),
                     "sg_future_collision_observers")
         if torch_out:
@@ -395,23 +421,11 @@ class RolloutEngine:
 
     def _nearest(self, call, n, k, radius, torch_out):
         k = int(k)
-        if torch_out:
-            import torch
-
-            dev = f"cuda:{self.cfg.device}"
-            feat = torch.empty((n, k, 8), dtype=torch.float64, device=dev)
-            slots = torch.empty((n, k), dtype=torch.int32, device=dev)
-            count = torch.empty((n,), dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(feat.device).synchronize()  # (the allocator's work before the handle's stream writes)
-            ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
-        else:
-            feat, slots, count = np.empty((n, k, 8), np.float64), np.empty((n, k), np.int32), np.empty(n, np.int32)
-            ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-        name = call.__name__
-        self._check(call(self.h, k, float(radius), ptr(feat), ptr(slots), ptr(count), int(bool(torch_out))), name)
+        outs, ptrs = self._outputs(torch_out, ((n, k, 8), "float64"), ((n, k), "int32"), ((n,), "int32"))
+        self._check(call(self.h, k, float(radius), *ptrs, int(bool(torch_out))), call.__name__)
         if torch_out:
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return feat, slots, count
+        return outs
 
     def nearest_entities(self, k, radius=float("inf"), torch_out=False):
         """The vector observation of the ego of every scenario (sg_nearest_entities): the k <= 32 nearest other entities that are
@@ -449,13 +463,7 @@ class RolloutEngine:
                                                   C.byref(ptr)), "sg_raster_map_device")
         self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
         if ent[2] != ptr.value:  # the scratch moved (first call, or it grew): wrap the new address once
-            import torch
-
-            class _Arr:
-                __cuda_array_interface__ = dict(shape=(self.R, len(lay), key[2], key[1]), typestr="|u1",
-                                                data=(int(ptr.value), False), version=2)
-
-            ent[2], ent[3] = ptr.value, torch.as_tensor(_Arr(), device=f"cuda:{self.cfg.device}")
+            ent[2], ent[3] = ptr.value, self._device_view(ptr.value, (self.R, len(lay), key[2], key[1]), "|u1")
         return ent[3]
 
     def tick(self, actions, layers, width=20.0, height=20.0, nw=20, nh=20, torch_out=False):
@@ -468,16 +476,7 @@ class RolloutEngine:
         if ent is None:
             ent = cache[key] = [np.ascontiguousarray(layers, np.int32), C.c_void_p(), C.c_void_p(), None, None, None]
         lay, d_obs, d_fl = ent[0], ent[1], ent[2]
-        ptr, on_device = None, 0
-        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
-            import torch
-
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == self.R * 2
-            torch.cuda.current_stream(actions.device).synchronize()
-            ptr, on_device = actions.data_ptr(), 1
-        elif actions is not None:
-            actions = np.ascontiguousarray(actions, np.float64).reshape(self.R, 2)
-            ptr = actions.ctypes.data
+        _keep, ptr, on_device = self._actions(actions, 1)
         self._check(self.lib.sg_tick(self.h, ptr, on_device, float(width), float(height), key[2], key[3], len(lay),
                                      lay.ctypes.data, C.byref(d_obs), C.byref(d_fl)), "sg_tick")
         self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
@@ -488,15 +487,8 @@ class RolloutEngine:
             self._check(self.lib.sg_copy_to_host(self.h, d_fl, fl.ctypes.data, fl.nbytes), "sg_copy_to_host")
             return obs.astype(bool), fl
         if ent[3] != (d_obs.value, d_fl.value):
-            import torch
-
-            def view(p, shp, typestr):
-                class _Arr:
-                    __cuda_array_interface__ = dict(shape=shp, typestr=typestr, data=(int(p), False), version=2)
-                return torch.as_tensor(_Arr(), device=f"cuda:{self.cfg.device}")
-
             ent[3] = (d_obs.value, d_fl.value)
-            ent[4], ent[5] = view(d_obs.value, shape, "|u1"), view(d_fl.value, (self.R,), "<i4")
+            ent[4], ent[5] = self._device_view(d_obs.value, shape, "|u1"), self._device_view(d_fl.value, (self.R,), "<i4")
         return ent[4], ent[5]
 
     def rollout(self, max_steps):
@@ -633,12 +625,6 @@ class RolloutEngine:
     def torch_state(self):
         """Zero-copy torch view [n_blocks, block_rows, 64] (fp64) over the device state blocks;
         field f of entity i is view[i // 64, f, i % 64].  torch is only the container."""
-        import torch
-
         v = self._view
+        return self._device_view(v.blocks, (v.n_blocks, v.block_rows, 64), "<f8")
 
-        class _Arr:
-            def __init__(self, ptr, shape, typestr):
-                self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(ptr), False), version=2)
-
-        return torch.as_tensor(_Arr(v.blocks, (v.n_blocks, v.block_rows, 64), "<f8"), device=f"cuda:{self.cfg.device}")

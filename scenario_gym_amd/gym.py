@@ -16,6 +16,7 @@ from .agent import CombinedSensor, FutureCollisionDetector, NearestEntitiesSenso
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_scenarios
+from .road_network import LAYER_CODES, shared_polygon_arrays
 from .scenario import Scenario
 from .state import State
 
@@ -302,34 +303,27 @@ class BatchedScenarioGym:
         terminal condition and the surface layers of the map sensor."""
         if self._roads_set:
             return
-        nets, index, net_of = [], {}, []
-        for sc in self.scenarios:
-            rn = sc.road_network
-            if rn is None:
-                net_of.append(-1)
-                continue
-            if id(rn) not in index:
-                index[id(rn)] = len(nets)
-                nets.append(rn.polygon_arrays())
-            net_of.append(index[id(rn)])
-        self.engine.set_road_networks(nets, net_of)
+        self.engine.set_road_networks(*shared_polygon_arrays(self.scenarios))
         self._roads_set = True
         # flags cached before the upload were computed without a road index (ego_off_road set for everybody): the answer must
         # not depend on which terminal condition was asked first
         if self._fut is not None:
             self._fut.pop(("term",), None)
 
-    def _raster_map(self, layers, width, height, nw, nh):
-        """[R][n_layers][nh][nw] of RasterizedMapSensor layers (names of sensor/map.py:44-53), cached per state."""
-        from .road_network import LAYER_CODES
-        codes = tuple(LAYER_CODES[l] for l in layers)
-        key = ("map", codes, width, height, nw, nh)
-        if self._fut is None or key not in self._fut:
-            if any(codes):
+    def _cached(self, key, compute, observers=False, roads=False, keep=None):
+        """The result `key` of the current state: compute() when it is first asked for, the same object until the next step.
+        roads: the road networks go down before it is computed; observers: so does the observer list, and the entry belongs to
+        that list (_observer drops it when the list grows); keep(value) False: computed again.  A dict that was self._fut
+        before is never changed: whoever holds one keeps what they saw."""
+        ent = (self._fut or {}).get(key)
+        if ent is None or (keep is not None and not keep(ent[0])):
+            if roads:
                 self._set_road_networks()
+            if observers:
+                self._send_observers()
             self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.raster_map(codes, width, height, nw, nh)
-        return self._fut[key]
+            ent = self._fut[key] = (compute(), observers)
+        return ent[0]
 
     def _observer(self, i: int, slot: int) -> int:
         """Position of entity `slot` of scenario `i` in the observer list; a new observer joins the list (and what was
@@ -339,7 +333,7 @@ class BatchedScenarioGym:
             k = self._observer_of[(i, slot)] = len(self._observers)
             self._observers.append((i, slot))
             if self._fut:
-                self._fut = {key: v for key, v in self._fut.items() if key[0] not in ("obs_map", "obs_fut", "obs_near")}
+                self._fut = {key: ent for key, ent in self._fut.items() if not ent[1]}
         return k
 
     def _send_observers(self):
@@ -348,54 +342,35 @@ class BatchedScenarioGym:
             self.engine.set_observers(scen, slot)
             self._observers_sent = len(self._observers)
 
-    def _raster_map_observers(self, layers, width, height, nw, nh):
-        """[n_observers][n_layers][nh][nw] of RasterizedMapSensor layers in the frame of every registered observer: one device
-        call per state and sensor configuration, cached like _raster_map."""
-        from .road_network import LAYER_CODES
+    # The sensor results of the current state, one device call per sensor configuration: a row per scenario for its ego, or with
+    # `observers` a row per registered observer (State._sensor_row picks the call and the row)
+    def _raster_map(self, observers: bool, layers, width, height, nw, nh):
+        """[n][n_layers][nh][nw] of RasterizedMapSensor layers (names of sensor/map.py:44-53)."""
         codes = tuple(LAYER_CODES[l] for l in layers)
-        key = ("obs_map", codes, width, height, nw, nh)
-        if self._fut is None or key not in self._fut:
-            if any(codes):
-                self._set_road_networks()
-            self._send_observers()
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.raster_map_observers(codes, width, height, nw, nh)
-        return self._fut[key]
+        call = self.engine.raster_map_observers if observers else self.engine.raster_map
+        return self._cached(("map", observers, codes, width, height, nw, nh), lambda: call(codes, width, height, nw, nh),
+                            observers=observers, roads=any(codes))
 
-    def _future_observers(self, horizon: float, n_samples: int):
-        key = ("obs_fut", horizon, n_samples)
-        if self._fut is None or key not in self._fut:
-            self._send_observers()
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.future_collision_observers(horizon, n_samples)
-        return self._fut[key]
+    def _future(self, observers: bool, horizon: float, n_samples: int):
+        call = self.engine.future_collision_observers if observers else self.engine.future_collision
+        return self._cached(("fut", observers, horizon, n_samples), lambda: call(horizon, n_samples), observers=observers)
 
-    def _nearest_observers(self, k: int, radius: float):
-        """(feat [n_observers, k, 8], slots [n_observers, k], count [n_observers]) of NearestEntitiesSensor for every registered
-        observer: one device call per state and sensor configuration, cached like _raster_map_observers."""
-        key = ("obs_near", k, radius)
-        if self._fut is None or key not in self._fut:
-            self._send_observers()
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.nearest_entities_observers(k, radius)
-        return self._fut[key]
+    def _nearest(self, observers: bool, k: int, radius: float):
+        """(feat [n, k, 8], slots [n, k], count [n]) of NearestEntitiesSensor."""
+        call = self.engine.nearest_entities_observers if observers else self.engine.nearest_entities
+        return self._cached(("near", observers, k, radius), lambda: call(k, radius), observers=observers)
 
-    def _nearest(self, k: int, radius: float):
-        """The same for the ego of every scenario ([R, ...]), cached per state."""
-        key = ("near", k, radius)
-        if self._fut is None or key not in self._fut:
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.nearest_entities(k, radius)
-        return self._fut[key]
+    def _raster(self, width, height, nw, nh):
+        return self._cached(("raster", width, height, nw, nh), lambda: self.engine.raster_entities(width, height, nw, nh))
+
+    def _terminal_flags(self):
+        """SG_TERM_* bits of every scenario's current state (all four conditions)."""
+        return self._cached(("term",), self.engine.terminal_flags)
 
     def _road_info(self, cap: int = 32):
-        """(count [R, E], geoms [R, E, >= cap], layers [R, E]) of engine.road_info for the current state, cached per state."""
-        key = ("road_info",)
-        if self._fut is None or key not in self._fut or self._fut[key][1].shape[2] < cap:
-            self._set_road_networks()
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.road_info(cap)
-        return self._fut[key]
+        """(count [R, E], geoms [R, E, >= cap], layers [R, E]) of engine.road_info for the current state; a result narrower
+        than `cap` is computed again."""
+        return self._cached(("road_info",), lambda: self.engine.road_info(cap), roads=True, keep=lambda v: v[1].shape[2] >= cap)
 
     def road_info(self, cap: int = 32):
         """State.get_road_info_at_entity for the whole batch: count [R, E] (-1: the entity is not in the scene), geoms
@@ -433,28 +408,6 @@ class BatchedScenarioGym:
         if self._cache is None:
             self._cache = self.engine.state()
         return self._cache
-
-    def _terminal_flags(self):
-        """SG_TERM_* bits of every scenario's current state (all four conditions), cached per state."""
-        key = ("term",)
-        if self._fut is None or key not in self._fut:
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.terminal_flags()
-        return self._fut[key]
-
-    def _future(self, horizon: float, n_samples: int):
-        key = (horizon, n_samples)
-        if self._fut is None or key not in self._fut:
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.future_collision(horizon, n_samples)
-        return self._fut[key]
-
-    def _raster(self, width, height, nw, nh):
-        key = ("raster", width, height, nw, nh)
-        if self._fut is None or key not in self._fut:
-            self._fut = dict(self._fut or {})
-            self._fut[key] = self.engine.raster_entities(width, height, nw, nh)
-        return self._fut[key]
 
     def _fetch_record(self):
         if not self.record:

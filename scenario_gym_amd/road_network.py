@@ -35,6 +35,19 @@ LAYER_CODES = {"entity": 0, "driveable_surface": LAYER_DRIVEABLE, "road": LAYER_
                "lane": LAYER_LANE, "walkable_surface": LAYER_WALKABLE, "pavement": LAYER_PAVEMENT, "crossing": LAYER_CROSSING}
 
 
+def shared_polygon_arrays(scenarios):
+    """The arguments of RolloutEngine.set_road_networks for `scenarios`: (polygon_arrays() of every distinct road network -- one
+    that several scenarios share, by object identity, once --, per scenario its index into that list, -1 for none)."""
+    nets, index, net_of = [], {}, []
+    for sc in scenarios:
+        rn = sc.road_network
+        if rn is not None and id(rn) not in index:
+            index[id(rn)] = len(nets)
+            nets.append(rn.polygon_arrays())
+        net_of.append(-1 if rn is None else index[id(rn)])
+    return nets, net_of
+
+
 def _ring(points) -> np.ndarray:
     r = np.array([[float(v["x"]), float(v["y"])] for v in points], np.float64).reshape(-1, 2)
     if len(r) > 1 and (r[0] == r[-1]).all():  # shapely closes rings itself; the device wants them open

@@ -178,19 +178,18 @@ class State:
     def get_entity_box_points(self, e: Entity) -> np.ndarray:
         return e.get_bounding_box_points(self.poses[e])
 
-    def _observer(self, entity: Optional[Entity]) -> Optional[int]:
-        """None for the ego (the per-scenario device calls answer), else the entity's place in the gym's observer list."""
+    def _sensor_row(self, entity: Optional[Entity]):
+        """(observers, row) of the gym's sensor results for `entity`: the per-scenario calls and this scenario's row for the
+        ego, else the observer-list calls and the entity's place in the gym's observer list."""
         if entity is None or entity is self._scenario.ego:
-            return None
-        return self._gym._observer(self._i, self._scenario.entities.index(entity))
+            return False, self._i
+        return True, self._gym._observer(self._i, self._scenario.entities.index(entity))
 
     def future_collision(self, horizon: float = 5.0, n_samples: int = 10, entity: Optional[Entity] = None) -> bool:
         """FutureCollisionDetector(entity, horizon) at the current time (sensor/common.py:87-106), computed on the device;
         entity: any entity of the scenario (default: the ego)."""
-        k = self._observer(entity)
-        if k is not None:
-            return bool(self._gym._future_observers(float(horizon), int(n_samples))[k])
-        return bool(self._gym._future(float(horizon), int(n_samples))[self._i])
+        observers, row = self._sensor_row(entity)
+        return bool(self._gym._future(observers, float(horizon), int(n_samples))[row])
 
     def entity_raster(self, width: float = 20.0, height: float = 20.0, nw: int = 20, nh: int = 20) -> np.ndarray:
         """RasterizedMapSensor "entity" layer around the ego (sensor/map.py:120-192), computed on the device: bool [nh, nw]."""
@@ -201,24 +200,18 @@ class State:
         """RasterizedMapSensor layers around `entity` -- any entity of the scenario, default the ego (sensor/map.py:136-271;
         names of its `_all_layers`) -- computed on the device from the scenario's road network: bool [n_layers, nh, nw]; all
         False for an entity that is not in `poses`."""
-        k = self._observer(entity)
-        if k is not None:
-            return self._gym._raster_map_observers(tuple(layers), float(width), float(height), int(nw), int(nh))[k]
-        return self._gym._raster_map(tuple(layers), float(width), float(height), int(nw), int(nh))[self._i]
+        observers, row = self._sensor_row(entity)
+        return self._gym._raster_map(observers, tuple(layers), float(width), float(height), int(nw), int(nh))[row]
 
     def nearest_entities(self, k: int = 8, radius: float = float("inf"), entity: Optional[Entity] = None):
         """NearestEntitiesSensor(entity, k, radius) at the current state, computed on the device: (neighbours, features) -- the
         at most k nearest other entities in `poses` within `radius` of `entity` (any entity of the scenario, default the ego)
         by ascending (squared distance, position in the scenario), and their [k, 8] feature rows in the entity's frame (zeros
         behind the last).  ([], zeros) for an entity that is not in `poses`."""
-        o = self._observer(entity)
-        if o is not None:
-            feat, slots, _ = self._gym._nearest_observers(int(k), float(radius))
-        else:
-            feat, slots, _ = self._gym._nearest(int(k), float(radius))
-            o = self._i
+        observers, row = self._sensor_row(entity)
+        feat, slots, _ = self._gym._nearest(observers, int(k), float(radius))
         ents = self._scenario.entities
-        return [ents[j] for j in slots[o] if j >= 0], feat[o].copy()
+        return [ents[j] for j in slots[row] if j >= 0], feat[row].copy()
 
     def get_road_info_at_entity(self, e: Entity):
         """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's

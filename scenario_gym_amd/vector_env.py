@@ -16,9 +16,9 @@ import numpy as np
 
 from . import _lib as L
 from .agent import ExternalVehicleAgent
-from .engine import RolloutEngine
+from .engine import RolloutEngine, terminal_mask
 from .packing import pack_scenarios
-from .road_network import LAYER_CODES
+from .road_network import LAYER_CODES, shared_polygon_arrays
 from .scenario import Scenario
 
 
@@ -45,18 +45,8 @@ class VectorScenarioEnv:
         self.engine = RolloutEngine(packed.n_scenarios, packed.n_entities, timestep=timestep,
                                     terminal_conditions=self.terminal_conditions, device=device)
         self.engine.upload(packed)
-        nets, index, net_of = [], {}, []
-        for sc in self.scenarios:  # shared road networks go down once
-            rn = sc.road_network
-            if rn is not None and id(rn) not in index:
-                index[id(rn)] = len(nets)
-                nets.append(rn.polygon_arrays())
-            net_of.append(-1 if rn is None else index[id(rn)])
-        self.engine.set_road_networks(nets, net_of)
-        self._mask = 0
-        for c in self.terminal_conditions:
-            self._mask |= {"max_length": L.TERM_MAX_LENGTH, "collision": L.TERM_COLLISION,
-                           "ego_collision": L.TERM_EGO_COLLISION, "ego_off_road": L.TERM_EGO_OFF_ROAD}[c]
+        self.engine.set_road_networks(*shared_polygon_arrays(self.scenarios))
+        self._mask = terminal_mask(self.terminal_conditions)
         self.done = np.zeros(self.n_envs, bool)
         self._obs_env, self._obs_slot = np.zeros(0, np.int32), np.zeros(0, np.int32)  # set_observers
 
@@ -122,17 +112,20 @@ class VectorScenarioEnv:
         self.engine.set_observers(env, slot)
         self._obs_env, self._obs_slot = np.array(env, np.int32), np.array(slot, np.int32)
 
+    def _observer_index(self, like):
+        """(env_of_observer [n], slot [n]) of the observers set: numpy arrays, or with torch_obs tensors beside `like`."""
+        if self.torch_obs:
+            import torch
+
+            return torch.as_tensor(self._obs_env, device=like.device), torch.as_tensor(self._obs_slot, device=like.device)
+        return self._obs_env, self._obs_slot
+
     def observe_entities(self):
         """The map observation of every observer of set_observers at the current state, with the environment's layers and
         geometry (sg_raster_map_observers): (obs [n, n_layers, n_px, n_px], env_of_observer [n], slot [n]).  torch_obs: torch
         tensors in HBM; else numpy arrays (obs bool)."""
-        env, slot = self._obs_env, self._obs_slot
         obs = self.engine.raster_map_observers(self._codes, self.width, self.height, self.n, self.n, torch_out=self.torch_obs)
-        if self.torch_obs:
-            import torch
-
-            return obs, torch.as_tensor(env, device=obs.device), torch.as_tensor(slot, device=obs.device)
-        return obs, env, slot
+        return (obs,) + self._observer_index(obs)
 
     def nearest_entities(self, k: int = 8, radius: float = float("inf")):
         """The vector observation of the ego of every environment at the current state (sg_nearest_entities): (feat [R, k, 8],
@@ -143,13 +136,8 @@ class VectorScenarioEnv:
         """The vector observation of every observer of set_observers at the current state (sg_nearest_entities_observers):
         (feat [n, k, 8], slots [n, k], count [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy
         arrays."""
-        env, slot = self._obs_env, self._obs_slot
-        feat, slots, count = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
-        if self.torch_obs:
-            import torch
-
-            return feat, slots, count, torch.as_tensor(env, device=feat.device), torch.as_tensor(slot, device=feat.device)
-        return feat, slots, count, env, slot
+        out = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
 
     def close(self):
         self.engine.close()
