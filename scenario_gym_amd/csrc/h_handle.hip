@@ -92,6 +92,7 @@ extern "C" int sg_create(const sg_config *cfg, sg_handle **out)
     h->crowd_models = env_int("SG_CROWD_MODELS", 1) != 0; // (0: batches with several pedestrian models keep to the general variant; the tests compare)
     h->slice_mode = env_int("SG_SLICE", 1);
     h->queue_mode = env_int("SG_QUEUE", 1);
+    h->quiet = env_int("SG_QUIET", 1) != 0;
     // the controller stream carries the serial chain of the table path (control_kernel_fast: 64 wavefronts that every rollout
     // launch waits for): highest stream priority, so that its launches are dispatched ahead of the rollout kernels'
     // (measured: no difference at 4096 x 64, where the launches never queue; SG_CTL_PRIO=0 creates it at the lowest)

@@ -125,7 +125,7 @@ static int launch_queue(sg_handle *h, int n_steps, int force, const double *d_ac
     }
     h->p.tab_steps = ts;
     const bool q_trace = env_int("SG_QUEUE_DEBUG", 0) != 0;
-    const size_t words = (size_t)sg::Q_STATE_WORDS + n_ctl_waves + nblk + (size_t)sg::Q_MAX_CHUNKS + 1 + (size_t)sg::Q_SEATS + (q_trace ? nblk : 0);
+    const size_t words = (size_t)sg::Q_PROG_STRIDE * (1 + n_ctl_waves) + nblk + (size_t)sg::Q_MAX_CHUNKS + 1 + (size_t)sg::Q_SEATS + (q_trace ? nblk : 0);
     if (words * sizeof(unsigned) > h->qwords.cap) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (const int rcw = h->qwords.ensure(h, words * sizeof(unsigned))) return rcw;
@@ -140,8 +140,9 @@ static int launch_queue(sg_handle *h, int n_steps, int force, const double *d_ac
     HIP_TRY(h, hipMemsetAsync(d_qwords, 0, words * sizeof(unsigned), h->stream)); // every polled word, before every launch
     sg::TabQueue tq{};
     tq.state = d_qwords;
-    tq.ctl_prog = tq.state + sg::Q_STATE_WORDS;
-    tq.blk_prog = tq.ctl_prog + n_ctl_waves;
+    static_assert(sg::Q_STATE_WORDS <= sg::Q_PROG_STRIDE, "the state words have the first line to themselves");
+    tq.ctl_prog = tq.state + sg::Q_PROG_STRIDE; // (one word per line, see Q_PROG_STRIDE)
+    tq.blk_prog = tq.ctl_prog + (size_t)sg::Q_PROG_STRIDE * n_ctl_waves;
     tq.chunk_cnt = tq.blk_prog + nblk;
     tq.seats = tq.chunk_cnt + sg::Q_MAX_CHUNKS + 1;
     tq.trace = q_trace ? tq.seats + sg::Q_SEATS : nullptr;
@@ -153,6 +154,7 @@ static int launch_queue(sg_handle *h, int n_steps, int force, const double *d_ac
     if (const int us = env_int("SG_QUEUE_TIMEOUT_US", 0)) tq.timeout_ticks = (long long)std::max(1, us) * 100ll; // (tests: a give-up on demand)
     tq.handoff = env_int("SG_QUEUE_HANDOFF", 1) != 0; // 0: a release fence per item instead (correct as well, 60 G on c3)
     tq.lag_prio = env_int("SG_QUEUE_LAGPRIO", 2);
+    tq.nap = std::max(1, std::min(64, env_int("SG_QUEUE_NAP", 4))); // x 3.4 us: the longest nap between two polls of a waiting wavefront
     const char *times_path = getenv("SG_QUEUE_TIMES"); // experiment: per-item time stamps, dumped as u64 after the launch
     static unsigned long long *d_times = nullptr;
     static size_t times_cap = 0;
@@ -212,7 +214,10 @@ static int launch_queue(sg_handle *h, int n_steps, int force, const double *d_ac
         const auto t_start = std::chrono::steady_clock::now();
         for (int i = 0; i < dbg; ++i) {
             std::this_thread::sleep_for(std::chrono::microseconds(us));
-            if (hipMemcpyAsync(w, d_qwords, (sg::Q_STATE_WORDS + 4) * sizeof(unsigned), hipMemcpyDeviceToHost, ws) != hipSuccess || hipStreamSynchronize(ws) != hipSuccess) break;
+            if (hipMemcpyAsync(w, d_qwords, sg::Q_STATE_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, ws) != hipSuccess ||
+                hipMemcpy2DAsync(w + sg::Q_STATE_WORDS, sizeof(unsigned), tq.ctl_prog, sg::Q_PROG_STRIDE * sizeof(unsigned), sizeof(unsigned),
+                                 std::min<size_t>(4, n_ctl_waves), hipMemcpyDeviceToHost, ws) != hipSuccess ||
+                hipStreamSynchronize(ws) != hipSuccess) break;
             fprintf(stderr, "queue +%.2f ms: tickets %u head %u err %u items done %u | ctl_prog %u %u %u %u",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), w[0], w[1], w[2], w[3], w[8], w[9], w[10], w[11]);
             unsigned *tr = w + sg::Q_STATE_WORDS + 8;

@@ -478,6 +478,7 @@ int Upload::static_arrays()
     apply_noise(h);
     p.ped_serial = h->ped_serial;
     p.ctl_general = env_int("SG_CTL_FAST", 1) == 0;
+    p.quiet = h->quiet;
     p.reset_mask = h->d_reset_mask;
     p.persist = h->cfg.persist;
     p.term_mask = h->cfg.terminal_mask;

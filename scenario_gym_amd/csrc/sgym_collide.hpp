@@ -24,11 +24,78 @@ namespace sg {
 // reaches own radius + the LARGEST radius of the tile, which for a pedestrian next to a car's tile-mate means every
 // pedestrian within ~3 m; `hetero` (static per tile, voted at launch) then runs one cheap circle test with the PAIR's radii
 // over the candidates before the filter.  Conservative like the broad phase itself, so it cannot change any output.
+// The prelude of the pass, per lane and without a word of LDS: the fp32 box centre, its reach and its stripe cell.  The step
+// loop of the QUIET variants (sgym_rollout.hpp) forms it, asks ego_near() and runs the rest of the pass only if it has to.
+struct TileCentre {
+    float fs, fc;      // hardware sin / cos of the heading
+    float fx, fy;      // box centre (NaN: absent)
+    float mag;         // |fx| + |fy|: the fp32 conversion error of the centre grows with it
+    float reach, thr;  // broad-phase reach of this lane and its square
+    float nthr;        // (PED) the same for PedestrianSensor.distance_threshold
+    int ix, iy;        // stripe cell
+    bool far_out;      // beyond 4000 cells: the tile walks all pairs
+};
+
+__device__ __forceinline__ TileCentre tile_centre(bool present, const double *pose, double bcx, double bcy, float rad_thr,
+                                                  float nbr_thr, float cell_inv)
+{
+    TileCentre C;
+    const double x = pose[0], y = pose[1];
+    // box centre in fp32 from the hardware sin/cos; the bounding circle radius and every error margin
+    // (fp32 rounding, SG_TRIG32_ERR x centre offset) live in rad_thr (static per lane)
+    sg_sincos_f32(pose[3], C.fs, C.fc);
+    const float bcxf = (float)bcx, bcyf = (float)bcy;
+    const float nanf_ = __builtin_nanf("");
+    C.fx = present ? (float)x + (bcxf * C.fc - bcyf * C.fs) : nanf_;
+    C.fy = present ? (float)y + (bcxf * C.fs + bcyf * C.fc) : nanf_;
+    // fp32 conversion error of the centre grows with |coordinate|: 2^-19 * (|x| + |y|) covers both lanes
+    C.mag = __builtin_fabsf(C.fx) + __builtin_fabsf(C.fy);
+    C.reach = rad_thr + 1.9073486e-6f * C.mag;
+    C.thr = C.reach * C.reach;
+    const float nreach = nbr_thr + 1.9073486e-6f * C.mag;
+    C.nthr = nreach * nreach;
+    // stripe coordinates: cells of side 1/cell_inv >= every reach in the tile, so two slots within reach
+    // of each other sit in the same or in adjacent x-stripes AND y-stripes
+    const float ax = C.fx * cell_inv, ay = C.fy * cell_inv;
+    C.ix = present ? (int)__builtin_floorf(ax) : 0;
+    C.iy = present ? (int)__builtin_floorf(ay) : 0;
+    C.far_out = present && !(__builtin_fabsf(ax) < 4000.0f && __builtin_fabsf(ay) < 4000.0f);
+    return C;
+}
+
+// Is some other body of the tile within the broad-phase reach of the tile's ego?  (per lane: this lane is; one wavefront per
+// tile, `ego_lane` = the LDS slot of the ego of this lane's tile)
+//
+// Why an empty vote over the tile means that the rest of the pass would leave the ego lane's row 0: both broad phases build
+// the EGO LANE's candidate set from this very predicate on these very floats -- the stripe path keeps cell neighbour j when
+// fmaf(dy, dy, dx * dx) <= thr with dx = cen_j.x - fx, dy = cen_j.y - fy and the lane's own thr (the circle loop below), the
+// all-pairs walk keeps slot j when thr - d2 has no sign bit, which for these operands is d2 <= thr, and then drops absent
+// slots.  REFINE only removes candidates.  With no candidate the ego lane has no certain pair, no fuzzy pair (so no twin and no
+// owner mapping of ITS row; it still takes part in the other lanes' exact path) and mult_rows == rows_out == 0.  An absent
+// lane holds NaN centres and fails the compare; an absent ego makes every compare fail, and an absent lane's row is 0 anyway.
+template <int G>
+__device__ __forceinline__ bool ego_near(const TileCentre &C, bool present, bool is_ego, int ego_lane)
+{
+    float ex, ey, et;
+    if (G == 64) { // (wave-uniform lane: three v_readlane)
+        ex = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(C.fx), ego_lane));
+        ey = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(C.fy), ego_lane));
+        et = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(C.thr), ego_lane));
+    } else {
+        ex = __shfl(C.fx, ego_lane, 64);
+        ey = __shfl(C.fy, ego_lane, 64);
+        et = __shfl(C.thr, ego_lane, 64);
+    }
+    const float dx = C.fx - ex, dy = C.fy - ey;
+    const float d2 = __builtin_fmaf(dy, dy, dx * dx);
+    return present && !is_ego && d2 <= et;
+}
+
 template <int G, int WV, bool PED, bool CROWD = false, bool REFINE = false, typename LDS>
-__device__ __forceinline__ void tile_collisions(bool present, const double *pose, double velx, double vely,
+__device__ __forceinline__ void tile_collisions_from(const TileCentre &C, bool present, const double *pose, double velx, double vely,
                                                 double dtn /* next_t - t of the coming step (PED) */,
-                                                double bcx, double bcy, float rad_thr, float trig_eps,
-                                                float nbr_thr, float cell_inv, bool is_ped_type, int sl, int tile0, LDS &L,
+                                                double bcx, double bcy, float trig_eps,
+                                                bool is_ped_type, int sl, int tile0, LDS &L,
                                                 uint64_t (&rows_out)[WV], uint64_t (&mult_rows)[WV],
                                                 uint64_t (&nbr_out)[WV], bool &dense /* in: this lane's wish from the previous call,
                                                 out: its wish for the next one; see all_pairs */, bool *crowd_ok = nullptr,
@@ -41,25 +108,9 @@ __device__ __forceinline__ void tile_collisions(bool present, const double *pose
     constexpr int TS = G * WV; // tile slots
     const int slot = sl - tile0;
     const double x = pose[0], y = pose[1];
-    // box centre in fp32 from the hardware sin/cos; the bounding circle radius and every error margin
-    // (fp32 rounding, SG_TRIG32_ERR x centre offset) live in rad_thr (static per lane)
-    float fs, fc;
-    sg_sincos_f32(pose[3], fs, fc);
-    const float bcxf = (float)bcx, bcyf = (float)bcy;
-    const float nanf_ = __builtin_nanf("");
-    const float fx = present ? (float)x + (bcxf * fc - bcyf * fs) : nanf_;
-    const float fy = present ? (float)y + (bcxf * fs + bcyf * fc) : nanf_;
-    // fp32 conversion error of the centre grows with |coordinate|: 2^-19 * (|x| + |y|) covers both lanes
-    const float mag = __builtin_fabsf(fx) + __builtin_fabsf(fy);
-    const float reach = rad_thr + 1.9073486e-6f * mag;
-    const float thr = reach * reach;
-    const float nreach = nbr_thr + 1.9073486e-6f * mag;
-    const float nthr = nreach * nreach;
-    // stripe coordinates: cells of side 1/cell_inv >= every reach in the tile, so two slots within reach
-    // of each other sit in the same or in adjacent x-stripes AND y-stripes
-    const float ax = fx * cell_inv, ay = fy * cell_inv;
-    const int ix = present ? (int)__builtin_floorf(ax) : 0, iy = present ? (int)__builtin_floorf(ay) : 0;
-    const bool far_out = present && !(__builtin_fabsf(ax) < 4000.0f && __builtin_fabsf(ay) < 4000.0f);
+    const float fs = C.fs, fc = C.fc, fx = C.fx, fy = C.fy, mag = C.mag, reach = C.reach, thr = C.thr, nthr = C.nthr;
+    const int ix = C.ix, iy = C.iy;
+    const bool far_out = C.far_out;
     PH(8); tile_sync<WV>(); PH(11);
     L.cx[sl] = fx;
     L.cy[sl] = fy;
@@ -412,6 +463,19 @@ __device__ __forceinline__ void tile_collisions(bool present, const double *pose
         for (int w = 0; w < WV; ++w) rows_out[w] = nr[w];
     }
     PH(4);
+}
+
+// the whole pass
+template <int G, int WV, bool PED, bool CROWD = false, bool REFINE = false, typename LDS>
+__device__ __forceinline__ void tile_collisions(bool present, const double *pose, double velx, double vely, double dtn, double bcx,
+                                                double bcy, float rad_thr, float trig_eps, float nbr_thr, float cell_inv,
+                                                bool is_ped_type, int sl, int tile0, LDS &L, uint64_t (&rows_out)[WV],
+                                                uint64_t (&mult_rows)[WV], uint64_t (&nbr_out)[WV], bool &dense, bool *crowd_ok = nullptr,
+                                                PhaseTimers *ptp = nullptr, bool hetero = false, float rmax_t = 0.0f)
+{
+    const TileCentre C = tile_centre(present, pose, bcx, bcy, rad_thr, nbr_thr, cell_inv);
+    tile_collisions_from<G, WV, PED, CROWD, REFINE>(C, present, pose, velx, vely, dtn, bcx, bcy, trig_eps, is_ped_type, sl, tile0, L,
+                                                    rows_out, mult_rows, nbr_out, dense, crowd_ok, ptp, hetero, rmax_t);
 }
 
 } // namespace sg

@@ -83,6 +83,7 @@ struct Params {
     const RoadIndex *road;   // device copy of the road index, nullptr = no road networks set
     int ctl_general;         // 1: control_kernel without its straight-line fast path (env SG_CTL_FAST=0; the tests compare the two)
     int ped_serial;          // 1: pedestrian pair loop one pedestrian per lane (env SG_PED_SERIAL; default 0: balanced over the wavefront)
+    int quiet;               // 1: the QUIET rollout variants skip the collision pass in steps nobody can see (env SG_QUIET, default 1; 0: every step runs it)
     int tab_steps;           // steps per table chunk (rows per lane = tab_steps + 1: the prefetch of the last step reads one row ahead)
     // random fluctuations of the social force (sg_set_ped_noise): 0 off, 1 stream of standard normal variates per scenario,
     // 2 counter-based generator

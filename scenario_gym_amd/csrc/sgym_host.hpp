@@ -69,6 +69,7 @@ struct sg_handle {
     int n_simd = 1024;                                       // SIMDs of the device (4 per compute unit)
     int tab_min = 16, chunk_steps = 1024, overlap = 1; // sg_set_tuning
     int slice_mode = 1;       // sg_set_tuning / env SG_SLICE: 0 never, 1 automatic (small batches, long rollouts)
+    bool quiet = true;              // env SG_QUIET=0: every step of the table rollout kernels runs the whole collision pass (Params::quiet)
     int queue_mode = 1;             // env SG_QUEUE=0: the chunk launches of rounds 1-4 instead
     int ctl_slice = 64;                                // steps per control_kernel launch (env SG_CTL_SLICE)
     int ped_serial = 0;                                // env SG_PED_SERIAL: pedestrian pair loop one pedestrian per lane
@@ -127,7 +128,8 @@ struct sg_handle {
     std::vector<int> launch_ev;   // their (start, stop) event indices into ev_pool
 
     // ---- h_queue.hip: the table path as one persistent launch (sgym_queue.hpp, launch_queue), and as chunk launches ----
-    sgh::GrowBuf qwords{sgh::GrowBuf::DEVICE}; // queue state + progress words: [Q_STATE_WORDS + n_ctl_waves + nblk + Q_MAX_CHUNKS] unsigned
+    sgh::GrowBuf qwords{sgh::GrowBuf::DEVICE}; // queue state + progress words, unsigned: [Q_PROG_STRIDE] the state words on a line of their own, [n_ctl_waves * Q_PROG_STRIDE] one
+                                               // pre-pass progress word per 128-byte line, [nblk] block progress, [Q_MAX_CHUNKS + 1] chunk counters, [Q_SEATS] (+ [nblk] trace)
     double *d_qtab = nullptr;       // the table ring
     size_t qtab_bytes = 0;
     int q_waves_per_cu[3] = {-1, -1, -1}; // occupancy of rollout_kernel_tabq / _planar / _rss_tabq (slots_of), queried once per G

@@ -27,10 +27,14 @@ enum { Q_TICKET = 0, Q_HEAD = 1, Q_ERR = 2, Q_ITEMS_DONE = 3, Q_CTL_CLAIMED = 4,
 constexpr int Q_SEATS = 1 << 14; // one word per SIMD of the device, indexed by (XCC, SE, SH, CU, SIMD) as the hardware reports them
 enum { Q_ERR_CTL_WAIT = 1, Q_ERR_BLOCK_WAIT = 2, Q_ERR_RING_WAIT = 3 };
 constexpr int Q_MAX_CHUNKS = 255;
+// the words the pre-pass publishes lie a cache line apart, on lines of their own: the rollout wavefronts that wait for a chunk poll
+// them past the L2, and side by side (and beside the item counter, which every pull hits with an atomic) two lines and one
+// memory channel took every poll of the launch
+constexpr int Q_PROG_STRIDE = 32;
 
 struct TabQueue {
     unsigned *state;      // [Q_STATE_WORDS] role tickets, item counter, give-up code, items finished -- zeroed before every launch
-    unsigned *ctl_prog;   // [n_ctl_waves] chunks pre-pass wavefront w has published
+    unsigned *ctl_prog;   // [n_ctl_waves * Q_PROG_STRIDE] chunks pre-pass wavefront w has published, at word w * Q_PROG_STRIDE
     unsigned *blk_prog;   // [nblk] chunks block b has finished
     unsigned *chunk_cnt;  // [n_chunks] blocks that have finished chunk c (the pre-pass waits on it before it reuses a ring buffer)
     unsigned *seats;      // [Q_SEATS] wavefronts of this launch that have arrived on SIMD s (role election)
@@ -43,6 +47,7 @@ struct TabQueue {
                                // wavefront w after chunk c at [n_items * 4 + w * n_chunks + c] (nullptr: not recorded)
     long long timeout_ticks; // of the 100 MHz wall clock
     int n_chunks, n_buf, nblk, n_ctl_waves;
+    int nap;              // the longest nap of a waiting wavefront between two polls, in units of ~3.4 us (s_sleep 127)
     int lag_prio;         // items of blocks that are behind run at a raised priority: 0 no, 1 s_setprio 1, 2 s_setprio 2 (c3: 88.5 ->
                           // 92.5 / 93.0 G, means of six interleaved runs each, profiles/r05_ab_lagprio.txt)
     int handoff;          // how a rollout item hands its block on: 0 = release fence (buffer_wbl2: the whole L2 of the XCD is written
@@ -65,11 +70,19 @@ __device__ __forceinline__ bool q_wait_ge(const unsigned *w, unsigned want, cons
     if (q_peek(w) >= want) return true;
     const long long t0 = wall_clock64();
     for (int spin = 0;; ++spin) {
-        // (a few quick looks, then ~3 us naps: thousands of wavefronts poll the same few words while the pre-pass writes its
-        // first chunk, and every poll is an L2 request on the pre-pass's path)
-        if (spin < 4) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(112);
+        // A few quick looks, then ~3 us naps, then naps that double up to tq.nap x 3.4 us -- small against a chunk of the pre-pass
+        // (0.2 - 1 ms), which is what a wait of that length is for.  Every poll is a request past the L2 to the channel of the
+        // polled line; when the rollout role outruns the pre-pass, thousands of wavefronts wait in every chunk, and at one poll
+        // per 3 us each they slowed the very chain they were waiting for (profiles/quiet_steps.txt).  The give-up word is
+        // looked at every eighth poll: it only has to be seen eventually.  The wall-clock bound holds at every poll.
+        if (spin < 4) __builtin_amdgcn_s_sleep(16);
+        else if (spin < 12) __builtin_amdgcn_s_sleep(112);
+        else {
+            const int n = min(tq.nap, 1 << min((spin - 12) >> 2, 6)); // (wave-uniform)
+            for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
+        }
         if (q_peek(w) >= want) return true;
-        if (q_peek(tq.state + Q_ERR) != 0) return false;
+        if ((spin & 7) == 7 && q_peek(tq.state + Q_ERR) != 0) return false;
         if (wall_clock64() - t0 > tq.timeout_ticks) {
             if (threadIdx.x == 0) atomicCAS(tq.state + Q_ERR, 0u, code);
             return false;
@@ -180,7 +193,7 @@ __device__ __forceinline__ void tabq_body(const Params &p, double timestep, int 
                                  tq.tab + (size_t)(c % tq.n_buf) * tq.buf_doubles, 0, RSS ? 0 : 1);
             q_release();
             if (tq.times && lane == 0) tq.times[(size_t)tq.n_chunks * tq.nblk * 4 + (size_t)ticket * tq.n_chunks + c] = wall_clock64();
-            if (lane == 0) __hip_atomic_store(tq.ctl_prog + ticket, (unsigned)(c + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_store(tq.ctl_prog + ticket * Q_PROG_STRIDE, (unsigned)(c + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // the chain is written: this wavefront rolls out like the others from here on (its slot would idle for the second half
         // of the call otherwise).  (Measured and dropped, round 5: rollout wavefronts that leave their SIMD to the pre-pass
@@ -219,13 +232,10 @@ __device__ __forceinline__ void tabq_body(const Params &p, double timestep, int 
         // A block whose previous chunk is not finished when its next one is pulled is behind the others: the call ends with
         // the slowest chain of items (tools/dbg/queue_timeline.py: the slowest block's items add up to 24.9 of the call's 27.1 ms),
         // so its item runs first in line at its SIMD's issue port (tq.lag_prio).
+        // (whoever waits, waits at priority 0: the raised priority of the previous item is not this item's)
+        if (tq.lag_prio) __builtin_amdgcn_s_setprio(0);
         const bool behind = c != 0 && q_peek(tq.blk_prog + b) < c;
         bool ok = c == 0 || q_wait_ge(tq.blk_prog + b, c, tq, Q_ERR_BLOCK_WAIT);
-        if (tq.lag_prio) {
-            if (!behind) __builtin_amdgcn_s_setprio(0);
-            else if (tq.lag_prio == 1) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(2);
-        }
         {   // the pre-pass wavefronts that integrate this block's controlled lanes
             const LanePtr st(p.stat + (size_t)b * (ST_COUNT * 64), (uint32_t)lane * 8u);
             const int64_t cq = fld<int64_t>(st, ST_CTL);
@@ -234,10 +244,14 @@ __device__ __forceinline__ void tabq_body(const Params &p, double timestep, int 
                 const int l = __builtin_ctzll(m);
                 m &= m - 1;
                 const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)(uint32_t)cq, l) >> 6;
-                ok = q_wait_ge(tq.ctl_prog + w, c + 1, tq, Q_ERR_CTL_WAIT);
+                ok = q_wait_ge(tq.ctl_prog + w * Q_PROG_STRIDE, c + 1, tq, Q_ERR_CTL_WAIT);
             }
         }
         if (!ok) break; // (somebody gave up: the host reports it)
+        if (tq.lag_prio && behind) { // (set behind the waits: a wavefront that sleeps on a flag has no use for the issue port)
+            if (tq.lag_prio == 1) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(2);
+        }
         trace(2);
         q_acquire();
         trace(3);

@@ -99,6 +99,11 @@ struct Variant {
     // accumulators wait in the lane's column of lds.ctrl -- a table variant has no controller parameters there -- between their
     // uses.  A table ego's come with its table and are never touched by a step; any other ego's are read and written once per step.
     static constexpr bool PARK = LATE && HAST && WV == 1;
+    // QUIET (the LATE variants with one wavefront per tile): while a call runs, the only reader of a collision row is the ego
+    // lane's CollisionMetric, so a step in which no body lies within the ego's broad-phase reach -- and which is not the last
+    // one of the call or of a scenario -- runs the pass up to the box centres only: the ego's row is 0, the other lanes keep
+    // the row of their last full pass until the next one (see ego_near in sgym_collide.hpp and `quiet_on` in rollout_body_l).
+    static constexpr bool QUIET = LATE && WV == 1 && !RSSV;
     static constexpr int TL = SG_TAB_LANES(G, WV);       // controlled lanes of a wavefront whose table rows the step loop fetches
     using Lds = TileLds<NS, PED, CROWD, CROWD && !RIDERS>; // the workgroup's LDS tile
 };
@@ -671,6 +676,10 @@ __device__ __forceinline__ void rollout_body_l(
         asm volatile("" : "+v"(r_o));
         return p.sdyn[r_o];
     };
+    // QUIET, wave-uniform and fixed for the call: may a step leave out the collision pass behind the box centres?  Only where
+    // nothing but the ego's CollisionMetric looks at a row between two full passes: max_length is the only terminal condition
+    // (the same condition as in vel_every_step), nothing is recorded, the switch (SG_QUIET, default on) is not off.
+    const bool quiet_on = V::QUIET && p.quiet != 0 && (p.term_mask & ~SG_TERM_MAX_LENGTH) == 0 && p.rec_cap == 0;
     PhaseTimers ptm;
 #ifdef SG_PHASE_TIMERS
     ptm.start();
@@ -1075,17 +1084,42 @@ __device__ __forceinline__ void rollout_body_l(
         }
         PH(1);
         // ---- State.collisions ----
-        uint64_t nrow[WV];
-        tile_collisions<G, WV, PED, CROWD, REFINE>(present, pose, velx, vely, (t + timestep) - t, bcx, bcy, rad_thr, trig_eps, nbr_thr, cell_inv,
-                                                   is_ped_type, sl, tile0, lds, nrow, mult_rows, nbr, dense, &crowd_ok, &ptm, hetero, rmax_tile);
-        if (run) {
+        const TileCentre cen = tile_centre(present, pose, bcx, bcy, rad_thr, nbr_thr, cell_inv);
+        // QUIET: a step whose rows nobody can see.  Not the last step of the call or work item (the rows are stored or handed
+        // on there), not a step that ends a running lane's scenario (the lane keeps the rows of that step: `done` by
+        // max_length, the test of check_terminal below on the clock just committed), and nobody within the ego's reach.  One
+        // vote.  Then the ego lane's row is 0 -- what the pass would give it -- so last_row becomes 0 and there are no events;
+        // every other lane keeps the row of its last full pass, which nothing reads before the next one: however the loop is
+        // left, the last step a lane RAN was a full pass (the call's last step, or the step that ended its scenario; a lane that
+        // never ran holds the row it loaded), and force / resumed calls change nothing about that.
+        bool quiet = false;
+        if (V::QUIET && quiet_on && k != n_steps - 1) {
+            const bool ends = (p.term_mask & SG_TERM_MAX_LENGTH) && (t + dt > length);
+            // the ego of this lane's tile as a lane of the wavefront, from the egos' ballot (the mask `is_ego` lives in anyway):
+            // G == 64 one scalar instruction, wave-uniform; G < 64 per lane -- a tile lies inside one 32-bit half of the ballot
+            const uint64_t ego_mask = __ballot(is_ego);
+            int ego_lane = (int)__builtin_ctzll(ego_mask | (1ull << 63));
+            if (G < 64) {
+                const uint32_t half = lane < 32 ? (uint32_t)ego_mask : (uint32_t)(ego_mask >> 32);
+                ego_lane = tile0 + (int)(__builtin_ctz((half >> (tile0 & 31)) | 0x80000000u) & (G - 1));
+            }
+            quiet = !sg_any(run_lane & (ends | ego_near<G>(cen, present, is_ego, ego_lane)));
+        }
+        if (V::QUIET && quiet) {
+            if (run && is_ego) row[0] = 0;
+        } else {
+            uint64_t nrow[WV];
+            tile_collisions_from<G, WV, PED, CROWD, REFINE>(cen, present, pose, velx, vely, (t + timestep) - t, bcx, bcy, trig_eps,
+                                                            is_ped_type, sl, tile0, lds, nrow, mult_rows, nbr, dense, &crowd_ok, &ptm, hetero, rmax_tile);
+            if (run) {
 #pragma unroll
-            for (int w = 0; w < WV; ++w) {
-                // (likewise the collision row: stored when it differs from the stored one in some lane of the wavefront;
-                // LATE: where the loop is left)
-                const bool row_moved = !LATE && (SLICE || sg_any(nrow[w] != row[w]));
-                row[w] = nrow[w];
-                if ((!SLICE || (sa.mode == 1 && !warm)) && row_moved) stf(dy, SG_F_COLL + w, row[w]);
+                for (int w = 0; w < WV; ++w) {
+                    // (likewise the collision row: stored when it differs from the stored one in some lane of the wavefront;
+                    // LATE: where the loop is left)
+                    const bool row_moved = !LATE && (SLICE || sg_any(nrow[w] != row[w]));
+                    row[w] = nrow[w];
+                    if ((!SLICE || (sa.mode == 1 && !warm)) && row_moved) stf(dy, SG_F_COLL + w, row[w]);
+                }
             }
         }
 
