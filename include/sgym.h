@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers) */
 
 typedef enum {
     SG_OK = 0,
@@ -80,6 +80,20 @@ typedef struct sg_road_networks {
     const double *verts;            /* [n_verts][2] x, y */
     const uint32_t *layers;         /* [n_polygons] SG_LAYER_* */
 } sg_road_networks;
+
+/* The lane centre lines of the same networks (Lane.center and Lane.successors, road_network/objects.py), for
+ * sg_lane_observation.  Lane q of network n = lanes [lane_off[n], lane_off[n+1]); its centre points =
+ * pts[pt_off[q] .. pt_off[q+1]) in driving order (fewer than two points: the lane has no segments and is never chosen);
+ * its successors = succ[succ_off[q] .. succ_off[q+1]), lane indices WITHIN the network (the library sorts them and drops
+ * duplicates).  HOST arrays, copied by the call. */
+typedef struct sg_lanes {
+    int32_t n_networks;
+    const int64_t *lane_off; /* [n_networks + 1] */
+    const int64_t *pt_off;   /* [n_lanes + 1] */
+    const double *pts;       /* [n_pts][2] x, y */
+    const int64_t *succ_off; /* [n_lanes + 1] */
+    const int32_t *succ;     /* [n_succ] */
+} sg_lanes;
 
 /* controller parameter slots (VehicleController.__init__ controller.py:64-98, PIDController.__init__ :154-196) */
 enum {
@@ -454,6 +468,60 @@ int sg_nearest_entities(sg_handle *h, int32_t k, double radius, double *feat, in
  * (feat may be NULL then). */
 int sg_nearest_entities_observers(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count,
                                   int32_t outputs_device);
+
+/* The lane centre lines of the networks of sg_set_road_networks, which comes first: its net_of_scenario tells which
+ * network a scenario uses.  SG_ERR_STATE before sg_upload or before sg_set_road_networks.  SG_ERR_INVALID: n_networks other
+ * than that call's, offsets that do not start at 0 or are not monotone, a successor index outside its network, a NULL array
+ * that is needed, 2^31 or more lanes or segments.  A refused call changes nothing.  sg_upload and sg_set_road_networks forget
+ * the lanes, as sg_upload forgets the networks and the observers.  The call waits for the work queued on sg_stream(h) (a queued
+ * sg_lane_observation may still read the previous lanes) and builds one device row per segment a -> b of every centre line,
+ * lane by lane in point order -- a, e = b - a, L2 = ex*ex + ey*ey (unfused), len = sqrt(L2), cum = the arclength of a within
+ * its lane as the sequential fp64 sum of the preceding len (0 for the first segment), b -- and per lane its segment range,
+ * total = cum + len of its last segment and its successors. */
+int sg_set_lanes(sg_handle *h, const sg_lanes *lanes);
+
+#define SG_LANE_MAX_K 8      /* lanes per observer */
+#define SG_LANE_MAX_AHEAD 16 /* centre-line points ahead per lane */
+#define SG_LANE_MAX_HOPS 4   /* successors a look-ahead point may walk through */
+
+/* The lane-frame vector observation of the ego of every scenario (n = n_scenarios observers): where the vehicle is relative
+ * to the k nearest lanes of its scenario's network and where their centre lines go next.  The reference has no such sensor (it
+ * stores Lane.center and the successor ids, road_network/objects.py, road_network.py:349-355).  Plain fp64 with IEEE division
+ * and square root, no fused operation.  For an observer with pose (px, py, h) and (s, c) = sin, cos of h:
+ *   projection onto segment i (a, b, e, L2 as sg_set_lanes built them) of its scenario's network: wx = px - ax, wy = py - ay,
+ *     t = (wx*ex + wy*ey) / L2; the closest point (cx, cy) is a when L2 == 0 or !(t > 0) (then t counts as 0), b exactly -- the
+ *     stored point, not a + e -- when t >= 1 (t counts as 1), else (ax + t*ex, ay + t*ey); dx = px - cx, dy = py - cy,
+ *     d2 = dx*dx + dy*dy; a segment whose d2 is not finite is skipped
+ *   a lane's key is the smallest (d2, segment index) over its segments; the lane is a candidate iff that d2 <= radius * radius
+ *     (inclusive; radius = +inf: every lane that has a segment); the candidates are ordered by ascending (d2, lane index) -- two
+ *     lanes that share an end point tie exactly and the lower index wins -- and the first k fill the rows
+ *   feat[o][j][0 .. 5 + 2*n_ahead] for a chosen lane with best segment i, (ux, uy) = (ex/len, ey/len) or (0, 0) when len == 0:
+ *     [0] ux*dy - uy*dx, the lateral offset, left of the lane direction positive; [1] c*ux + s*uy and [2] s*ux - c*uy, cos and sin
+ *     of the observer's heading relative to the lane; [3] s0 = cum + t*len, the arclength along the lane; [4] total - s0;
+ *     [5] sqrt(d2); then for m = 1..n_ahead the centre-line point at arclength target = s0 + (double)m * spacing, walked from
+ *     the chosen lane anew for every m: while target > total of the lane, fewer than SG_LANE_MAX_HOPS hops were made and the
+ *     lane has a successor with at least one segment, target -= total and the lane becomes its lowest-index such successor; if
+ *     target > total still, the point is the lane's last point; else with g the last segment of the lane with cum[g] <= target
+ *     and u = (target - cum[g]) / len[g] (0 when len[g] == 0) the point is b of g when u >= 1, else (ax + u*ex, ay + u*ey).
+ *     With X = x - px, Y = y - py: [6 + 2(m-1)] = X*c + Y*s, [7 + 2(m-1)] = Y*c - X*s (the observer's frame)
+ *   lanes[o][j]  the lane's index within its network, -1 behind the last candidate.  May be NULL
+ *   count[o]     the number of candidates (it may exceed k).  May be NULL
+ * Rows behind the last candidate are +0.0.  An observer that is not in State.poses gets count -1, lanes -1 and zeros; a
+ * scenario without a network, or a handle without sg_set_lanes, count 0, lanes -1 and zeros.  Every byte of the outputs given
+ * is written.  feat: [n][k][6 + 2*n_ahead] doubles, lanes: [n][k], count: [n]; HOST (outputs_device == 0, synchronous, through
+ * the observation scratch) or DEVICE (queued on sg_stream(h), not waited for), as in sg_nearest_entities, and a persistent
+ * rollout launch that gave up is reported as there.  SG_ERR_INVALID: k outside 1..SG_LANE_MAX_K, n_ahead outside
+ * 0..SG_LANE_MAX_AHEAD, spacing NaN, negative or infinite, radius NaN or negative, feat NULL.  SG_ERR_STATE before sg_upload.
+ * One wavefront per observer tests every segment of the network (the committed networks have at most 11,040 centre points: no
+ * index) and selects in k rounds of a cross-lane minimum.  Not part of the sg_tick graph. */
+int sg_lane_observation(sg_handle *h, int32_t k, int32_t n_ahead, double spacing, double radius,
+                        double *feat, int32_t *lanes, int32_t *count, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_lane_observation for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_lane_observation_observers(sg_handle *h, int32_t k, int32_t n_ahead, double spacing, double radius,
+                                  double *feat, int32_t *lanes, int32_t *count, int32_t outputs_device);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

@@ -8,6 +8,7 @@ from .agent import (  # noqa: F401
     ExternalVehicleAgent,
     FutureCollisionDetector,
     GlobalCollisionDetector,
+    LaneSensor,
     NearestEntitiesSensor,
     PIDController,
     RasterizedMapSensor,
@@ -27,7 +28,8 @@ from .agent import (  # noqa: F401
 )
 from .engine import PackedScenarios, RolloutEngine  # noqa: F401
 from .observation import (  # noqa: F401
-    CollisionObservation, FutureCollisionObservation, MapObservation, NearestEntitiesObservation, Observation, SingleEntityObservation,
+    CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
+    SingleEntityObservation,
     combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401

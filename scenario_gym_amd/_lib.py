@@ -35,6 +35,7 @@ SYMBOLS = (
     "sg_group_read_metrics", "sg_group_last_error", "sg_host_alloc", "sg_host_free", "sg_road_info", "sg_road_info_points",
     "sg_set_observers", "sg_raster_map_observers", "sg_future_collision_observers",
     "sg_nearest_entities", "sg_nearest_entities_observers",
+    "sg_set_lanes", "sg_lane_observation", "sg_lane_observation_observers",
 )
 
 
@@ -54,6 +55,10 @@ class SgScenarios(C.Structure):
 class SgRoadNetworks(C.Structure):
     _fields_ = [("n_networks", C.c_int32)] + [(n, C.c_void_p) for n in
                                               ("net_of_scenario", "poly_off", "ring_off", "vert_off", "verts", "layers")]
+
+
+class SgLanes(C.Structure):  # include/sgym.h sg_lanes
+    _fields_ = [("n_networks", C.c_int32)] + [(n, C.c_void_p) for n in ("lane_off", "pt_off", "pts", "succ_off", "succ")]
 
 
 class SgSocialForce(C.Structure):
@@ -201,6 +206,9 @@ def load():
     lib.sg_future_collision_observers.argtypes = [H, C.c_double, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_nearest_entities.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_nearest_entities_observers.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_set_lanes.argtypes = [H, C.POINTER(SgLanes)]
+    lib.sg_lane_observation.argtypes = [H, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes
     lib.sg_debug_trig32.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _lib as L
 from .entity import Entity
-from .observation import (CollisionObservation, FutureCollisionObservation, MapObservation, NearestEntitiesObservation,
-                          SingleEntityObservation, combine_observations)
+from .observation import (CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation,
+                          NearestEntitiesObservation, SingleEntityObservation, combine_observations)
 from .scenario import Scenario
 
 
@@ -155,6 +155,25 @@ class NearestEntitiesSensor(Sensor):
     def _step(self, state):
         neighbours, features = state.nearest_entities(self.k, self.radius, entity=self.entity)
         return NearestEntitiesObservation(self.entity, *state.get_entity_data(self.entity), neighbours, features)
+
+
+class LaneSensor(Sensor):
+    """Where the sensor's entity sits relative to the lanes (no counterpart in the reference): the k lanes of the scenario's
+    road network whose centre lines are nearest, within `radius`, and n_ahead centre-line points `spacing` apart ahead on each,
+    in the entity's frame, computed on the device for the whole batch: sg_lane_observation for the egos, one
+    sg_lane_observation_observers call for the sensors of all other entities."""
+
+    def __init__(self, entity: Entity, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf")):
+        super().__init__(entity)
+        self.k, self.n_ahead, self.spacing, self.radius = int(k), int(n_ahead), float(spacing), float(radius)
+
+    @property
+    def output_shape(self):
+        return (self.k, 6 + 2 * self.n_ahead)
+
+    def _step(self, state):
+        lanes, features = state.lane_observation(self.k, self.n_ahead, self.spacing, self.radius, entity=self.entity)
+        return LaneObservation(self.entity, *state.get_entity_data(self.entity), lanes, features)
 
 
 class GlobalCollisionDetector(Sensor):

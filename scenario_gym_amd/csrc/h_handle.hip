@@ -146,6 +146,7 @@ extern "C" int sg_destroy(sg_handle *h)
     free_pool(h->static_allocs);
     free_pool(h->state_allocs);
     free_pool(h->road_allocs);
+    free_pool(h->lane_allocs);
     free_pool(h->slice_allocs);
     free_pool(h->wide_allocs);
     h->pin_sd.release();

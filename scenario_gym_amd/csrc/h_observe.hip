@@ -1,5 +1,5 @@
-// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead and nearest-entity
-// observations of the ego and of a list of observers.
+// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity and
+// lane-frame observations of the ego and of a list of observers.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -299,4 +299,44 @@ extern "C" int sg_nearest_entities_observers(sg_handle *h, int32_t k, double rad
 {
     if (!h) return SG_ERR_INVALID;
     return nearest_call(h, "sg_nearest_entities_observers", true, k, radius, feat, slots, count, outputs_device);
+}
+
+// ---- the lane-frame vector observation (lane_observation_kernel, sgym_observers.hpp) ---------------------------------------
+// n observers as above.  Host outputs pass through the observation scratch: [n][k][6 + 2 * n_ahead] doubles, then [n][k] lane
+// indices, then [n] counts (the last two only when asked for).
+static int lane_call(sg_handle *h, const char *who, bool observers, int32_t k, int32_t n_ahead, double spacing, double radius, double *feat,
+                     int32_t *lanes, int32_t *count, int32_t outputs_device)
+{
+    if (k < 1 || k > SG_LANE_MAX_K) return fail(h, SG_ERR_INVALID, "%s: k=%d outside 1..%d", who, k, SG_LANE_MAX_K);
+    if (n_ahead < 0 || n_ahead > SG_LANE_MAX_AHEAD) return fail(h, SG_ERR_INVALID, "%s: n_ahead=%d outside 0..%d", who, n_ahead, SG_LANE_MAX_AHEAD);
+    if (!(spacing >= 0.0) || std::isinf(spacing)) return fail(h, SG_ERR_INVALID, "%s: spacing is negative, infinite or NaN", who);
+    if (!(radius >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: radius is negative or NaN", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    const size_t nk = (size_t)n * k;
+    return deliver(h, who, outputs_device, obs_scratch,
+                   {{feat, nk * (6 + 2 * (size_t)n_ahead) * sizeof(double)}, {lanes, nk * sizeof(int32_t)}, {count, (size_t)n * sizeof(int32_t)}}, 0,
+                   [&](void *const *d) {
+                       sgl::lane_observation(h->stream, h->p, h->lanes, d_scen, d_slot, n, k, n_ahead, spacing, radius, static_cast<double *>(d[0]),
+                                             static_cast<int32_t *>(d[1]), static_cast<int32_t *>(d[2]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_lane_observation(sg_handle *h, int32_t k, int32_t n_ahead, double spacing, double radius, double *feat, int32_t *lanes,
+                                   int32_t *count, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return lane_call(h, "sg_lane_observation", false, k, n_ahead, spacing, radius, feat, lanes, count, outputs_device);
+}
+
+extern "C" int sg_lane_observation_observers(sg_handle *h, int32_t k, int32_t n_ahead, double spacing, double radius, double *feat,
+                                             int32_t *lanes, int32_t *count, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return lane_call(h, "sg_lane_observation_observers", true, k, n_ahead, spacing, radius, feat, lanes, count, outputs_device);
 }

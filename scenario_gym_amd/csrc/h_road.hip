@@ -1,4 +1,5 @@
-// h_road.hip -- road networks: the cell index built on the host, and which road geometries contain each entity / point.
+// h_road.hip -- road networks: the cell index built on the host, the lane centre lines, and which road geometries contain each
+// entity / point.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -218,6 +219,7 @@ extern "C" int sg_set_road_networks(sg_handle *h, const sg_road_networks *in)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     free_pool(h->road_allocs);
+    forget_lanes(h); // (they index these networks)
     h->has_road = false;
     h->p.road = nullptr;
     h->geom = sg::RoadGeom{};
@@ -286,6 +288,87 @@ extern "C" int sg_set_road_networks(sg_handle *h, const sg_road_networks *in)
     h->p.road = dR;
     h->has_road = true;
     ++h->generation;
+    return SG_OK;
+}
+
+// ---- lane centre lines (lane_observation_kernel, sgym_observers.hpp) --------------------------------------------------
+// One device row per centre-line segment, lane by lane in point order.  This unit is compiled with -ffp-contract=off like the
+// rest of the library: the products and sums below are the unfused ones the definition in include/sgym.h names.
+extern "C" int sg_set_lanes(sg_handle *h, const sg_lanes *in)
+{
+    if (!h || !in) return h ? fail(h, SG_ERR_INVALID, "sg_set_lanes: null argument") : SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_set_lanes: no scenarios uploaded");
+    if (!h->has_road) return fail(h, SG_ERR_STATE, "sg_set_lanes: no road networks set (sg_set_road_networks comes first)");
+    if (in->n_networks != h->road.n_nets)
+        return fail(h, SG_ERR_INVALID, "sg_set_lanes: %d networks, sg_set_road_networks got %d", in->n_networks, h->road.n_nets);
+    const int nn = in->n_networks;
+    if (nn > 0 && !in->lane_off) return fail(h, SG_ERR_INVALID, "sg_set_lanes: null lane_off");
+    for (int n = 0; n < nn; ++n)
+        if (in->lane_off[0] != 0 || in->lane_off[n + 1] < in->lane_off[n]) return fail(h, SG_ERR_INVALID, "sg_set_lanes: lane_off not monotone");
+    const int64_t n_lanes = nn ? in->lane_off[nn] : 0;
+    if (n_lanes > 0 && (!in->pt_off || !in->succ_off)) return fail(h, SG_ERR_INVALID, "sg_set_lanes: null pt_off or succ_off");
+    if (n_lanes >= 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "sg_set_lanes: 2^31 - 1 or more lanes");
+    for (int64_t q = 0; q < n_lanes; ++q) {
+        if (in->pt_off[0] != 0 || in->pt_off[q + 1] < in->pt_off[q]) return fail(h, SG_ERR_INVALID, "sg_set_lanes: pt_off not monotone");
+        if (in->succ_off[0] != 0 || in->succ_off[q + 1] < in->succ_off[q]) return fail(h, SG_ERR_INVALID, "sg_set_lanes: succ_off not monotone");
+    }
+    const int64_t n_pts = n_lanes ? in->pt_off[n_lanes] : 0, n_succ = n_lanes ? in->succ_off[n_lanes] : 0;
+    if ((n_pts > 0 && !in->pts) || (n_succ > 0 && !in->succ)) return fail(h, SG_ERR_INVALID, "sg_set_lanes: null pts or succ");
+    if (n_pts >= 0x7fffffffLL || n_succ >= 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "sg_set_lanes: 2^31 - 1 or more points or successors");
+    for (int n = 0; n < nn; ++n) {
+        const int64_t in_net = in->lane_off[n + 1] - in->lane_off[n];
+        for (int64_t m = in->succ_off[in->lane_off[n]]; m < in->succ_off[in->lane_off[n + 1]]; ++m)
+            if (in->succ[m] < 0 || in->succ[m] >= in_net)
+                return fail(h, SG_ERR_INVALID, "sg_set_lanes: succ[%lld]=%d outside the %lld lanes of network %d", (long long)m, in->succ[m], (long long)in_net, n);
+    }
+    std::vector<sg::LaneSeg> segs;
+    std::vector<sg::LaneRow> rows((size_t)n_lanes);
+    std::vector<sg::LaneNet> nets((size_t)nn);
+    std::vector<int32_t> succ;
+    for (int n = 0; n < nn; ++n) {
+        const int64_t l0 = in->lane_off[n], l1 = in->lane_off[n + 1];
+        nets[(size_t)n].lane0 = (int32_t)l0; nets[(size_t)n].lane1 = (int32_t)l1;
+        nets[(size_t)n].seg0 = (int32_t)segs.size();
+        for (int64_t q = l0; q < l1; ++q) {
+            sg::LaneRow &row = rows[(size_t)q];
+            row.seg0 = (int32_t)segs.size();
+            double cum = 0.0;
+            for (int64_t i = in->pt_off[q]; i + 1 < in->pt_off[q + 1]; ++i) {
+                const double *a = in->pts + 2 * i, *b = a + 2;
+                sg::LaneSeg g{};
+                g.ax = a[0]; g.ay = a[1]; g.bx = b[0]; g.by = b[1];
+                g.ex = g.bx - g.ax; g.ey = g.by - g.ay;
+                g.L2 = g.ex * g.ex + g.ey * g.ey;
+                g.len = std::sqrt(g.L2);
+                g.cum = cum;
+                g.lane = (int32_t)q; g.first = row.seg0;
+                cum = cum + g.len;
+                segs.push_back(g);
+            }
+            row.seg1 = (int32_t)segs.size();
+            row.total = row.seg1 > row.seg0 ? segs.back().cum + segs.back().len : 0.0;
+            row.succ0 = (int32_t)succ.size();
+            for (int64_t m = in->succ_off[q]; m < in->succ_off[q + 1]; ++m) succ.push_back((int32_t)(l0 + in->succ[m]));
+            std::sort(succ.begin() + row.succ0, succ.end()); // ascending, each once: "the lowest-index successor" is the first that has segments
+            succ.erase(std::unique(succ.begin() + row.succ0, succ.end()), succ.end());
+            row.succ1 = (int32_t)succ.size();
+        }
+        nets[(size_t)n].seg1 = (int32_t)segs.size();
+    }
+    if (segs.size() >= (size_t)0x7fffffff) return fail(h, SG_ERR_INVALID, "sg_set_lanes: 2^31 - 1 or more segments");
+    if (segs.empty()) segs.push_back(sg::LaneSeg{}); // (seg != nullptr says that lanes are set)
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued sg_lane_observation may still read the previous lanes)
+    forget_lanes(h);
+    auto &A = h->lane_allocs;
+    sg::LaneIndex L{};
+    int rc = 0;
+    if (!(rc = dev_upload(h, A, &L.seg, segs)) && !(rc = dev_upload(h, A, &L.lane, rows)) && !(rc = dev_upload(h, A, &L.succ, succ)))
+        rc = dev_upload(h, A, &L.net, nets);
+    if (rc) { forget_lanes(h); return rc; }
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // host vectors go out of scope
+    L.net_of_scen = h->road.net_of_scen;
+    h->lanes = L;
     return SG_OK;
 }
 

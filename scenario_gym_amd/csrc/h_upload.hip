@@ -136,6 +136,7 @@ static void forget_batch(sg_handle *h)
     h->static_allocs.rewind(); // (buffers of the previous batch are reused where they are large enough)
     h->state_allocs.rewind();
     free_pool(h->road_allocs); // the networks belong to a batch (net_of_scenario)
+    forget_lanes(h);
     // the RSS records and the line-test queue (GiBs) belong to the handle's shape, not to the batch: they stay allocated and
     // start anew (ensure_rss / ensure_rssq on first use; a hipFree + hipMalloc of the queue per upload stalled every tenth
     // or so sg_upload of a sweep for a second)

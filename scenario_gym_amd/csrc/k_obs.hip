@@ -1,5 +1,6 @@
-// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel: the map, look-ahead and nearest-entity observations of
-// the ego of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
+// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel: the map, look-ahead,
+// nearest-entity and lane-frame observations of the ego of every scenario or of a list of observers (scenario, slot), any entity
+// of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -36,5 +37,13 @@ void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int3
     else if (p.E > 128) sg::nearest_kernel<4><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
     else if (p.E > 64) sg::nearest_kernel<2><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
     else sg::nearest_kernel<1><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+}
+
+void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L, const int32_t *scen, const int32_t *slot, int64_t n, int k,
+                      int n_ahead, double spacing, double radius, double *feat, int32_t *lanes, int32_t *count)
+{
+    if (n <= 0) return;
+    const double r2 = radius * radius; // (+inf for an infinite radius: every finite distance passes)
+    sg::lane_observation_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, L, scen, slot, n, k, n_ahead, spacing, r2, feat, lanes, count);
 }
 } // namespace sgl

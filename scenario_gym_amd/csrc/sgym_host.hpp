@@ -189,6 +189,9 @@ struct sg_handle {
     bool has_road = false;
     sg::RoadGeom geom{};                               // ... and of the per-geometry lists beside it (sg_road_info; arrays in road_allocs)
     sgh::GrowBuf road_info{sgh::GrowBuf::DEVICE_POISONED}; // device scratch of sg_road_info / sg_road_info_points (grown on demand)
+    std::vector<void *> lane_allocs;                   // sg_set_lanes
+    sg::LaneIndex lanes{};                             // host copy of its device pointers (seg == nullptr: no lanes set); sg_upload and
+                                                       // sg_set_road_networks forget them (forget_lanes)
 
     // ---- h_observe.hip: the observers ----
     sgh::GrowBuf observers{sgh::GrowBuf::DEVICE};      // sg_set_observers: [2][capacity] int32_t, scenario and slot of every observer (grown on demand)
@@ -334,6 +337,13 @@ inline void free_pool(std::vector<void *> &pool)
 {
     for (void *ptr : pool) (void)hipFree(ptr);
     pool.clear();
+}
+
+// the lanes of sg_set_lanes go with the networks they belong to (sg_set_road_networks, sg_upload, sg_destroy)
+inline void forget_lanes(sg_handle *h)
+{
+    free_pool(h->lane_allocs);
+    h->lanes = sg::LaneIndex{};
 }
 
 // one group holding every block: an ordinary launch of a table variant

@@ -59,6 +59,11 @@ void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const i
 // observer for scenarios of at most 512 entities (NB = 1, 2, 4, 8 blocks of 64 slots), one workgroup beyond (NB = 0).
 void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int k, double radius, double *feat,
              int32_t *slots, int32_t *count);
+// lane_observation_kernel: the k <= 8 nearest lane centre lines within `radius` of observer o < n (the same two lists) and
+// n_ahead <= 16 points ahead on each.  feat [n][k][6 + 2 * n_ahead], lanes [n][k] (or nullptr), count [n] (or nullptr), all DEVICE;
+// L: the rows of sg_set_lanes (L.seg == nullptr: none set).  One wavefront per observer.
+void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L, const int32_t *scen, const int32_t *slot, int64_t n, int k,
+                      int n_ahead, double spacing, double radius, double *feat, int32_t *lanes, int32_t *count);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -1,5 +1,5 @@
-// sgym_observers.hpp -- The map, look-ahead and nearest-entity observations: one raster kernel, one look-ahead kernel and one
-// nearest-entity kernel for the ego of every scenario and for a caller-given list of observers (any entity).
+// sgym_observers.hpp -- The map, look-ahead, nearest-entity and lane-frame observations: one raster kernel, one look-ahead kernel,
+// one nearest-entity kernel and one lane kernel for the ego of every scenario and for a caller-given list of observers (any entity).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
@@ -412,6 +412,182 @@ static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int
         const int slot[2] = {fin_slot[lane], fin_slot[lane + 64]};
         const int nb = near_select<2>(key, slot, k, lane);
         near_store(p, f, o, k, lane, nb, fin_total[0] + fin_total[1] + fin_total[2] + fin_total[3], feat, slots, count);
+    }
+}
+#endif // SG_UNIT_OBS
+
+// ------------------------------------------------------------------------------------------------
+// The lane-frame vector observation: where an observer sits relative to the k nearest lane centre lines of its scenario's
+// network, and where those lines go next (no counterpart in the reference, which only stores Lane.center and the successor
+// ids).  The definition is in include/sgym.h at sg_lane_observation; the rows below are built by sg_set_lanes (h_road.hip).
+// Segments are listed lane by lane, so a lane's segments are consecutive and segment order is lane order.
+// (SG_LANE_MAX_K, SG_LANE_MAX_AHEAD, SG_LANE_MAX_HOPS: include/sgym.h.)
+// ------------------------------------------------------------------------------------------------
+
+struct LaneSeg {      // one centre-line segment a -> b: 80 bytes
+    double ax, ay, ex, ey, L2, len, cum, bx, by; // e = b - a, L2 = ex*ex + ey*ey, len = sqrt(L2), cum = arclength of a within its lane
+    int32_t lane, first;                         // its lane and that lane's first segment (both indices over all networks)
+};
+struct LaneRow {      // one lane
+    double total;           // its length: cum + len of its last segment (0 without segments)
+    int32_t seg0, seg1;     // its segments [seg0, seg1)
+    int32_t succ0, succ1;   // its successors succ[succ0 .. succ1): lane indices over all networks, ascending
+};
+struct LaneNet {      // one network
+    int32_t lane0, lane1, seg0, seg1; // its lanes and (all of) their segments
+};
+struct LaneIndex {    // device pointers, by value; seg == nullptr: no lanes set
+    const LaneSeg *seg;
+    const LaneRow *lane;
+    const int32_t *succ;
+    const LaneNet *net;
+    const int32_t *net_of_scen; // the list of sg_set_road_networks
+};
+
+// the closest point of segment g to (px, py): the squared distance, the offsets from that point, the effective parameter
+__device__ __forceinline__ double lane_project(const LaneSeg &g, double px, double py, double &dx, double &dy, double &t)
+{
+    const double wx = px - g.ax, wy = py - g.ay;
+    t = (wx * g.ex + wy * g.ey) / g.L2;
+    double cx = g.ax, cy = g.ay;
+    if (g.L2 == 0.0 || !(t > 0.0)) t = 0.0;
+    else if (t >= 1.0) { t = 1.0; cx = g.bx; cy = g.by; }
+    else { cx = g.ax + t * g.ex; cy = g.ay + t * g.ey; }
+    dx = px - cx; dy = py - cy;
+    return dx * dx + dy * dy;
+}
+
+// the centre-line point at arclength `target` from the start of lane q, walked through the lowest-index successors that
+// have segments
+__device__ __forceinline__ void lane_point_ahead(const LaneIndex &L, int q, double target, double &x, double &y)
+{
+    LaneRow row = L.lane[q];
+    for (int hops = 0; target > row.total && hops < SG_LANE_MAX_HOPS; ++hops) {
+        int next = -1;
+        for (int m = row.succ0; m < row.succ1 && next < 0; ++m) {
+            const int cand = L.succ[m];
+            if (L.lane[cand].seg1 > L.lane[cand].seg0) next = cand;
+        }
+        if (next < 0) break;
+        target -= row.total;
+        row = L.lane[next];
+    }
+    if (target > row.total) { // the end of the walk: the lane's last point
+        x = L.seg[row.seg1 - 1].bx; y = L.seg[row.seg1 - 1].by;
+        return;
+    }
+    int lo = row.seg0, hi = row.seg1; // the last segment with cum <= target (cum[seg0] = 0 <= target)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (L.seg[mid].cum <= target) lo = mid; else hi = mid;
+    }
+    const LaneSeg g = L.seg[lo];
+    const double u = g.len == 0.0 ? 0.0 : (target - g.cum) / g.len;
+    if (u >= 1.0) { x = g.bx; y = g.by; }
+    else { x = g.ax + u * g.ex; y = g.ay + u * g.ey; }
+}
+
+// Observer o < n as in nearest_kernel; feat [n][k][6 + 2 * n_ahead], lanes [n][k] (may be nullptr), count [n] (may be nullptr),
+// every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no atomics.
+// Selection: k rounds; in each the wavefront's lanes stride over the network's segment rows (a load is 64 consecutive 80-byte
+// rows), skip the segments of the road lanes chosen so far -- at most eight ids, the same in every lane of the wavefront --
+// and keep the smallest (d2 bits, segment index); near_wave_min makes it the wavefront's.  A rescan per round rather than a
+// table of per-road-lane minima in LDS: a network has no bound on its lanes, so the table would need a second path for
+// the networks that do not fit, and k times the segment tests of the largest committed network (11,040 points) is below the
+// launch overhead of the call.  Round 0 also counts the candidates: a segment within the radius counts for its road lane iff no
+// earlier segment of that lane is within the radius -- the 64 segments of one stride step are consecutive, so that is a ballot
+// and the lane counted last.
+// Then item j * (n_ahead + 1) + m of the wavefront is feature group m of row j: group 0 the six scalars of the best segment,
+// group m >= 1 the m-th point ahead.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, LaneIndex L, const int32_t *obs_scen, const int32_t *obs_slot,
+                                                                      int64_t n, int k, int n_ahead, double spacing, double r2, double *feat,
+                                                                      int32_t *lanes, int32_t *count)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t o = (int64_t)blockIdx.x * 4 + w;
+    if (o >= n) return; // (the whole wavefront, which meets no barrier)
+    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    const int net = (f.present && L.seg) ? L.net_of_scen[f.r] : -1;
+    int total = f.present ? 0 : -1, found = 0;
+    int mine = 0; // lane j: the best segment of row j
+    if (net >= 0) {
+        const LaneNet N = L.net[net];
+        int ch[SG_LANE_MAX_K]; // the road lanes chosen so far (wavefront-uniform; registers: only ever indexed by unrolled loops)
+#pragma unroll
+        for (int m = 0; m < SG_LANE_MAX_K; ++m) ch[m] = -1;
+        int counted = -1; // round 0: the last road lane counted
+        for (int j = 0; j < k; ++j) {
+            uint64_t bk = NEAR_NONE;
+            int bs = NEAR_NO_SLOT;
+            for (int i0 = N.seg0; i0 < N.seg1; i0 += 64) { // (uniform trip count: the ballot below is the whole wavefront's)
+                const int i = i0 + lane;
+                const LaneSeg g = L.seg[min(i, N.seg1 - 1)];
+                double dx, dy, t;
+                const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
+                bool in = i < N.seg1 && d2 <= r2 && d2 < __builtin_inf(); // (a NaN fails both)
+                if (j == 0) {
+                    const uint64_t q = __ballot(in);
+                    const int run = max(g.first - i0, 0); // where this road lane's segments start within the step
+                    const uint64_t before = q & ((1ull << lane) - 1) & ~((1ull << run) - 1);
+                    total += __popcll(__ballot(in && before == 0 && g.lane != counted));
+                    if (q) counted = __shfl(g.lane, 63 - __clzll(q), 64);
+                }
+#pragma unroll
+                for (int m = 0; m < SG_LANE_MAX_K; ++m) in = in && g.lane != ch[m];
+                const uint64_t key = (uint64_t)__double_as_longlong(d2);
+                const bool take = in && (key < bk || (key == bk && i < bs));
+                bk = take ? key : bk;
+                bs = take ? i : bs;
+            }
+            near_wave_min(bk, bs);
+            if (bk == NEAR_NONE) break; // (the same in every lane: no candidate is left)
+            const int q = __builtin_amdgcn_readfirstlane(L.seg[bs].lane);
+#pragma unroll
+            for (int m = 0; m < SG_LANE_MAX_K; ++m) ch[m] = m == j ? q : ch[m];
+            if (lane == j) mine = bs;
+            ++found;
+        }
+    }
+    if (lane == 0 && count) count[o] = total;
+    const int groups = n_ahead + 1, W = 6 + 2 * n_ahead;
+    for (int t0 = 0; t0 < k * groups; t0 += 64) { // (uniform trip count: the cross-lane read is the whole wavefront's)
+        const int item = t0 + lane, j = min(item / groups, SG_LANE_MAX_K - 1), m = item - (item / groups) * groups;
+        const int best = __shfl(mine, j, 64);
+        if (item >= k * groups) continue;
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        int q = -1;
+        if (j < found) {
+            const LaneSeg g = L.seg[best];
+            q = g.lane;
+            double dx, dy, t;
+            const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
+            const double s0 = g.cum + t * g.len;
+            if (m == 0) {
+                const double ux = g.len == 0.0 ? 0.0 : g.ex / g.len, uy = g.len == 0.0 ? 0.0 : g.ey / g.len;
+                v[0] = ux * dy - uy * dx;
+                v[1] = f.c * ux + f.s * uy;
+                v[2] = f.s * ux - f.c * uy;
+                v[3] = s0;
+                v[4] = L.lane[q].total - s0;
+                v[5] = __builtin_sqrt(d2);
+            } else {
+                double x, y;
+                lane_point_ahead(L, q, s0 + (double)m * spacing, x, y);
+                const double X = x - f.x, Y = y - f.y;
+                v[0] = X * f.c + Y * f.s;
+                v[1] = Y * f.c - X * f.s;
+            }
+        }
+        double *row = feat + ((size_t)o * k + j) * W;
+        if (m == 0) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) row[c] = v[c];
+            if (lanes) lanes[(size_t)o * k + j] = q < 0 ? -1 : q - L.net[net].lane0;
+        } else {
+            row[4 + 2 * m] = v[0];
+            row[5 + 2 * m] = v[1];
+        }
     }
 }
 #endif // SG_UNIT_OBS

@@ -380,7 +380,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -440,6 +440,53 @@ class RolloutEngine:
         """nearest_entities for every observer of set_observers (sg_nearest_entities_observers): (feat [n, k, 8], slots [n, k],
         count [n]); empty arrays when no observers are set."""
         return self._nearest(self.lib.sg_nearest_entities_observers, self._n_obs, k, radius, torch_out)
+
+    def set_lanes(self, networks):
+        """sg_set_lanes: the lane centre lines of the networks of set_road_networks, which comes first (its net_of_scenario
+        holds).  networks: one lane_arrays() dict (pt_off, pts, succ_off, succ; scenario_gym_amd.road_network.RoadNetwork) per
+        network of that call, in its order.  Needed by lane_observation; upload() and set_road_networks() forget the lanes."""
+        lane_off, pt_off, succ_off, pts, succ = [0], [np.zeros(1, np.int64)], [np.zeros(1, np.int64)], [], []
+        n_pts = n_succ = 0
+        for a in networks:
+            po, so = np.asarray(a["pt_off"], np.int64), np.asarray(a["succ_off"], np.int64)
+            pt_off.append(po[1:] + n_pts)  # (running totals: a network without lanes adds nothing)
+            succ_off.append(so[1:] + n_succ)
+            n_pts, n_succ = n_pts + int(po[-1]), n_succ + int(so[-1])
+            pts.append(np.asarray(a["pts"], np.float64).reshape(-1, 2))
+            succ.append(np.asarray(a["succ"], np.int32).ravel())
+            lane_off.append(lane_off[-1] + len(po) - 1)
+        lane_off = np.array(lane_off, np.int64)
+        pt_off, succ_off = np.concatenate(pt_off), np.concatenate(succ_off)
+        pts = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 2)))
+        succ = np.ascontiguousarray(np.concatenate(succ) if succ else np.zeros(0, np.int32))
+        p = lambda a: a.ctypes.data  # noqa: E731
+        st = L.SgLanes(len(networks), p(lane_off), p(pt_off), p(pts), p(succ_off), p(succ))
+        self._check(self.lib.sg_set_lanes(self.h, C.byref(st)), "sg_set_lanes")
+
+    def _lane_observation(self, call, n, k, n_ahead, spacing, radius, torch_out):
+        k, n_ahead = int(k), int(n_ahead)
+        outs, ptrs = self._outputs(torch_out, ((n, k, 6 + 2 * max(n_ahead, 0)), "float64"), ((n, k), "int32"), ((n,), "int32"))
+        self._check(call(self.h, k, n_ahead, float(spacing), float(radius), *ptrs, int(bool(torch_out))), call.__name__)
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
+
+    def lane_observation(self, k=3, n_ahead=4, spacing=2.0, radius=float("inf"), torch_out=False):
+        """The lane-frame vector observation of the ego of every scenario (sg_lane_observation): the k <= 8 lanes of the
+        scenario's network whose centre lines are nearest to the ego and within `radius` (inclusive), by ascending (squared
+        distance, lane index).  Returns (feat [R, k, 6 + 2 * n_ahead] float64, lanes [R, k] int32, count [R] int32): per lane the
+        lateral offset from the centre line (left positive), cos and sin of the ego's heading relative to the lane direction,
+        the arclength along the lane and what is left of it, the distance, then n_ahead <= 16 centre-line points `spacing` apart
+        ahead of the ego in the ego's frame, continued through the lowest-index successors (at most four) and held at the last
+        point where they end.  lanes: indices into `RoadNetwork.lanes`, -1 and zero features behind the last; count = the lanes
+        within the radius (it may exceed k), -1 for an ego that is not in the scene, 0 without a network or before set_lanes.
+        torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
+        return self._lane_observation(self.lib.sg_lane_observation, self.R, k, n_ahead, spacing, radius, torch_out)
+
+    def lane_observation_observers(self, k=3, n_ahead=4, spacing=2.0, radius=float("inf"), torch_out=False):
+        """lane_observation for every observer of set_observers (sg_lane_observation_observers): (feat [n, k, 6 + 2 * n_ahead],
+        lanes [n, k], count [n]); empty arrays when no observers are set."""
+        return self._lane_observation(self.lib.sg_lane_observation_observers, self._n_obs, k, n_ahead, spacing, radius, torch_out)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

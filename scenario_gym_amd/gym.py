@@ -12,11 +12,11 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .agent import CombinedSensor, FutureCollisionDetector, NearestEntitiesSensor, RasterizedMapSensor, _create_agent
+from .agent import CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RasterizedMapSensor, _create_agent
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_scenarios
-from .road_network import LAYER_CODES, shared_polygon_arrays
+from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
 from .state import State
 
@@ -50,7 +50,7 @@ class BatchedScenarioGym:
         self._rec = None
         self._fut = None
         self._rss_cache = None
-        self._observers: list = []   # (scenario index, entity slot) of the non-ego entities that carry a map / look-ahead / nearest-entity sensor
+        self._observers: list = []   # (scenario index, entity slot) of the non-ego entities that carry a map / look-ahead / nearest-entity / lane sensor
         self._observer_of: dict = {}  # ... -> position in the engine's observer list
         self._observers_sent = 0     # how many of them the engine knows
 
@@ -193,7 +193,7 @@ class BatchedScenarioGym:
         self._packed = packed
         self.scenarios, self.states, self._host_agents, self._policy_agents = [], [], [], []
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
-        self._roads_set = True
+        self._roads_set, self._lanes_set = True, False
         self.metrics = [list(self.metric_factory()) for _ in range(packed.n_scenarios)]
         if any(not isinstance(m, _DeviceMetric) for m in self.metrics[0]):
             raise ValueError("set_packed: device metrics only")
@@ -255,7 +255,7 @@ class BatchedScenarioGym:
         if self._rss_on:
             self.engine.set_rss(True)
         self.engine.upload(packed)
-        self._roads_set = False
+        self._roads_set = self._lanes_set = False
         # the road network reaches the device when the rollout itself needs it: the ego_off_road terminal condition, and
         # pedestrian agents (the boundary terms of the social force, social_force.py:86-104)
         if "ego_off_road" in dev_terms or (sf is not None and any(sc.road_network is not None for sc in self.scenarios)):
@@ -276,7 +276,7 @@ class BatchedScenarioGym:
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
-        # the observers of the batch: every map / look-ahead / nearest-entity sensor of a non-ego entity (inside a CombinedSensor too), so that
+        # the observers of the batch: every map / look-ahead / nearest-entity / lane sensor of a non-ego entity (inside a CombinedSensor too), so that
         # one device call per step and sensor configuration serves all of them; a sensor met later joins when it is first stepped
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
 
@@ -290,7 +290,7 @@ class BatchedScenarioGym:
         for i, sc in enumerate(self.scenarios):
             for a in agents[i].values():
                 for s in leaves(getattr(a, "sensor", None)):
-                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
                         self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
@@ -359,6 +359,24 @@ class BatchedScenarioGym:
         """(feat [n, k, 8], slots [n, k], count [n]) of NearestEntitiesSensor."""
         call = self.engine.nearest_entities_observers if observers else self.engine.nearest_entities
         return self._cached(("near", observers, k, radius), lambda: call(k, radius), observers=observers)
+
+    def _set_lanes(self):
+        """The lane centre lines of every scenario's road network -> the device (behind the networks themselves, whose
+        scenario list they share), when a lane observation is first asked for."""
+        self._set_road_networks()
+        if not self._lanes_set and self.scenarios:
+            self.engine.set_lanes(shared_lane_arrays(self.scenarios)[0])
+            self._lanes_set = True
+
+    def _lane_observation(self, observers: bool, k: int, n_ahead: int, spacing: float, radius: float):
+        """(feat [n, k, 6 + 2 * n_ahead], lanes [n, k], count [n]) of LaneSensor."""
+        call = self.engine.lane_observation_observers if observers else self.engine.lane_observation
+
+        def compute():
+            self._set_lanes()
+            return call(k, n_ahead, spacing, radius)
+
+        return self._cached(("lane", observers, k, n_ahead, spacing, radius), compute, observers=observers)
 
     def _raster(self, width, height, nw, nh):
         return self._cached(("raster", width, height, nw, nh), lambda: self.engine.raster_entities(width, height, nw, nh))

@@ -59,6 +59,19 @@ class NearestEntitiesObservation(SingleEntityObservation):
     features: np.ndarray
 
 
+@dataclass
+class LaneObservation(SingleEntityObservation):
+    """The lane-frame vector observation (no counterpart in the reference): `lanes`, the lanes of the scenario's road network
+    whose centre lines are nearest to the entity, within the sensor's radius, by ascending (squared distance, position in
+    `RoadNetwork.lanes`), at most k of them, and `lane_features` [k, 6 + 2 * n_ahead] -- per lane the lateral offset from the
+    centre line (left positive), cos and sin of the entity's heading relative to the lane direction, the arclength along the
+    lane and what is left of it, the distance, then the n_ahead centre-line points ahead in the entity's frame; rows behind
+    the last lane are zero."""
+
+    lanes: list
+    lane_features: np.ndarray
+
+
 def combine_observations(*classes, prefixes: Optional[Sequence[Optional[str]]] = None):
     """observation.py:31-84: a dataclass holding the fields of all `classes` in order.  A field name that an earlier class
     already contributed is skipped -- or, with `prefixes` (one per class), taken as "<prefix>_<name>"; a name that is still

@@ -18,7 +18,9 @@ the even-odd rule.
 Which geometries contain a point (`get_geometries_at_point`, road_network.py:375-407) is answered on the device, for
 batches of entities or points: `State.get_road_info_at_entity`, `ScenarioGym.get_geometries_at_point`,
 `BatchedScenarioGym.get_geometries_at_points` / `road_info`.  `geometry_index()` maps the indices the device returns to
-the objects here.  The lane graph (road_network.py:330-373) is host-only.
+the objects here.  The lane graph (road_network.py:330-373) is answered on the host; the lanes' centre lines and successors also
+go to the device (`lane_arrays()`, `sg_set_lanes`) for the lane-frame observation (`State.lane_observation`, `LaneSensor`,
+`VectorScenarioEnv.lane_observation`).
 """
 import json
 import os
@@ -44,6 +46,19 @@ def shared_polygon_arrays(scenarios):
         if rn is not None and id(rn) not in index:
             index[id(rn)] = len(nets)
             nets.append(rn.polygon_arrays())
+        net_of.append(-1 if rn is None else index[id(rn)])
+    return nets, net_of
+
+
+def shared_lane_arrays(scenarios):
+    """The argument of RolloutEngine.set_lanes for `scenarios`, shared as shared_polygon_arrays shares: (lane_arrays() of every
+    distinct road network once, per scenario its index into that list, -1 for none)."""
+    nets, index, net_of = [], {}, []
+    for sc in scenarios:
+        rn = sc.road_network
+        if rn is not None and id(rn) not in index:
+            index[id(rn)] = len(nets)
+            nets.append(rn.lane_arrays())
         net_of.append(-1 if rn is None else index[id(rn)])
     return nets, net_of
 
@@ -360,6 +375,23 @@ class RoadNetwork:
         if (~inside).any():
             z[~inside] = outside_fn(xy[~inside])
         return z.squeeze() if both_1d else z
+
+    def lane_arrays(self) -> Dict[str, np.ndarray]:
+        """The centre lines and successors of `lanes`, lane q = lanes[q]: pt_off [n_lanes + 1] and pts [n_pts][2] (a lane with a
+        missing or one-point centre has no points here), succ_off [n_lanes + 1] and succ -- the successor ids resolved to lane
+        indices, ascending, duplicates and unknown ids dropped (the reference's order is a per-process set order)."""
+        if getattr(self, "_lane_arrays", None) is not None:
+            return self._lane_arrays
+        lanes = self.lanes
+        index = {l.id: q for q, l in enumerate(lanes)}
+        pts = [l.center if l.center is not None and len(l.center) >= 2 else np.zeros((0, 2)) for l in lanes]
+        succ = [sorted({index[i] for i in getattr(l, "successors", ()) if i in index}) for l in lanes]
+        self._lane_arrays = dict(
+            pt_off=np.concatenate([[0], np.cumsum([len(c) for c in pts])]).astype(np.int64),
+            pts=np.ascontiguousarray(np.concatenate(pts, axis=0) if pts else np.zeros((0, 2)), np.float64),
+            succ_off=np.concatenate([[0], np.cumsum([len(x) for x in succ])]).astype(np.int64),
+            succ=np.array([q for x in succ for q in x], np.int32))
+        return self._lane_arrays
 
     def polygon_arrays(self) -> Dict[str, np.ndarray]:
         """Every boundary polygon once, with the unions it belongs to as LAYER_* bits:

@@ -213,6 +213,19 @@ class State:
         ents = self._scenario.entities
         return [ents[j] for j in slots[row] if j >= 0], feat[row].copy()
 
+    def lane_observation(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf"),
+                         entity: Optional[Entity] = None):
+        """LaneSensor(entity, k, n_ahead, spacing, radius) at the current state, computed on the device: (lanes, features) -- the
+        at most k lanes of the scenario's road network (objects of `RoadNetwork.lanes`) whose centre lines are nearest to
+        `entity` (any entity of the scenario, default the ego) and within `radius`, by ascending (squared distance, position in
+        `RoadNetwork.lanes`), and their [k, 6 + 2 * n_ahead] feature rows (zeros behind the last).  ([], zeros) for an entity
+        that is not in `poses` and for a scenario without a road network."""
+        observers, row = self._sensor_row(entity)
+        feat, idx, _ = self._gym._lane_observation(observers, int(k), int(n_ahead), float(spacing), float(radius))
+        rn = self._scenario.road_network
+        lanes = rn.lanes if rn is not None else []
+        return [lanes[j] for j in idx[row] if j >= 0], feat[row].copy()
+
     def get_road_info_at_entity(self, e: Entity):
         """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's
         position -- "Road", "Intersection", "Lane", "Pavement", "Crossing", "Building", the objects the scenario's RoadNetwork

@@ -18,7 +18,7 @@ from . import _lib as L
 from .agent import ExternalVehicleAgent
 from .engine import RolloutEngine, terminal_mask
 from .packing import pack_scenarios
-from .road_network import LAYER_CODES, shared_polygon_arrays
+from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
 
 
@@ -46,6 +46,7 @@ class VectorScenarioEnv:
                                     terminal_conditions=self.terminal_conditions, device=device)
         self.engine.upload(packed)
         self.engine.set_road_networks(*shared_polygon_arrays(self.scenarios))
+        self._lanes_set = False  # the lane centre lines go down when a lane observation is first asked for
         self._mask = terminal_mask(self.terminal_conditions)
         self.done = np.zeros(self.n_envs, bool)
         self._obs_env, self._obs_slot = np.zeros(0, np.int32), np.zeros(0, np.int32)  # set_observers
@@ -137,6 +138,26 @@ class VectorScenarioEnv:
         (feat [n, k, 8], slots [n, k], count [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy
         arrays."""
         out = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
+
+    def _set_lanes(self):
+        if not self._lanes_set:
+            self.engine.set_lanes(shared_lane_arrays(self.scenarios)[0])
+            self._lanes_set = True
+
+    def lane_observation(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf")):
+        """The lane-frame vector observation of the ego of every environment at the current state (sg_lane_observation):
+        (feat [R, k, 6 + 2 * n_ahead], lanes [R, k] positions in scenarios[i].road_network.lanes or -1, count [R]).  torch_obs:
+        torch tensors in HBM; else numpy arrays."""
+        self._set_lanes()
+        return self.engine.lane_observation(k, n_ahead, spacing, radius, torch_out=self.torch_obs)
+
+    def observe_entities_lanes(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf")):
+        """The lane-frame vector observation of every observer of set_observers at the current state
+        (sg_lane_observation_observers): (feat [n, k, 6 + 2 * n_ahead], lanes [n, k], count [n], env_of_observer [n], slot [n]).
+        torch_obs: torch tensors in HBM; else numpy arrays."""
+        self._set_lanes()
+        out = self.engine.lane_observation_observers(k, n_ahead, spacing, radius, torch_out=self.torch_obs)
         return tuple(out) + self._observer_index(out[0])
 
     def close(self):
