@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers) */
 
 typedef enum {
     SG_OK = 0,
@@ -522,6 +522,46 @@ int sg_lane_observation(sg_handle *h, int32_t k, int32_t n_ahead, double spacing
  * (feat may be NULL then). */
 int sg_lane_observation_observers(sg_handle *h, int32_t k, int32_t n_ahead, double spacing, double radius,
                                   double *feat, int32_t *lanes, int32_t *count, int32_t outputs_device);
+
+/* The range scan (lidar): a fan of n_rays beams from the pose point of the ego of every scenario (n = n_scenarios observers),
+ * each reporting the distance to the first other entity's box it meets and how fast that distance changes.  The reference
+ * has no such sensor (its RasterizedMapSensor is the image-shaped equivalent); the nearest-entity rows give reference points,
+ * not box surfaces, and know nothing of occlusion.  Plain fp64, IEEE division, nothing fused.
+ * The observer is slot so of scenario r with pose (xo, yo, ho), velocity (vxo, vyo) and (s, c) = sin, cos of ho.  Beam b in
+ * [0, n_rays) has the angle a_b = angle0 + (double)b * dangle from the observer's heading, (sb, cb) = sin, cos of a_b, and the
+ * world direction ux = cb*c - sb*s, uy = sb*c + cb*s.  Every OTHER slot e of r that is in State.poses (the presence rule of
+ * sg_nearest_entities), with pose (xe, ye, he), (se, ce) = sin, cos of he and box (W, L, cx, cy) = (width, length, center_x,
+ * center_y), is met in its own frame -- the inverse of the rotation Entity.get_bounding_box_points applies, so the same
+ * rectangle up to rounding:
+ *   dx = xo - xe, dy = yo - ye;  ox = dx*ce + dy*se, oy = dy*ce - dx*se;  lx = ux*ce + uy*se, ly = uy*ce - ux*se
+ *   x-slab: lo = cx - 0.5*L, hi = cx + 0.5*L against (ox, lx);  y-slab: lo = cy - 0.5*W, hi = cy + 0.5*W against (oy, ly)
+ *   slab (o, l, lo, hi): l == 0: (tn, tf) = (-inf, +inf) when o >= lo && o <= hi, else (+inf, -inf); otherwise t1 = (lo - o)/l,
+ *     t2 = (hi - o)/l, tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1
+ *   tmin = 0; if (tnx > tmin) tmin = tnx; if (tny > tmin) tmin = tny;  tmax = tfy < tfx ? tfy : tfx
+ *   e is hit iff tmin <= tmax && tmin <= max_range && tmin < +inf (inclusive; an origin inside or on a box gives 0; any NaN
+ *   gives no hit)
+ * The beam's hit is the smallest (tmin, slot) over the hit entities: ties in range go to the lower slot.
+ *   feat[o][b][0]  the range tmin; max_range (which may be +inf) without a hit
+ *   feat[o][b][1]  the range rate (vxe - vxo)*ux + (vye - vyo)*uy of the hit entity, negative when it closes along the beam;
+ *                  +0.0 without a hit
+ *   slots[o][b]    the hit slot, -1 without.  May be NULL
+ *   hits[o]        the number of beams that hit something.  May be NULL
+ * An observer that is not in State.poses gets hits -1, slots -1 and features +0.0.  Every byte of the outputs given is
+ * written.  feat: [n][n_rays][2] doubles, slots: [n][n_rays], hits: [n]; HOST (outputs_device == 0, synchronous, through the
+ * observation scratch) or DEVICE (queued on sg_stream(h), not waited for), as in sg_nearest_entities, and a persistent rollout
+ * launch that gave up is reported as there.  SG_ERR_INVALID: n_rays outside 1..SG_SCAN_MAX_RAYS, angle0 or dangle NaN or
+ * infinite, max_range NaN or negative, feat NULL.  SG_ERR_STATE before sg_upload.  A refused call writes nothing and leaves
+ * the handle working.  One wavefront per observer computes what a beam needs of an entity once per observer, 64 entities at a
+ * time, and runs 64 beams against them; any scenario width.  Not part of the sg_tick graph. */
+#define SG_SCAN_MAX_RAYS 1024
+int sg_range_scan(sg_handle *h, int32_t n_rays, double angle0, double dangle, double max_range, double *feat, int32_t *slots,
+                  int32_t *hits, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_range_scan for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_range_scan_observers(sg_handle *h, int32_t n_rays, double angle0, double dangle, double max_range, double *feat,
+                            int32_t *slots, int32_t *hits, int32_t outputs_device);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

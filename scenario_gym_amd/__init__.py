@@ -11,6 +11,7 @@ from .agent import (  # noqa: F401
     LaneSensor,
     NearestEntitiesSensor,
     PIDController,
+    RangeScanSensor,
     RasterizedMapSensor,
     ReplayTrajectoryController,
     Sensor,
@@ -29,7 +30,7 @@ from .agent import (  # noqa: F401
 from .engine import PackedScenarios, RolloutEngine  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
-    SingleEntityObservation,
+    RangeScanObservation, SingleEntityObservation,
     combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401

@@ -36,6 +36,7 @@ SYMBOLS = (
     "sg_set_observers", "sg_raster_map_observers", "sg_future_collision_observers",
     "sg_nearest_entities", "sg_nearest_entities_observers",
     "sg_set_lanes", "sg_lane_observation", "sg_lane_observation_observers",
+    "sg_range_scan", "sg_range_scan_observers",
 )
 
 
@@ -209,6 +210,8 @@ def load():
     lib.sg_set_lanes.argtypes = [H, C.POINTER(SgLanes)]
     lib.sg_lane_observation.argtypes = [H, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes
+    lib.sg_range_scan.argtypes = [H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_range_scan_observers.argtypes = lib.sg_range_scan.argtypes
     lib.sg_debug_trig32.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from .entity import Entity
-from .observation import (CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation,
+from .observation import (CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, RangeScanObservation,
                           NearestEntitiesObservation, SingleEntityObservation, combine_observations)
 from .scenario import Scenario
 
@@ -174,6 +174,26 @@ class LaneSensor(Sensor):
     def _step(self, state):
         lanes, features = state.lane_observation(self.k, self.n_ahead, self.spacing, self.radius, entity=self.entity)
         return LaneObservation(self.entity, *state.get_entity_data(self.entity), lanes, features)
+
+
+class RangeScanSensor(Sensor):
+    """A range scan (lidar) around the sensor's entity (no counterpart in the reference): n_rays beams from its pose point, beam
+    b at the angle angle0 + b * dangle from its heading (dangle None: 2 pi / n_rays, a full turn), each reporting the distance
+    to the first other entity's bounding box within max_range and the rate at which it changes, computed on the device for
+    the whole batch: sg_range_scan for the egos, one sg_range_scan_observers call for the sensors of all other entities."""
+
+    def __init__(self, entity: Entity, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0):
+        super().__init__(entity)
+        self.n_rays, self.angle0, self.max_range = int(n_rays), float(angle0), float(max_range)
+        self.dangle = None if dangle is None else float(dangle)
+
+    @property
+    def output_shape(self):
+        return (self.n_rays, 2)
+
+    def _step(self, state):
+        ranges, rates, hit = state.range_scan(self.n_rays, self.angle0, self.dangle, self.max_range, entity=self.entity)
+        return RangeScanObservation(self.entity, *state.get_entity_data(self.entity), ranges, rates, hit)
 
 
 class GlobalCollisionDetector(Sensor):

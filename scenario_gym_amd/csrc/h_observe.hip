@@ -1,5 +1,5 @@
-// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity and
-// lane-frame observations of the ego and of a list of observers.
+// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity,
+// lane-frame and range-scan observations of the ego and of a list of observers.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -339,4 +339,42 @@ extern "C" int sg_lane_observation_observers(sg_handle *h, int32_t k, int32_t n_
 {
     if (!h) return SG_ERR_INVALID;
     return lane_call(h, "sg_lane_observation_observers", true, k, n_ahead, spacing, radius, feat, lanes, count, outputs_device);
+}
+
+// ---- the range scan (range_scan_kernel, sgym_observers.hpp) ----------------------------------------------------------------
+// n observers as above.  Host outputs pass through the observation scratch: [n][n_rays][2] doubles, then [n][n_rays] slots, then
+// [n] hit counts (the last two only when asked for).
+static int scan_call(sg_handle *h, const char *who, bool observers, int32_t n_rays, double angle0, double dangle, double max_range, double *feat,
+                     int32_t *slots, int32_t *hits, int32_t outputs_device)
+{
+    if (n_rays < 1 || n_rays > SG_SCAN_MAX_RAYS) return fail(h, SG_ERR_INVALID, "%s: n_rays=%d outside 1..%d", who, n_rays, SG_SCAN_MAX_RAYS);
+    if (!std::isfinite(angle0) || !std::isfinite(dangle)) return fail(h, SG_ERR_INVALID, "%s: angle0 or dangle is infinite or NaN", who);
+    if (!(max_range >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: max_range is negative or NaN", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    const size_t nb = (size_t)n * n_rays;
+    return deliver(h, who, outputs_device, obs_scratch, {{feat, nb * 2 * sizeof(double)}, {slots, nb * sizeof(int32_t)}, {hits, (size_t)n * sizeof(int32_t)}}, 0,
+                   [&](void *const *d) {
+                       sgl::range_scan(h->stream, h->p, d_scen, d_slot, n, n_rays, angle0, dangle, max_range, static_cast<double *>(d[0]),
+                                       static_cast<int32_t *>(d[1]), static_cast<int32_t *>(d[2]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_range_scan(sg_handle *h, int32_t n_rays, double angle0, double dangle, double max_range, double *feat, int32_t *slots,
+                             int32_t *hits, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return scan_call(h, "sg_range_scan", false, n_rays, angle0, dangle, max_range, feat, slots, hits, outputs_device);
+}
+
+extern "C" int sg_range_scan_observers(sg_handle *h, int32_t n_rays, double angle0, double dangle, double max_range, double *feat,
+                                       int32_t *slots, int32_t *hits, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return scan_call(h, "sg_range_scan_observers", true, n_rays, angle0, dangle, max_range, feat, slots, hits, outputs_device);
 }

@@ -1,6 +1,6 @@
-// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel: the map, look-ahead,
-// nearest-entity and lane-frame observations of the ego of every scenario or of a list of observers (scenario, slot), any entity
-// of its scenario (sgym_observers.hpp).
+// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel: the map,
+// look-ahead, nearest-entity, lane-frame and range-scan observations of the ego of every scenario or of a list of observers
+// (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -45,5 +45,12 @@ void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L
     if (n <= 0) return;
     const double r2 = radius * radius; // (+inf for an infinite radius: every finite distance passes)
     sg::lane_observation_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, L, scen, slot, n, k, n_ahead, spacing, r2, feat, lanes, count);
+}
+
+void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_rays, double angle0, double dangle,
+                double max_range, double *feat, int32_t *slots, int32_t *hits)
+{
+    if (n <= 0) return;
+    sg::range_scan_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, n_rays, angle0, dangle, max_range, feat, slots, hits);
 }
 } // namespace sgl

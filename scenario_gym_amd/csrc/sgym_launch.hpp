@@ -64,6 +64,11 @@ void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int3
 // L: the rows of sg_set_lanes (L.seg == nullptr: none set).  One wavefront per observer.
 void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L, const int32_t *scen, const int32_t *slot, int64_t n, int k,
                       int n_ahead, double spacing, double radius, double *feat, int32_t *lanes, int32_t *count);
+// range_scan_kernel: n_rays <= SG_SCAN_MAX_RAYS beams from observer o < n (the same two lists) at angle0 + b * dangle from its
+// heading, each against the boxes of the other present entities up to max_range.  feat [n][n_rays][2] (range, range rate), slots
+// [n][n_rays] (or nullptr), hits [n] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
+void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_rays, double angle0, double dangle,
+                double max_range, double *feat, int32_t *slots, int32_t *hits);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -592,4 +592,110 @@ static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, 
 }
 #endif // SG_UNIT_OBS
 
+// ------------------------------------------------------------------------------------------------
+// The range scan: a fan of beams from an observer's pose point, each reporting the distance to the first other entity's box
+// it meets and how fast that distance changes (no counterpart in the reference, whose RasterizedMapSensor is the image-shaped
+// equivalent).  The definition is in include/sgym.h at sg_range_scan: a slab test of the beam in the entity's frame, plain
+// unfused fp64 with IEEE divisions.  (SG_SCAN_MAX_RAYS: include/sgym.h.)
+// ------------------------------------------------------------------------------------------------
+
+// what a beam needs of one entity, computed once per observer: the observer's position in the entity's frame, the box slabs
+// there, cos / sin of the entity's heading, its velocity relative to the observer's
+struct ScanRow {
+    double ox, oy, xlo, xhi, ylo, yhi, ce, se, dvx, dvy;
+};
+
+// one slab of the definition: the parameters at which o + t * l enters and leaves [lo, hi] (a beam along the slab is inside
+// for every t or for none)
+__device__ __forceinline__ void scan_slab(double o, double l, double lo, double hi, double &tn, double &tf)
+{
+    const double t1 = (lo - o) / l, t2 = (hi - o) / l;
+    const bool along = l == 0.0, inside = o >= lo && o <= hi, up = t1 < t2;
+    tn = along ? (inside ? -__builtin_inf() : __builtin_inf()) : (up ? t1 : t2);
+    tf = along ? (inside ? __builtin_inf() : -__builtin_inf()) : (up ? t2 : t1);
+}
+
+// Observer o < n as in nearest_kernel; feat [n][n_rays][2] (range, range rate), slots [n][n_rays] (may be nullptr), hits [n]
+// (may be nullptr), every byte written.  One wavefront per observer, four observers per workgroup, no barrier.  The scenario's
+// slots go by in blocks of 64, ascending, through the wavefront's own LDS rows:
+//   phase one, lane = entity: presence, sin / cos of its heading, the ScanRow -- once per observer and block of beams, not once
+//     per beam -- and whether any beam can reach the box at all: a hit needs both slabs entered by max_range, and with
+//     |l| <= 1 + a few ulp a slab whose two bounds lie on one side of the origin, both more than g away, is entered no sooner
+//     than g * (1 - 1e-15) or lies behind the beam; so g > max_range * (1 + 1e-9) on either axis rules the entity out, with
+//     the very subtractions the slab test divides (bounds in either order: extents may be negative).  A NaN keeps the entity in.
+//   phase two, lane = beam: the rows of the entities within reach, a wavefront-uniform bit mask walked upwards, read as LDS
+//     broadcasts; (best, slot, rate) with a strict <, so ascending slots give the tie rule with no cross-lane step.
+// More than 64 beams go block by block of 64, each with phase one anew (some hundred instructions beside 64 slab tests per row).
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void range_scan_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n, int n_rays,
+                                                                double angle0, double dangle, double max_range, double *feat, int32_t *slots,
+                                                                int32_t *hits)
+{
+    __shared__ ScanRow rows[4][64];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t o = (int64_t)blockIdx.x * 4 + w;
+    if (o >= n) return; // (the whole wavefront, which meets no barrier)
+    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    const double reach = max_range * 1.000000001;
+    int total = f.present ? 0 : -1;
+    for (int b0 = 0; b0 < n_rays; b0 += 64) {
+        const int b = b0 + lane;
+        double best = __builtin_inf(), rate = 0.0;
+        int slot = -1;
+        if (f.present) {
+            double sb, cb;
+            sg_sincos(angle0 + (double)b * dangle, sb, cb);
+            const double ux = cb * f.c - sb * f.s, uy = sb * f.c + cb * f.s;
+            for (int e0 = 0; e0 < p.E; e0 += 64) {
+                const int e = e0 + lane;
+                const bool other = e < p.E && e != f.slot; // (a lane without a slot reads the observer's own rows, which are there)
+                const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)(other ? e : f.slot);
+                const double *d = near_dyn(p, idx), *st = near_stat(p, idx);
+                ScanRow q;
+                sg_sincos(d[(SG_F_POSE + 3) * 64], q.se, q.ce);
+                const double dx = f.x - d[(SG_F_POSE + 0) * 64], dy = f.y - d[(SG_F_POSE + 1) * 64];
+                const double W = st[ST_BW * 64], L = st[ST_BL * 64], cx = st[ST_BCX * 64], cy = st[ST_BCY * 64];
+                q.ox = dx * q.ce + dy * q.se;
+                q.oy = dy * q.ce - dx * q.se;
+                q.xlo = cx - 0.5 * L; q.xhi = cx + 0.5 * L;
+                q.ylo = cy - 0.5 * W; q.yhi = cy + 0.5 * W;
+                q.dvx = d[(SG_F_VEL + 0) * 64] - f.vx;
+                q.dvy = d[(SG_F_VEL + 1) * 64] - f.vy;
+                const double x1 = q.xlo - q.ox, x2 = q.xhi - q.ox, y1 = q.ylo - q.oy, y2 = q.yhi - q.oy;
+                const bool out_of_reach = (x1 > reach && x2 > reach) || (x1 < -reach && x2 < -reach) || (y1 > reach && y2 > reach) ||
+                                          (y1 < -reach && y2 < -reach);
+                const bool present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
+                tile_sync<1>(); // (the previous block's rows have been read)
+                rows[w][lane] = q;
+                tile_sync<1>();
+                for (uint64_t todo = __ballot(other && present && !out_of_reach); todo; todo &= todo - 1) {
+                    const int j = __builtin_ctzll(todo);
+                    const ScanRow g = rows[w][j];
+                    const double lx = ux * g.ce + uy * g.se, ly = uy * g.ce - ux * g.se;
+                    double tnx, tfx, tny, tfy;
+                    scan_slab(g.ox, lx, g.xlo, g.xhi, tnx, tfx);
+                    scan_slab(g.oy, ly, g.ylo, g.yhi, tny, tfy);
+                    double tmin = 0.0;
+                    if (tnx > tmin) tmin = tnx;
+                    if (tny > tmin) tmin = tny;
+                    const double tmax = tfy < tfx ? tfy : tfx;
+                    const bool take = tmin <= tmax && tmin <= max_range && tmin < __builtin_inf() && tmin < best;
+                    best = take ? tmin : best;
+                    slot = take ? e0 + j : slot;
+                    rate = take ? g.dvx * ux + g.dvy * uy : rate;
+                }
+            }
+            total += __popcll(__ballot(b < n_rays && slot >= 0));
+        }
+        if (b < n_rays) {
+            double *row = feat + ((size_t)o * n_rays + b) * 2; // (16 bytes per lane, consecutive lanes consecutive beams)
+            row[0] = !f.present ? 0.0 : slot >= 0 ? best : max_range;
+            row[1] = rate;
+            if (slots) slots[(size_t)o * n_rays + b] = slot;
+        }
+    }
+    if (lane == 0 && hits) hits[o] = total;
+}
+#endif // SG_UNIT_OBS
+
 } // namespace sg

@@ -380,7 +380,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -487,6 +487,31 @@ class RolloutEngine:
         """lane_observation for every observer of set_observers (sg_lane_observation_observers): (feat [n, k, 6 + 2 * n_ahead],
         lanes [n, k], count [n]); empty arrays when no observers are set."""
         return self._lane_observation(self.lib.sg_lane_observation_observers, self._n_obs, k, n_ahead, spacing, radius, torch_out)
+
+    def _range_scan(self, call, n, n_rays, angle0, dangle, max_range, torch_out):
+        n_rays = int(n_rays)
+        dangle = 2.0 * np.pi / max(n_rays, 1) if dangle is None else float(dangle)  # (n_rays < 1 is the library's to refuse)
+        outs, ptrs = self._outputs(torch_out, ((n, max(n_rays, 0), 2), "float64"), ((n, max(n_rays, 0)), "int32"), ((n,), "int32"))
+        self._check(call(self.h, n_rays, float(angle0), dangle, float(max_range), *ptrs, int(bool(torch_out))), call.__name__)
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
+
+    def range_scan(self, n_rays=64, angle0=-np.pi, dangle=None, max_range=100.0, torch_out=False):
+        """The range scan of the ego of every scenario (sg_range_scan): n_rays <= 1024 beams from the ego's pose point, beam b at
+        the angle angle0 + b * dangle from its heading (dangle None: 2 pi / n_rays, a full turn), each against the bounding
+        boxes of the other entities that are in the scene.  Returns (feat [R, n_rays, 2] float64, slots [R, n_rays] int32, hits
+        [R] int32): per beam the distance to the first box it meets within max_range (inclusive; 0 from inside a box;
+        max_range, which may be inf, without a hit) and the rate at which that distance changes -- the hit entity's velocity
+        relative to the ego's along the beam, negative when it closes, 0 without a hit; slots: the hit entity or -1; hits: the
+        beams that hit something, -1 for an ego that is not in the scene (features 0, slots -1).  torch_out: torch tensors in
+        HBM the kernel writes directly (waited for, as in raster_map_observers)."""
+        return self._range_scan(self.lib.sg_range_scan, self.R, n_rays, angle0, dangle, max_range, torch_out)
+
+    def range_scan_observers(self, n_rays=64, angle0=-np.pi, dangle=None, max_range=100.0, torch_out=False):
+        """range_scan for every observer of set_observers (sg_range_scan_observers): (feat [n, n_rays, 2], slots [n, n_rays],
+        hits [n]); empty arrays when no observers are set."""
+        return self._range_scan(self.lib.sg_range_scan_observers, self._n_obs, n_rays, angle0, dangle, max_range, torch_out)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

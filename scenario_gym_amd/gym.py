@@ -12,7 +12,8 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .agent import CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RasterizedMapSensor, _create_agent
+from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RangeScanSensor, RasterizedMapSensor,
+                    _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_scenarios
@@ -290,7 +291,7 @@ class BatchedScenarioGym:
         for i, sc in enumerate(self.scenarios):
             for a in agents[i].values():
                 for s in leaves(getattr(a, "sensor", None)):
-                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor, RangeScanSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
                         self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
@@ -359,6 +360,12 @@ class BatchedScenarioGym:
         """(feat [n, k, 8], slots [n, k], count [n]) of NearestEntitiesSensor."""
         call = self.engine.nearest_entities_observers if observers else self.engine.nearest_entities
         return self._cached(("near", observers, k, radius), lambda: call(k, radius), observers=observers)
+
+    def _range_scan(self, observers: bool, n_rays: int, angle0: float, dangle: Optional[float], max_range: float):
+        """(feat [n, n_rays, 2], slots [n, n_rays], hits [n]) of RangeScanSensor."""
+        call = self.engine.range_scan_observers if observers else self.engine.range_scan
+        return self._cached(("scan", observers, n_rays, angle0, dangle, max_range), lambda: call(n_rays, angle0, dangle, max_range),
+                            observers=observers)
 
     def _set_lanes(self):
         """The lane centre lines of every scenario's road network -> the device (behind the networks themselves, whose

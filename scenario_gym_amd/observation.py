@@ -72,6 +72,18 @@ class LaneObservation(SingleEntityObservation):
     lane_features: np.ndarray
 
 
+@dataclass
+class RangeScanObservation(SingleEntityObservation):
+    """The range scan (no counterpart in the reference): per beam of the sensor's fan `ranges`, the distance from the entity's
+    pose point to the first other entity's bounding box (the sensor's max_range without a hit, 0 from inside a box),
+    `range_rates`, the rate at which that distance changes (negative when the hit entity closes along the beam, 0 without a
+    hit), and `hit_entities`, that entity or None."""
+
+    ranges: np.ndarray
+    range_rates: np.ndarray
+    hit_entities: list
+
+
 def combine_observations(*classes, prefixes: Optional[Sequence[Optional[str]]] = None):
     """observation.py:31-84: a dataclass holding the fields of all `classes` in order.  A field name that an earlier class
     already contributed is skipped -- or, with `prefixes` (one per class), taken as "<prefix>_<name>"; a name that is still

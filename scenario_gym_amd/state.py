@@ -213,6 +213,19 @@ class State:
         ents = self._scenario.entities
         return [ents[j] for j in slots[row] if j >= 0], feat[row].copy()
 
+    def range_scan(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0,
+                   entity: Optional[Entity] = None):
+        """RangeScanSensor(entity, n_rays, angle0, dangle, max_range) at the current state, computed on the device: (ranges
+        [n_rays], range_rates [n_rays], hit_entities) -- per beam from the pose point of `entity` (any entity of the scenario,
+        default the ego), at the angle angle0 + b * dangle from its heading (dangle None: 2 pi / n_rays), the distance to the
+        first other entity's bounding box within max_range (max_range without a hit), the rate at which it changes, and that
+        entity (None without a hit).  (zeros, zeros, Nones) for an entity that is not in `poses`."""
+        observers, row = self._sensor_row(entity)
+        feat, slots, _ = self._gym._range_scan(observers, int(n_rays), float(angle0), None if dangle is None else float(dangle),
+                                               float(max_range))
+        ents = self._scenario.entities
+        return feat[row, :, 0].copy(), feat[row, :, 1].copy(), [ents[j] if j >= 0 else None for j in slots[row]]
+
     def lane_observation(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf"),
                          entity: Optional[Entity] = None):
         """LaneSensor(entity, k, n_ahead, spacing, radius) at the current state, computed on the device: (lanes, features) -- the

@@ -140,6 +140,19 @@ class VectorScenarioEnv:
         out = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
         return tuple(out) + self._observer_index(out[0])
 
+    def range_scan(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0):
+        """The range scan of the ego of every environment at the current state (sg_range_scan): (feat [R, n_rays, 2] range and
+        range rate per beam, slots [R, n_rays] positions in scenarios[i].entities or -1, hits [R]).  torch_obs: torch tensors in
+        HBM; else numpy arrays."""
+        return self.engine.range_scan(n_rays, angle0, dangle, max_range, torch_out=self.torch_obs)
+
+    def observe_entities_ranges(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0):
+        """The range scan of every observer of set_observers at the current state (sg_range_scan_observers): (feat
+        [n, n_rays, 2], slots [n, n_rays], hits [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else
+        numpy arrays."""
+        out = self.engine.range_scan_observers(n_rays, angle0, dangle, max_range, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
+
     def _set_lanes(self):
         if not self._lanes_set:
             self.engine.set_lanes(shared_lane_arrays(self.scenarios)[0])
