@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers) */
 
 typedef enum {
     SG_OK = 0,
@@ -336,6 +336,46 @@ int sg_step(sg_handle *h, int32_t n_steps, const double *actions, int32_t action
  * present yet spawns at its trajectory start like every other agent (:240-244).  sg_rollout refuses batches with such
  * slots (SG_ERR_STATE): they have to be driven tick by tick. */
 int sg_set_external_poses(sg_handle *h, const double *poses);
+
+/* Per-entity vehicle actions: the drivers.  The reference gives any number of entities of one scenario an agent with a
+ * VehicleController (controller.py:57-140, create_agents scenario_gym.py:188-211); sg_step's actions are one pair per scenario.
+ * A driver is an SG_KIND_AGENT_EXTERNAL slot whose pose the DEVICE produces: sg_step_drivers runs VehicleController._step for it
+ * from its own (accel, steer) and puts the result where sg_set_external_poses would have put it.  Driver k is entity slot slot[k]
+ * of scenario scenario[k]; its controller parameters are the slot's row of sg_scenarios.ctrl (SG_C_MAX_STEER, SG_C_MAX_ACCEL,
+ * SG_C_MAX_SPEED, SG_C_ALLOW_REVERSE), its wheel base the slot's bounding-box length, as for SG_KIND_AGENT_VEHICLE.
+ * HOST arrays [n], copied once into a device list the handle owns; the order is the caller's and is the order of the actions.
+ * n == 0 clears the list.  The list holds until it is replaced, cleared or sg_upload (which forgets it, as it forgets the
+ * observers); sg_reset / sg_reset_scenarios / sg_step keep it.  SG_ERR_STATE before sg_upload.  SG_ERR_INVALID: n < 0, a NULL
+ * array with n > 0, a scenario outside [0, n_scenarios), a slot outside [0, n_entities), a slot whose kind is not
+ * SG_KIND_AGENT_EXTERNAL, a (scenario, slot) pair listed twice.  A refused call leaves the previous list in place.  Setting a
+ * list waits for the work queued on sg_stream(h) first. */
+int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot);
+
+/* n_steps x ScenarioGym.step() on every scenario, done or not, with the drivers' controllers run on the device.
+ * actions: [n_steps][n_drivers][2] (accel, steer) in list order, HOST (copied into a buffer of the handle; the caller's buffer is
+ * free on return) or, with actions_device != 0, a DEVICE pointer of the same shape; NULL: (0, 0) for every driver.  Nothing
+ * beyond n_steps * n_drivers * 2 doubles is read.  For each step k, in this order on sg_stream(h):
+ *   1. one lane per driver d = (r, slot), (a, s) = actions[k][d], t = sg_scenario_state.t of r, next_t = t + timestep,
+ *      dt = next_t - t (the clock arithmetic of the step itself).
+ *      The slot is not in State.poses (SG_F_PRESENT == 0): its external-pose row becomes NaN and its controller speed stays; the
+ *      step spawns it at its trajectory start like every other agent (scenario_gym.py:240-244).
+ *      Otherwise, with pose = its SG_F_POSE rows, speed = its SG_F_CTRL + 0 cell, l = its box length, (sin_h, cos_h) of pose[3]
+ *      and the parameters of its ctrl row -- VehicleController._step, plain fp64, nothing fused:
+ *        a = min(max(a, -max_accel), max_accel);  s = min(max(s, -max_steer), max_steer)
+ *        x += (speed * cos_h) * dt;  y += (speed * sin_h) * dt;  h += (speed * tan(s) / l) * dt;  z, pitch, roll stay
+ *        speed = speed + a * dt;  allow_reverse == 0: speed = max(0, speed);  max_speed not NaN: speed = min(max_speed, speed)
+ *      the pose goes to the slot's external-pose row, the speed back to SG_F_CTRL + 0.  The same function, bit for bit, as an
+ *      SG_KIND_AGENT_VEHICLE lane steps with under sg_step.  The resets write `present ? |velocity at t0| : 0` into that cell for
+ *      every kind (Controller.reset, controller.py:100-103), so sg_reset / sg_reset_scenarios restart a driver's speed.
+ *   2. the step of sg_step(h, 1, NULL, 0): forced, the RSS callback as sg_set_rss has it, whatever kernel family the batch takes
+ *      (scenarios of more than 512 entities included).  It consumes the drivers' rows as it consumes those of
+ *      sg_set_external_poses; SG_KIND_AGENT_VEHICLE slots of the batch get (0, 0); SG_KIND_AGENT_EXTERNAL slots that are not
+ *      drivers keep the pose sg_set_external_poses gave them.
+ * The call waits for the stream once, at its end, as sg_step does.  A driver that is the hazard of an ego collision event is
+ * reported like every caller-run agent (sg_event.type -2: unclassified).  SG_ERR_STATE before sg_upload or without a driver list;
+ * SG_ERR_INVALID: n_steps < 1.  One short launch ahead of every step; not part of the sg_tick graph (sg_tick and sg_rollout
+ * keep refusing batches with SG_KIND_AGENT_EXTERNAL slots). */
+int sg_step_drivers(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device);
 
 /* ScenarioGym.rollout(): reset, then step each scenario while it is not done, at most max_steps
  * (scenario_gym.py:256-267).  The time loop runs inside the kernels: one launch for short runs; long runs of batches with

@@ -37,6 +37,7 @@ SYMBOLS = (
     "sg_nearest_entities", "sg_nearest_entities_observers",
     "sg_set_lanes", "sg_lane_observation", "sg_lane_observation_observers",
     "sg_range_scan", "sg_range_scan_observers",
+    "sg_set_drivers", "sg_step_drivers",
 )
 
 
@@ -212,7 +213,9 @@ def load():
     lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes
     lib.sg_range_scan.argtypes = [H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_range_scan_observers.argtypes = lib.sg_range_scan.argtypes
-    lib.sg_debug_trig32.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sg_set_drivers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.sg_step_drivers.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
+    lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)
             getattr(lib, name).restype = C.c_int

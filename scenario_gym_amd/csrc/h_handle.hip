@@ -154,6 +154,8 @@ extern "C" int sg_destroy(sg_handle *h)
     h->obs.release();
     h->road_info.release();
     h->observers.release();
+    h->drivers.release();
+    h->drv_actions.release();
     if (h->d_reset_mask) (void)hipFree(h->d_reset_mask);
     h->term_flags.release();
     if (h->d_rss_state) (void)hipFree(h->d_rss_state);

@@ -147,6 +147,7 @@ static void forget_batch(sg_handle *h)
     h->road = sg::RoadIndex{};
     h->geom = sg::RoadGeom{};
     h->n_obs = 0; // the observers are slots of a batch
+    h->n_drv = 0; // ... and so are the drivers
     h->uploaded = false; // (the controller table buffers stay: launch_rollout regrows them when the new batch needs more)
     h->ego_first = true;
     ++h->generation;
@@ -162,8 +163,10 @@ static int classify_batch(sg_handle *h, const sg_scenarios *sc)
     h->all_ped = true;
     h->sliceable = true;
     h->slot_empty.resize((size_t)h->R * h->E);
+    h->slot_external.resize((size_t)h->R * h->E);
     for (size_t i = 0; i < (size_t)h->R * h->E; ++i) {
         h->slot_empty[i] = sc->kind[i] == SG_KIND_NONE;
+        h->slot_external[i] = sc->kind[i] == SG_KIND_AGENT_EXTERNAL;
         h->sliceable = h->sliceable && (sc->kind[i] == SG_KIND_NONE || sc->kind[i] == SG_KIND_REPLAY || sc->kind[i] == SG_KIND_AGENT_REPLAY ||
                                         sc->kind[i] == SG_KIND_AGENT_PID || sc->kind[i] == SG_KIND_AGENT_VEHICLE);
         h->has_ped = h->has_ped || sc->kind[i] == SG_KIND_AGENT_PEDESTRIAN;

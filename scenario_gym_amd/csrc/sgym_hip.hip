@@ -240,6 +240,21 @@ int sgh::rss_fused_call(sg_handle *h, bool live_only, bool *fused, bool *fresh)
 // room for n doubles of actions (n is 0 or at least R * 2); callers that hand the address to a graph bump `generation` on *grew
 int sgh::ensure_actions(sg_handle *h, size_t n, bool *grew) { return h->actions.ensure(h, n * sizeof(double), grew); }
 
+// the stepping of sg_step, and of every step of sg_step_drivers (h_drive.hip): forced steps, the RSS callback as the handle has it
+int sgh::step_forced(sg_handle *h, int n_steps, const double *d_act)
+{
+    bool fused = false;
+    int rc = rss_fused_call(h, true, &fused);
+    if (rc) return rc;
+    if (h->rss_enabled && !fused) { // (no records of this batch yet, or the ego is not entity 0) one step per launch
+        for (int k = 0; k < n_steps && !rc; ++k)
+            if (!(rc = launch_rollout(h, 1, 0, 1, d_act + (size_t)k * h->R * 2))) rc = sg_rss_update(h, 0);
+    } else {
+        rc = launch_rollout(h, n_steps, 0, 1, d_act, fused);
+    }
+    return rc;
+}
+
 extern "C" int sg_step(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device)
 {
     if (!h) return SG_ERR_INVALID;
@@ -261,16 +276,7 @@ extern "C" int sg_step(sg_handle *h, int32_t n_steps, const double *actions, int
         if (n) HIP_TRY(h, hipMemsetAsync(h->actions.ptr, 0, n * sizeof(double), h->stream));
         d_act = h->actions.as<double>();
     }
-    bool fused = false;
-    int rc = rss_fused_call(h, true, &fused);
-    if (rc) return rc;
-    if (h->rss_enabled && !fused) { // (no records of this batch yet, or the ego is not entity 0) one step per launch
-        for (int k = 0; k < n_steps && !rc; ++k)
-            if (!(rc = launch_rollout(h, 1, 0, 1, d_act + (size_t)k * h->R * 2))) rc = sg_rss_update(h, 0);
-    } else {
-        rc = launch_rollout(h, n_steps, 0, 1, d_act, fused);
-    }
-    if (rc) return rc;
+    if (const int rc = step_forced(h, n_steps, d_act)) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return check_queue(h);
 }

@@ -1,7 +1,7 @@
 // sgym_host.hpp -- what the host units of libsgym_hip.so share (private: the public side is include/sgym.h).
 // The handle, the error and allocation helpers, and the declarations of the few internal functions that cross unit
 // boundaries (namespace sgh).  The units: sgym_hip.hip (the dispatcher and the stepping entry points), h_handle.hip, h_upload.hip,
-// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_read.hip, h_group.hip.  None of them holds a
+// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_drive.hip, h_read.hip, h_group.hip.  None of them holds a
 // kernel: they launch through sgym_launch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -197,6 +197,13 @@ struct sg_handle {
     sgh::GrowBuf observers{sgh::GrowBuf::DEVICE};      // sg_set_observers: [2][capacity] int32_t, scenario and slot of every observer (grown on demand)
     int64_t n_obs = 0;                                 // observers set (0: none); sg_upload forgets them
 
+    // ---- h_drive.hip: the drivers ----
+    std::vector<uint8_t> slot_external;                // [R * E] the slot is SG_KIND_AGENT_EXTERNAL in the uploaded batch (what sg_set_drivers asks for)
+    sgh::GrowBuf drivers{sgh::GrowBuf::DEVICE};        // sg_set_drivers: [2][capacity] int32_t, scenario and slot of every driver (grown on demand)
+    int64_t n_drv = 0;                                 // drivers set (0: none); sg_upload forgets them
+    sgh::GrowBuf drv_actions{sgh::GrowBuf::DEVICE};    // host actions of sg_step_drivers ([n_steps][n_drv][2] doubles): not `actions`, whose
+                                                       // address the captured tick graph holds
+
     // ---- h_read.hip ----
     // page-locked staging of sg_read_metrics (the per-scenario state and the event table travel every time metrics are read:
     // 0.5 + up to 6 MB for 4096 scenarios; pageable copies ran at a third of the PCIe rate)
@@ -390,6 +397,9 @@ int launch_main(sg_handle *h, const LaunchPlan &pl, Fam fam, int n_steps, int do
 int rss_fused_call(sg_handle *h, bool live_only, bool *fused, bool *fresh = nullptr);
 int get_event(sg_handle *h, size_t idx, hipEvent_t *out);
 int ensure_actions(sg_handle *h, size_t n, bool *grew = nullptr); // room for n doubles in h->actions
+// n_steps forced steps of the whole batch with the per-scenario actions d_actions ([n_steps][R][2], DEVICE), enqueued, not waited
+// for: what sg_step does between its argument handling and its wait (the RSS callback fused or as a call of its own per step)
+int step_forced(sg_handle *h, int n_steps, const double *d_actions);
 // sg_last_kernel of the schedules that launch from other units (every name the handle can report is written in sgym_hip.hip)
 void note_wide(sg_handle *h);
 void note_queue(sg_handle *h, bool rss);

@@ -69,6 +69,12 @@ void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L
 // [n][n_rays] (or nullptr), hits [n] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
 void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_rays, double angle0, double dangle,
                 double max_range, double *feat, int32_t *slots, int32_t *hits);
+// k_drive.hip (sgym_drive.hpp): drive_kernel, one lane per driver d < n: the VehicleController step of entity (scen[d], slot[d]) with
+// actions[d] = (accel, steer) (nullptr: (0, 0)) from its current pose, into row (scen[d] * EP + slot[d]) of ext, the handle's
+// external-pose buffer [NE][6] -- NaN for a driver that is not in the scene; the controller speed in the slot's SG_F_CTRL + 0 cell.
+// All pointers DEVICE.
+void drive(hipStream_t s, const sg::Params &p, double timestep, const int32_t *scen, const int32_t *slot, int64_t n, const double *actions,
+           double *ext);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

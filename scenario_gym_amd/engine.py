@@ -124,6 +124,7 @@ class RolloutEngine:
         self._view = None
         self._keep = None
         self._n_obs = 0  # observers set (set_observers)
+        self._n_drv = 0  # drivers set (set_drivers)
         if social_force is not None and "models" in social_force:  # per-agent models (BatchedScenarioGym)
             self.set_ped_models(social_force["models"], social_force.get("model_of"), noise=social_force.get("noise"),
                                 noise_seed=social_force.get("noise_seed", 0), normals=social_force.get("normals"))
@@ -265,6 +266,7 @@ class RolloutEngine:
         )
         sc = L.SgScenarios(*[None if arrs[n] is None else arrs[n].ctypes.data for n, _ in L.SgScenarios._fields_])
         self._n_obs = 0  # (sg_upload forgets the observers)
+        self._n_drv = 0  # (... and the drivers)
         self._check(self.lib.sg_upload(self.h, C.byref(sc)), "sg_upload")
         self._view = L.SgStateView()
         self._check(self.lib.sg_state_view_get(self.h, C.byref(self._view)), "sg_state_view_get")
@@ -285,6 +287,35 @@ class RolloutEngine:
         """Poses [R, E, 6] of the caller-run agents (KIND_AGENT_EXTERNAL slots; NaN x = the agent returned None)."""
         poses = np.ascontiguousarray(poses, np.float64).reshape(self.R, self.E, 6)
         self._check(self.lib.sg_set_external_poses(self.h, poses.ctypes.data), "sg_set_external_poses")
+
+    def set_drivers(self, scenario, slot):
+        """sg_set_drivers: the policy-driven vehicles of step_drivers -- driver k is entity slot slot[k] of scenario
+        scenario[k], a KIND_AGENT_EXTERNAL slot whose VehicleController (its ctrl row) the device runs itself.  Any number per
+        scenario, no pair twice; the order is the order of the actions.  An empty list clears it; upload() forgets it; a
+        refused list leaves the previous one in place."""
+        scen = np.ascontiguousarray(scenario, np.int32).ravel()
+        slot = np.ascontiguousarray(slot, np.int32).ravel()
+        if scen.shape != slot.shape:
+            raise ValueError("set_drivers: scenario and slot must have the same length")
+        self._check(self.lib.sg_set_drivers(self.h, len(scen), scen.ctypes.data if len(scen) else None,
+                                            slot.ctypes.data if len(scen) else None), "sg_set_drivers")
+        self._n_drv = len(scen)
+
+    def step_drivers(self, actions=None, n=1):
+        """n x ScenarioGym.step() with the drivers' controllers run on the device (sg_step_drivers): actions [n, n_drivers, 2]
+        (accel, steer) in the order of set_drivers -- numpy, a float64 torch tensor on the device, or None for (0, 0)."""
+        n, nd = int(n), getattr(self, "_n_drv", 0)
+        ptr, on_device = None, 0
+        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
+            import torch
+
+            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * nd * 2
+            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
+            ptr, on_device = actions.data_ptr(), 1
+        elif actions is not None:
+            actions = np.ascontiguousarray(actions, np.float64).reshape(n, nd, 2)
+            ptr = actions.ctypes.data
+        self._check(self.lib.sg_step_drivers(self.h, n, ptr, on_device), "sg_step_drivers")
 
     def future_collision(self, horizon=5.0, n_samples=10):
         """FutureCollisionDetector (sensor/common.py:59-106) for the ego of every scenario at the current time: bool [R]."""

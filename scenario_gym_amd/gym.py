@@ -16,7 +16,7 @@ from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, Nearest
                     _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
-from .packing import pack_scenarios
+from .packing import pack_policy_drivers, pack_scenarios
 from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
 from .state import State
@@ -44,6 +44,7 @@ class BatchedScenarioGym:
         self.scenarios: List[Scenario] = []
         self._host_agents: list = []
         self._policy_agents: list = []
+        self._driver_agents: list = []  # (scenario index, entity slot, agent): several policy agents in one scenario (engine.set_drivers)
         self.states: List[State] = []
         self.metrics: List[List[Metric]] = []
         self._cache = None
@@ -72,7 +73,7 @@ class BatchedScenarioGym:
     def _per_step_host_path(self) -> bool:
         custom_metric = any(not isinstance(m, _DeviceMetric) for ms in self.metrics for m in ms)
         return bool(custom_metric or self._host_callbacks or self._host_terminals() or self._host_agents
-                    or self._policy_agents or self._custom_actions())
+                    or self._policy_agents or self._driver_agents or self._custom_actions())
 
     def _custom_actions(self) -> bool:
         """Some scenario carries an action whose trigger / effect is the caller's own code (not one of the time-triggered
@@ -118,7 +119,23 @@ class BatchedScenarioGym:
                 if agent.entity in st.poses:
                     a = agent.host_action(st)
                     actions[0, i] = (a.acceleration, a.steering)
+        if self._driver_agents:
+            if actions is not None:
+                raise NotImplementedError("per-scenario actions (ExternalVehicleAgent) beside several policy agents in one scenario")
+            self._driver_actions = np.zeros((1, len(self._driver_agents), 2))
+            for k, (i, _, agent) in enumerate(self._driver_agents):
+                st = self.states[i]
+                if agent.entity in st.poses:
+                    a = agent.host_action(st)
+                    self._driver_actions[0, k] = (a.acceleration, a.steering)
         return actions
+
+    def _device_step(self, actions):
+        """One tick on the device with what _push_host_agents prepared: through the driver list when the batch has one."""
+        if self._driver_agents:
+            self.engine.step_drivers(self._driver_actions, 1)
+        else:
+            self.engine.step(1, actions)
 
     # ------------------------------------------------------------------ set up
     @classmethod
@@ -192,7 +209,7 @@ class BatchedScenarioGym:
                 self.engine.set_rss(True)
         self.engine.upload(packed)
         self._packed = packed
-        self.scenarios, self.states, self._host_agents, self._policy_agents = [], [], [], []
+        self.scenarios, self.states, self._host_agents, self._policy_agents, self._driver_agents = [], [], [], [], []
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
         self._roads_set, self._lanes_set = True, False
         self.metrics = [list(self.metric_factory()) for _ in range(packed.n_scenarios)]
@@ -208,6 +225,10 @@ class BatchedScenarioGym:
 
         _t = _time.perf_counter()
         packed, agents = pack_scenarios(self.scenarios, create_agent)
+        # Python policies over the device VehicleController.  At most one per scenario: the action array of sg_step carries one
+        # (accel, steer) per scenario.  Several in some scenario: every one of the batch is a driver (sg_set_drivers), its
+        # controller stepped by the device from its own action (sg_step_drivers)
+        policies, several = pack_policy_drivers(packed, self.scenarios, agents)
         self._timings = {"pack": _time.perf_counter() - _t}
         self._packed = packed
         horizon = float(np.max(packed.length - packed.t0))
@@ -269,11 +290,10 @@ class BatchedScenarioGym:
         from . import _lib as L
         self._host_agents = [(i, sc.entities.index(e), a) for i, sc in enumerate(self.scenarios)
                              for e, a in agents[i].items() if a.device_kind() == L.KIND_AGENT_EXTERNAL]
-        # a Python policy over the device VehicleController: the action array carries one (accel, steer) per scenario
-        self._policy_agents = [(i, a) for i, sc in enumerate(self.scenarios) for e, a in agents[i].items()
-                               if a.device_kind() == L.KIND_AGENT_VEHICLE and getattr(a, "host_action", None) is not None]
-        if len({i for i, _ in self._policy_agents}) != len(self._policy_agents):
-            raise NotImplementedError("one external-action vehicle agent per scenario (sg_step actions are [n][R][2])")
+        self._policy_agents = [] if several else [(i, a) for i, _, a in policies]
+        self._driver_agents = policies if several else []
+        if self._driver_agents:
+            self.engine.set_drivers([i for i, _, _ in policies], [slot for _, slot, _ in policies])
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
@@ -451,6 +471,8 @@ class BatchedScenarioGym:
             agent.reset(self.states[i])
         for i, agent in self._policy_agents:
             agent.reset(self.states[i])
+        for i, _, agent in self._driver_agents:
+            agent.reset(self.states[i])
         for st, ms in zip(self.states, self.metrics):
             for m in ms:
                 m.reset(st)
@@ -487,7 +509,9 @@ class BatchedScenarioGym:
             before = self._prev_state
             if n == 1:
                 actions = self._push_host_agents(actions)
-            self.engine.step(n, actions)
+                self._device_step(actions)
+            else:
+                self.engine.step(n, actions)
             self._invalidate()
             if self._per_step_host_path():
                 self._after_host_step()
@@ -527,7 +551,7 @@ class BatchedScenarioGym:
             for _ in range(max_steps):
                 # a scenario that finished keeps stepping on the device but is frozen for the caller
                 self._prev_state = self._fetch_state()
-                self.engine.step(1, self._push_host_agents(None))
+                self._device_step(self._push_host_agents(None))
                 self._invalidate()
                 done |= self._after_host_step() | self._fetch_state()["done"]
                 if done.all():

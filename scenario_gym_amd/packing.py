@@ -135,6 +135,21 @@ def pack_scenarios(scenarios, create_agent=None):
     return packed, agents
 
 
+def pack_policy_drivers(packed: PackedScenarios, scenarios, agents):
+    """The Python-policy agents over the built-in VehicleController of a batch pack_scenarios packed, as (scenario, slot, agent)
+    in scenario and entity order.  When some scenario has more than one of them, every one of the batch becomes a
+    KIND_AGENT_EXTERNAL slot -- its ctrl row is already its controller's -- to be registered as a driver
+    (RolloutEngine.set_drivers); returns (the list, whether that was done).  At most one per scenario: nothing is changed."""
+    E = packed.n_entities
+    found = [(i, sc.entities.index(e), a) for i, sc in enumerate(scenarios) for e, a in agents[i].items()
+             if a.device_kind() == L.KIND_AGENT_VEHICLE and getattr(a, "host_action", None) is not None]
+    several = len({i for i, _, _ in found}) != len(found)
+    if several:
+        for i, slot, _ in found:
+            packed.kind[i * E + slot] = L.KIND_AGENT_EXTERNAL
+    return found, several
+
+
 def _file_arrays(path: str, relabel: bool):
     """One OpenSCENARIO file as the arrays pack_arrays takes -- what import_scenario + pack_scenarios produce for it with the
     reference's default agents (the ego replays its trajectory as an agent, everybody else through the batch path), without a

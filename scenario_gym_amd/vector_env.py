@@ -9,13 +9,18 @@ max_accel=5.0)` and `MapOnlySensor(channels_first=True, height=30, width=30, n=1
 otherwise (:300-310).  `VectorScenarioEnv` is that loop for R scenarios at once: one `sg_tick` per tick (the step with the
 [R, 2] actions, the terminal conditions and the map observation replayed as one captured hipGraph) and
 `sg_reset_scenarios` for the environments whose episode ended.  No arithmetic of the environment runs on the host.
+
+`drivers=`: several policy-driven vehicles per environment (the reference accepts any number of agents with a
+VehicleController in one scenario).  Every listed entity is a driver of the engine (`sg_set_drivers`); a tick is
+`sg_step_drivers` with one (acceleration, steering) per driver, then `sg_terminal_flags`; the observations are those of the
+observer list, which the drivers form by default.
 """
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib as L
-from .agent import ExternalVehicleAgent
+from .agent import ExternalVehicleAgent, ReplayTrajectoryAgent
 from .engine import RolloutEngine, terminal_mask
 from .packing import pack_scenarios
 from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
@@ -26,7 +31,10 @@ class VectorScenarioEnv:
     def __init__(self, scenarios: Sequence[Scenario], timestep: float = 0.1,
                  terminal_conditions: Optional[Sequence[str]] = None, layers: Optional[Sequence[str]] = None,
                  height: float = 30.0, width: float = 30.0, n: int = 128, max_steer: float = 0.9, max_accel: float = 5.0,
-                 auto_reset: bool = True, torch_obs: bool = False, device: int = 0):
+                 auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
+                 drivers: Optional[Sequence[Sequence[int]]] = None):
+        """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
+        VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -35,11 +43,25 @@ class VectorScenarioEnv:
         self.height, self.width, self.n = float(height), float(width), int(n)
         self.auto_reset, self.torch_obs = auto_reset, torch_obs
 
+        if drivers is not None and len(drivers) != len(self.scenarios):
+            raise ValueError("drivers: one list of entity indices per environment")
+
         def create_agent(scenario, entity):  # openaigym.py:280-293: the ego is driven by the policy
             if entity is scenario.ego:
-                return ExternalVehicleAgent(entity, max_steer=max_steer, max_accel=max_accel)
+                if drivers is None:
+                    return ExternalVehicleAgent(entity, max_steer=max_steer, max_accel=max_accel)
+                return ReplayTrajectoryAgent(entity)  # (unless it is listed, below: the reference's default agent)
 
         packed, _ = pack_scenarios(self.scenarios, create_agent)
+        self._drv_env = self._drv_slot = None
+        if drivers is not None:
+            # the driven slots: caller-run slots whose VehicleController the device steps itself (sg_set_drivers)
+            self._drv_env = np.array([i for i, ks in enumerate(drivers) for _ in ks], np.int32)
+            self._drv_slot = np.array([int(k) for ks in drivers for k in ks], np.int32)
+            for i, k in zip(self._drv_env, self._drv_slot):
+                agent = ExternalVehicleAgent(self.scenarios[i].entities[k], max_steer=max_steer, max_accel=max_accel)
+                packed.kind[int(i) * packed.n_entities + int(k)] = L.KIND_AGENT_EXTERNAL
+                packed.ctrl[int(i) * packed.n_entities + int(k)] = agent.controller.ctrl_row()
         self.n_envs = packed.n_scenarios
         self._ego = np.array([sc.entities.index(sc.ego) for sc in self.scenarios], np.int64)
         self.engine = RolloutEngine(packed.n_scenarios, packed.n_entities, timestep=timestep,
@@ -50,12 +72,21 @@ class VectorScenarioEnv:
         self._mask = terminal_mask(self.terminal_conditions)
         self.done = np.zeros(self.n_envs, bool)
         self._obs_env, self._obs_slot = np.zeros(0, np.int32), np.zeros(0, np.int32)  # set_observers
+        if drivers is not None:
+            self.engine.set_drivers(self._drv_env, self._drv_slot)
+            self.set_observers(drivers)  # (the default: every driver observes)
+
+    @property
+    def n_drivers(self):
+        return 0 if self._drv_env is None else len(self._drv_env)
 
     @property
     def observation_shape(self):
         return (len(self.layers), self.n, self.n)  # channels first, as MapOnlySensor(channels_first=True)
 
     def _observe(self):
+        if self._drv_env is not None:  # the observations of the observer list (the drivers, unless set_observers changed it)
+            return self.observe_entities()[0]
         if self.torch_obs:
             return self.engine.raster_map_torch(self._codes, self.width, self.height, self.n, self.n)
         return self.engine.raster_map(self._codes, self.width, self.height, self.n, self.n)
@@ -73,6 +104,8 @@ class VectorScenarioEnv:
         `step` does."""
         if not self.auto_reset and self.done.any():
             raise ValueError("Step called when state is terminal.")
+        if self._drv_env is not None:
+            return self._step_drivers(actions)
         if not hasattr(actions, "data_ptr"):
             actions = np.asarray(actions, np.float64).reshape(self.n_envs, 2)
         # step + terminal conditions + observation: one captured graph launch (sg_tick)
@@ -88,6 +121,23 @@ class VectorScenarioEnv:
             self.done = np.zeros(self.n_envs, bool)
             obs = self._observe()  # the restarted environments return the first observation of their new episode
         return obs, reward, done, {"terminal_flags": flags}
+
+    def _step_drivers(self, actions):
+        """step() with a driver list: actions [n_drivers, 2] in list order (environment by environment, each in the order of
+        its `drivers` entry).  sg_step_drivers, then sg_terminal_flags; reward, done and auto-reset per environment as without
+        drivers; obs [n_observers, n_layers, n, n] of the observer list (observe_entities)."""
+        if not hasattr(actions, "data_ptr"):
+            actions = np.asarray(actions, np.float64).reshape(self.n_drivers, 2)
+        self.engine.step_drivers(actions, 1)
+        flags = self.engine.terminal_flags()
+        done = (flags & self._mask) != 0
+        bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
+        reward = np.where(done & bad, -1.0, 0.01)  # RLAgent.reward, openaigym.py:300-310
+        self.done = done
+        if self.auto_reset and done.any():
+            self.engine.reset_scenarios(done)  # (the reset restarts the drivers' controller speeds with the rest of the state)
+            self.done = np.zeros(self.n_envs, bool)
+        return self._observe(), reward, done, {"terminal_flags": flags}
 
     def road_info(self, cap: int = 32):
         """State.get_road_info_at_entity for the ego of every environment (sg_road_info): count [R], geoms [R, cap] indices

@@ -41,6 +41,7 @@ GENERATORS = {
     "make_golden_route": ["route"],
     "make_golden_rss": ["rss"],
     "make_golden_sensors": ["sensors"],
+    "make_golden_drivers": ["drivers"],
 }
 
 
