@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers; sg_entity_status, sg_entity_status_observers) */
 
 typedef enum {
     SG_OK = 0,
@@ -602,6 +602,61 @@ int sg_range_scan(sg_handle *h, int32_t n_rays, double angle0, double dangle, do
  * (feat may be NULL then). */
 int sg_range_scan_observers(sg_handle *h, int32_t n_rays, double angle0, double dangle, double max_range, double *feat,
                             int32_t *slots, int32_t *hits, int32_t outputs_device);
+
+/* The episode status of an entity: what a per-agent reward and termination need of the ego of every scenario (n = n_scenarios
+ * observers) in one launch -- whether it is in the scene, in a collision and with what, where it stands on the road surfaces,
+ * its speed, its distance travelled, and the clearance: the distance from its box to the nearest other box.  The reference asks
+ * TERMINAL_CONDITIONS["ego_collision"] / ["ego_off_road"] (state/state.py:397-408) of entities[0] alone; here they are asked
+ * of THIS entity.  Plain fp64, IEEE division and square root, nothing fused.
+ * The observer is slot so of scenario r; `row` is its SG_F_COLL words as the state holds them (State.collisions(); the resets
+ * compute the collisions of the reset state).  An observer that is in State.poses:
+ *   flags[o]    SG_ST_PRESENT, and the SG_ST_* bits below
+ *   info[o][0]  the number of set bits of row
+ *   info[o][1]  the lowest set slot of row, -1 when none
+ *   info[o][2]  how many of its 4 box corners lie strictly inside the driveable surface (0..4)
+ *   info[o][3]  the slot of the nearest other box, -1 when none
+ *   feat[o][0]  |vel[:3]|, as EgoMaxSpeed takes it
+ *   feat[o][1]  State.distances (SG_F_DIST)
+ *   feat[o][2]  the clearance, +inf when there is no other box
+ * The corners are the RR, FR, FL, RL points of Entity.get_bounding_box_points.  A point ON a ring is outside, as everywhere in
+ * this library; the surface tests are those of sg_road_info and ego_off_road.
+ * The clearance: every OTHER slot e of r that is in State.poses (the presence rule of sg_nearest_entities) is a candidate with
+ * the squared gap
+ *   gap2 = +0.0 when bit e of row is set; otherwise the smallest of 32 squared distances d2 -- each corner P of one box against
+ *   each edge a -> b of the other (edges i -> (i + 1) & 3 of the corner ring), both ways round -- by the rule of
+ *   sg_lane_observation:
+ *     ex = bx - ax, ey = by - ay, L2 = ex*ex + ey*ey;  wx = px - ax, wy = py - ay, t = (wx*ex + wy*ey) / L2
+ *     the closest point is a when L2 == 0 or !(t > 0), b (the stored corner) when t >= 1, otherwise (ax + t*ex, ay + t*ey)
+ *     dx, dy = P minus that point, d2 = dx*dx + dy*dy
+ *   A d2 that is not finite is skipped; an entity with no finite d2 is not a candidate.
+ * The nearest box is the smallest (gap2, slot): info[o][3] its slot, feat[o][2] = sqrt(gap2).  Two disjoint convex quads are
+ * closest at a corner of one and an edge of the other, so for boxes that do not meet this is the distance between the fp64
+ * corner sets up to rounding.
+ * An observer that is NOT in State.poses gets flags = SG_ST_OFF_ROAD alone (the reference's rule for an absent entities[0]),
+ * info -1, -1, -1, -1 and feat +0.0.
+ * flags: [n], required; info: [n][SG_ST_NINFO], may be NULL; feat: [n][SG_ST_NFEAT] doubles, may be NULL.  Every byte of the
+ * arrays given is written.  HOST (outputs_device == 0, synchronous, through the observation scratch) or DEVICE (queued on
+ * sg_stream(h), not waited for), as in sg_nearest_entities, and a persistent rollout launch that gave up is reported as there.
+ * SG_ERR_INVALID: flags NULL.  SG_ERR_STATE before sg_upload.  A refused call writes nothing and leaves the handle working.
+ * One wavefront per observer: the scenario's slots go by in blocks of 64, lane = entity; any scenario width.  Not part of the
+ * sg_tick graph. */
+#define SG_ST_PRESENT        1u   /* the entity is in State.poses */
+#define SG_ST_COLLISION      2u   /* its State.collisions() row is not empty */
+#define SG_ST_OFF_ROAD       4u   /* TERMINAL_CONDITIONS["ego_off_road"] asked of THIS entity: not in State.poses, or its pose point not
+                                     strictly inside the driveable surface; no networks / a scenario without one = empty surface = set */
+#define SG_ST_CORNER_OFF     8u   /* present and at least one box corner not strictly inside the driveable surface */
+#define SG_ST_HIT_VEHICLE   16u   /* a slot of its collision row has etype 0 */
+#define SG_ST_HIT_PEDESTRIAN 32u  /* ... etype 1 */
+#define SG_ST_HIT_OTHER     64u   /* ... any other etype */
+#define SG_ST_LAYER_SHIFT    8    /* bits 8..15: the OR of the SG_LAYER_* bits of all polygons strictly containing the pose point */
+#define SG_ST_NINFO 4
+#define SG_ST_NFEAT 3
+int sg_entity_status(sg_handle *h, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_entity_status for scenario r.  With no observers set: SG_OK, nothing is written
+ * (flags may be NULL then). */
+int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device);
 
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).

@@ -29,7 +29,7 @@ from .agent import (  # noqa: F401
 )
 from .engine import PackedScenarios, RolloutEngine  # noqa: F401
 from .observation import (  # noqa: F401
-    CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
+    CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
     RangeScanObservation, SingleEntityObservation,
     combine_observations,
 )

@@ -15,6 +15,9 @@ ABI_VERSION = 7
 (KIND_NONE, KIND_REPLAY, KIND_AGENT_REPLAY, KIND_AGENT_PID, KIND_AGENT_VEHICLE, KIND_AGENT_PEDESTRIAN,
  KIND_AGENT_EXTERNAL) = range(7)
 TERM_MAX_LENGTH, TERM_COLLISION, TERM_EGO_COLLISION, TERM_EGO_OFF_ROAD = 1, 2, 4, 8
+# SG_ST_* of sg_entity_status: the flag bits, the shift of the layer bits, the widths of the info and feature rows
+ST_PRESENT, ST_COLLISION, ST_OFF_ROAD, ST_CORNER_OFF, ST_HIT_VEHICLE, ST_HIT_PEDESTRIAN, ST_HIT_OTHER = 1, 2, 4, 8, 16, 32, 64
+ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
 NCTRL = 16
 NOISE_OFF, NOISE_STREAM, NOISE_DEVICE = 0, 1, 2  # sg_set_ped_noise
 PED_SOCIAL_FORCE, PED_RANDOM_WALK = 0, 1         # sg_set_ped_behaviour
@@ -38,6 +41,7 @@ SYMBOLS = (
     "sg_set_lanes", "sg_lane_observation", "sg_lane_observation_observers",
     "sg_range_scan", "sg_range_scan_observers",
     "sg_set_drivers", "sg_step_drivers",
+    "sg_entity_status", "sg_entity_status_observers",
 )
 
 
@@ -213,6 +217,8 @@ def load():
     lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes
     lib.sg_range_scan.argtypes = [H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_range_scan_observers.argtypes = lib.sg_range_scan.argtypes
+    lib.sg_entity_status.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_entity_status_observers.argtypes = lib.sg_entity_status.argtypes
     lib.sg_set_drivers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sg_step_drivers.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,5 +1,5 @@
 // h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity,
-// lane-frame and range-scan observations of the ego and of a list of observers.
+// lane-frame and range-scan observations and the episode status of the ego and of a list of observers.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -377,4 +377,36 @@ extern "C" int sg_range_scan_observers(sg_handle *h, int32_t n_rays, double angl
 {
     if (!h) return SG_ERR_INVALID;
     return scan_call(h, "sg_range_scan_observers", true, n_rays, angle0, dangle, max_range, feat, slots, hits, outputs_device);
+}
+
+// ---- the entity status (entity_status_kernel, sgym_observers.hpp) ----------------------------------------------------------
+// n observers as above.  Host outputs pass through the observation scratch, the doubles first: [n][SG_ST_NFEAT] doubles, then
+// [n][SG_ST_NINFO] ints, then [n] flag words (the first two only when asked for).
+static int status_call(sg_handle *h, const char *who, bool observers, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device)
+{
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!flags) return fail(h, SG_ERR_INVALID, "%s: null flags", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    return deliver(h, who, outputs_device, obs_scratch,
+                   {{feat, (size_t)n * SG_ST_NFEAT * sizeof(double)}, {info, (size_t)n * SG_ST_NINFO * sizeof(int32_t)}, {flags, (size_t)n * sizeof(uint32_t)}}, 0,
+                   [&](void *const *d) {
+                       sgl::entity_status(h->stream, h->p, d_scen, d_slot, n, static_cast<uint32_t *>(d[2]), static_cast<int32_t *>(d[1]),
+                                          static_cast<double *>(d[0]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_entity_status(sg_handle *h, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return status_call(h, "sg_entity_status", false, flags, info, feat, outputs_device);
+}
+
+extern "C" int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return status_call(h, "sg_entity_status_observers", true, flags, info, feat, outputs_device);
 }

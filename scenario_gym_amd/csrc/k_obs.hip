@@ -1,6 +1,6 @@
-// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel: the map,
-// look-ahead, nearest-entity, lane-frame and range-scan observations of the ego of every scenario or of a list of observers
-// (scenario, slot), any entity of its scenario (sgym_observers.hpp).
+// k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel /
+// entity_status_kernel: the map, look-ahead, nearest-entity, lane-frame and range-scan observations and the episode status of the
+// ego of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -52,5 +52,12 @@ void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const i
 {
     if (n <= 0) return;
     sg::range_scan_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, n_rays, angle0, dangle, max_range, feat, slots, hits);
+}
+
+void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, uint32_t *flags, int32_t *info,
+                   double *feat)
+{
+    if (n <= 0) return;
+    sg::entity_status_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, flags, info, feat);
 }
 } // namespace sgl

@@ -69,6 +69,10 @@ void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L
 // [n][n_rays] (or nullptr), hits [n] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
 void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_rays, double angle0, double dangle,
                 double max_range, double *feat, int32_t *slots, int32_t *hits);
+// entity_status_kernel: the episode status of observer o < n (the same two lists): flags [n] SG_ST_* bits, info [n][SG_ST_NINFO] (or
+// nullptr), feat [n][SG_ST_NFEAT] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
+void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, uint32_t *flags, int32_t *info,
+                   double *feat);
 // k_drive.hip (sgym_drive.hpp): drive_kernel, one lane per driver d < n: the VehicleController step of entity (scen[d], slot[d]) with
 // actions[d] = (accel, steer) (nullptr: (0, 0)) from its current pose, into row (scen[d] * EP + slot[d]) of ext, the handle's
 // external-pose buffer [NE][6] -- NaN for a driver that is not in the scene; the controller speed in the slot's SG_F_CTRL + 0 cell.

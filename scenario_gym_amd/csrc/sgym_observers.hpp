@@ -1,5 +1,5 @@
-// sgym_observers.hpp -- The map, look-ahead, nearest-entity and lane-frame observations: one raster kernel, one look-ahead kernel,
-// one nearest-entity kernel and one lane kernel for the ego of every scenario and for a caller-given list of observers (any entity).
+// sgym_observers.hpp -- The map, look-ahead, nearest-entity, lane-frame and range-scan observations and the entity status: one kernel
+// each for the ego of every scenario and for a caller-given list of observers (any entity).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
@@ -695,6 +695,144 @@ static __global__ __launch_bounds__(256) void range_scan_kernel(Params p, const 
         }
     }
     if (lane == 0 && hits) hits[o] = total;
+}
+#endif // SG_UNIT_OBS
+
+// ------------------------------------------------------------------------------------------------
+// The entity status: what a per-agent reward and termination ask of one entity -- in the scene, in a collision and with what,
+// on the road, its speed and distance travelled, and the clearance, the distance from its box to the nearest other box (the
+// reference asks ego_collision / ego_off_road of entities[0] alone, state/state.py:397-408).  The definition is in
+// include/sgym.h at sg_entity_status: plain unfused fp64 with IEEE division and square root.
+// ------------------------------------------------------------------------------------------------
+
+// the smallest finite squared distance from the four corners of P to the four edges i -> (i + 1) & 3 of Q, folded into `best`
+// (+inf to begin with: a NaN or an infinite d2 is never taken); the point-to-segment rule of lane_project
+__device__ __forceinline__ double status_corners_to_edges(const double (&P)[8], const double (&Q)[8], double best)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int j = (i + 1) & 3;
+        const double ax = Q[2 * i], ay = Q[2 * i + 1], bx = Q[2 * j], by = Q[2 * j + 1];
+        const double ex = bx - ax, ey = by - ay, L2 = ex * ex + ey * ey;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double px = P[2 * k], py = P[2 * k + 1];
+            const double wx = px - ax, wy = py - ay, t = (wx * ex + wy * ey) / L2;
+            const bool at_a = L2 == 0.0 || !(t > 0.0), at_b = t >= 1.0;
+            const double cx = at_a ? ax : at_b ? bx : ax + t * ex, cy = at_a ? ay : at_b ? by : ay + t * ey;
+            const double dx = px - cx, dy = py - cy, d2 = dx * dx + dy * dy;
+            best = d2 < best ? d2 : best;
+        }
+    }
+    return best;
+}
+
+// Observer o < n as in nearest_kernel; flags [n], info [n][SG_ST_NINFO] (may be nullptr), feat [n][SG_ST_NFEAT] (may be nullptr),
+// every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no barrier, no atomics.  What belongs
+// to the observer alone -- its rows, its corners, its collision row's word of the block at hand -- is the same in every lane:
+// each lane loads and computes it for itself (one address per load, one sg_sincos), which costs no more than staging it would.
+//   the row: lane l takes the words l, l + 64, ... (one word up to 64 slots, at most 256): set bits, the lowest, and the entity
+//     type of every set slot; a butterfly sums, takes the minimum and ORs.
+//   the clearance: the scenario's slots go by in blocks of 64, ascending, lane = entity.  A lane whose bit of the row is set
+//     has gap2 = +0.0; the other present ones get sin / cos of their heading, their corners, and the 32 corner-to-edge tests;
+//     a block in which no lane has such a test to run (nobody present, or everybody in the row) skips them.  Per lane a running
+//     (gap2 bits, slot) with a strict <, then near_wave_min: a finite non-negative double orders as its bit pattern does.
+//     No pre-filter: every candidate is tested, so the answers are those of the plain definition by construction.
+//   the surfaces: lane 0 looks up the pose point for all eight layers, lanes 1..4 a corner each for the driveable surface.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n,
+                                                                   uint32_t *flags, int32_t *info, double *feat)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t o = (int64_t)blockIdx.x * 4 + w;
+    if (o >= n) return; // (the whole wavefront, which meets no barrier)
+    const int r = obs_scen ? obs_scen[o] : (int)o, slot = obs_scen ? obs_slot[o] : p.sstat[o].ego;
+    const uint32_t base = (uint32_t)r * p.EP;
+    const double *d = near_dyn(p, base + (uint32_t)slot), *st = near_stat(p, base + (uint32_t)slot);
+    if (reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] == 0) { // not in State.poses: the rule for an absent entities[0]
+        if (lane == 0) flags[o] = SG_ST_OFF_ROAD;
+        if (info && lane < SG_ST_NINFO) info[(size_t)o * SG_ST_NINFO + lane] = -1;
+        if (feat && lane < SG_ST_NFEAT) feat[(size_t)o * SG_ST_NFEAT + lane] = 0.0;
+        return;
+    }
+    const double x = d[(SG_F_POSE + 0) * 64], y = d[(SG_F_POSE + 1) * 64];
+    double A[8], sa, ca;
+    sg_sincos(d[(SG_F_POSE + 3) * 64], sa, ca);
+    sg_corners(x, y, sa, ca, st[ST_BW * 64], st[ST_BL * 64], st[ST_BCX * 64], st[ST_BCY * 64], A);
+
+    // the collision row
+    const uint64_t *row = reinterpret_cast<const uint64_t *>(d) + SG_F_COLL * 64; // word q: row[q * 64]
+    const int W = p.FROWS - SG_F_COLL;                                             // (64 * W >= E)
+    int pop = 0, low = NEAR_NO_SLOT;
+    uint32_t hit = 0u;
+    for (int q = lane; q < W; q += 64) {
+        uint64_t m = row[(size_t)q * 64];
+        pop += __popcll(m);
+        if (m && low == NEAR_NO_SLOT) low = q * 64 + __builtin_ctzll(m); // (ascending q: this lane's lowest)
+        for (; m; m &= m - 1) {
+            const int e = q * 64 + __builtin_ctzll(m);
+            if (e >= p.E) continue; // (a row holds entity slots only)
+            const int64_t meta = reinterpret_cast<const int64_t *>(near_stat(p, base + (uint32_t)e))[ST_META * 64];
+            const int etype = (int)((meta >> 8) & 0xff);
+            hit |= etype == 0 ? SG_ST_HIT_VEHICLE : etype == 1 ? SG_ST_HIT_PEDESTRIAN : SG_ST_HIT_OTHER;
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        pop += __shfl_xor(pop, m, 64);
+        low = min(low, __shfl_xor(low, m, 64));
+        hit |= (uint32_t)__shfl_xor((int)hit, m, 64);
+    }
+
+    // the clearance
+    uint64_t bk = NEAR_NONE;
+    int bs = NEAR_NO_SLOT;
+    for (int e0 = 0; e0 < p.E; e0 += 64) {
+        const int e = e0 + lane;
+        const bool other = e < p.E && e != slot; // (a lane without a slot reads the observer's own rows, which are there)
+        const uint32_t idx = base + (uint32_t)(other ? e : slot);
+        const double *de = near_dyn(p, idx), *se = near_stat(p, idx);
+        const bool in = other && reinterpret_cast<const uint64_t *>(de)[SG_F_PRESENT * 64] != 0;
+        const bool bit = ((row[(size_t)(e0 >> 6) * 64] >> lane) & 1ull) != 0;
+        double g = __builtin_inf();
+        if (sg_any(in && !bit)) {
+            double B[8], sb, cb;
+            sg_sincos(de[(SG_F_POSE + 3) * 64], sb, cb);
+            sg_corners(de[(SG_F_POSE + 0) * 64], de[(SG_F_POSE + 1) * 64], sb, cb, se[ST_BW * 64], se[ST_BL * 64], se[ST_BCX * 64],
+                       se[ST_BCY * 64], B);
+            g = status_corners_to_edges(A, B, g);
+            g = status_corners_to_edges(B, A, g);
+        }
+        g = bit ? 0.0 : g;
+        const uint64_t key = in && g < __builtin_inf() ? (uint64_t)__double_as_longlong(g) : NEAR_NONE;
+        const bool take = key < bk; // (ascending slots per lane: the lower slot keeps a tie)
+        bk = take ? key : bk;
+        bs = take ? e : bs;
+    }
+    near_wave_min(bk, bs);
+
+    // the surfaces: the pose point (every layer) and the four corners (the driveable surface)
+    uint32_t lay = 0u;
+    if (lane < 5 && p.road) {
+        const RoadIndex RI = *p.road;
+        const double px = lane == 0 ? x : lane == 1 ? A[0] : lane == 2 ? A[2] : lane == 3 ? A[4] : A[6];
+        const double py = lane == 0 ? y : lane == 1 ? A[1] : lane == 2 ? A[3] : lane == 3 ? A[5] : A[7];
+        lay = rn_layers_at(RI, RI.net_of_scen[r], lane == 0 ? 0xffu : SG_LAYER_DRIVEABLE, px, py);
+    }
+    const int corners_on = __popcll(__ballot(lane >= 1 && lane < 5 && (lay & SG_LAYER_DRIVEABLE) != 0));
+    const uint32_t lay0 = (uint32_t)__shfl((int)lay, 0, 64);
+
+    if (lane == 0)
+        flags[o] = SG_ST_PRESENT | (pop ? SG_ST_COLLISION : 0u) | ((lay0 & SG_LAYER_DRIVEABLE) ? 0u : SG_ST_OFF_ROAD) |
+                   (corners_on < 4 ? SG_ST_CORNER_OFF : 0u) | hit | (lay0 << SG_ST_LAYER_SHIFT);
+    if (info && lane < SG_ST_NINFO)
+        info[(size_t)o * SG_ST_NINFO + lane] = lane == 0 ? pop : lane == 1 ? (low == NEAR_NO_SLOT ? -1 : low) : lane == 2 ? corners_on
+                                                                                                              : (bk == NEAR_NONE ? -1 : bs);
+    if (feat && lane < SG_ST_NFEAT) {
+        const double speed = sg_norm3(d[(SG_F_VEL + 0) * 64], d[(SG_F_VEL + 1) * 64], d[(SG_F_VEL + 2) * 64]);
+        const double gap = bk == NEAR_NONE ? __builtin_inf() : __builtin_sqrt(__longlong_as_double((long long)bk));
+        feat[(size_t)o * SG_ST_NFEAT + lane] = lane == 0 ? speed : lane == 1 ? d[SG_F_DIST * 64] : gap;
+    }
 }
 #endif // SG_UNIT_OBS
 

@@ -411,7 +411,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -543,6 +543,32 @@ class RolloutEngine:
         """range_scan for every observer of set_observers (sg_range_scan_observers): (feat [n, n_rays, 2], slots [n, n_rays],
         hits [n]); empty arrays when no observers are set."""
         return self._range_scan(self.lib.sg_range_scan_observers, self._n_obs, n_rays, angle0, dangle, max_range, torch_out)
+
+    def _entity_status(self, call, n, torch_out):
+        outs, ptrs = self._outputs(torch_out, ((n,), "int32" if torch_out else "uint32"), ((n, L.ST_NINFO), "int32"), ((n, L.ST_NFEAT), "float64"))
+        self._check(call(self.h, *ptrs, int(bool(torch_out))), call.__name__)
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
+
+    def entity_status(self, torch_out=False):
+        """The episode status of the ego of every scenario (sg_entity_status): what a per-agent reward and termination need in
+        one launch.  Returns (flags [R] uint32, info [R, 4] int32, feat [R, 3] float64).  flags: ST_PRESENT (in the scene),
+        ST_COLLISION (its State.collisions() row is not empty), ST_OFF_ROAD (ego_off_road asked of this entity: not in the scene
+        or its pose point not strictly inside the driveable surface), ST_CORNER_OFF (a box corner is not), ST_HIT_VEHICLE /
+        ST_HIT_PEDESTRIAN / ST_HIT_OTHER (the entity types in its row), and from bit ST_LAYER_SHIFT the LAYER_* bits of the
+        polygons that contain its pose point.  info: the number of entities it collides with, the lowest of their slots (-1:
+        none), how many of its four box corners are on the driveable surface, the slot of the nearest other box (-1: none).
+        feat: its speed, its distance travelled, and the clearance -- the distance from its box to the nearest other box, 0
+        when they collide, inf when it is alone.  An ego that is not in the scene: ST_OFF_ROAD alone, info -1, feat 0.
+        torch_out: torch tensors in HBM the kernel writes directly (flags as int32 bit patterns; waited for, as in
+        raster_map_observers)."""
+        return self._entity_status(self.lib.sg_entity_status, self.R, torch_out)
+
+    def entity_status_observers(self, torch_out=False):
+        """entity_status for every observer of set_observers (sg_entity_status_observers): (flags [n], info [n, 4], feat
+        [n, 3]); empty arrays when no observers are set."""
+        return self._entity_status(self.lib.sg_entity_status_observers, self._n_obs, torch_out)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

@@ -12,6 +12,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
+from . import _lib as L
 from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RangeScanSensor, RasterizedMapSensor,
                     _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
@@ -386,6 +387,31 @@ class BatchedScenarioGym:
         call = self.engine.range_scan_observers if observers else self.engine.range_scan
         return self._cached(("scan", observers, n_rays, angle0, dangle, max_range), lambda: call(n_rays, angle0, dangle, max_range),
                             observers=observers)
+
+    def _entity_status(self, observers: bool):
+        """(flags [n], info [n, 4], feat [n, 3]) of State.entity_status."""
+        call = self.engine.entity_status_observers if observers else self.engine.entity_status
+        return self._cached(("status", observers), call, observers=observers, roads=True)
+
+    def entity_status(self):
+        """State.entity_status for every entity slot of the batch: (flags [R, E] ST_* bits, info [R, E, 4], feat [R, E, 3]) as
+        RolloutEngine.entity_status gives them for the egos -- one device call with every slot an observer; a padding slot
+        reads as an entity that is not in the scene.  The gym's own observer list is put back afterwards."""
+        R, E = self.engine.R, self.engine.E
+        kinds = np.asarray(self._packed.kind).reshape(R, E)
+        r, e = np.nonzero(kinds != L.KIND_NONE)
+        flags, info, feat = np.full((R, E), L.ST_OFF_ROAD, np.uint32), np.full((R, E, L.ST_NINFO), -1, np.int32), np.zeros((R, E, L.ST_NFEAT))
+        self._set_road_networks()
+        self.engine.set_observers(r, e)
+        try:
+            flags[r, e], info[r, e], feat[r, e] = self.engine.entity_status_observers()
+        finally:
+            self._observers_sent = 0
+            if self._observers:
+                self._send_observers()
+            else:
+                self.engine.set_observers([], [])
+        return flags, info, feat
 
     def _set_lanes(self):
         """The lane centre lines of every scenario's road network -> the device (behind the networks themselves, whose

@@ -84,6 +84,30 @@ class RangeScanObservation(SingleEntityObservation):
     hit_entities: list
 
 
+@dataclass
+class EntityStatus:
+    """The episode status of one entity (State.entity_status, sg_entity_status; the reference asks ego_collision and
+    ego_off_road of entities[0] alone): `present` -- it is in State.poses; `in_collision` -- its State.collisions() row is not
+    empty; `off_road` -- TERMINAL_CONDITIONS["ego_off_road"] asked of this entity (not present, or its pose point not strictly
+    inside the driveable surface); `corners_on_road` -- how many of its four box corners are strictly inside it (-1 when not
+    present); `layers` -- the class names of the road geometries that contain its pose point ("Road", "Intersection", "Lane",
+    "Pavement", "Crossing", "Building"); `hit_entities` -- the entities of its collision row; `nearest_entity` and `clearance`
+    -- the other entity whose box is nearest and the distance between the two boxes (0 when they collide; None and inf when
+    it is alone); `speed`, `distance` -- |velocity[:3]| and the distance travelled.  Not present: zeros."""
+
+    entity: Any
+    present: bool
+    in_collision: bool
+    off_road: bool
+    corners_on_road: int
+    layers: list
+    hit_entities: list
+    nearest_entity: Any
+    clearance: float
+    speed: float
+    distance: float
+
+
 def combine_observations(*classes, prefixes: Optional[Sequence[Optional[str]]] = None):
     """observation.py:31-84: a dataclass holding the fields of all `classes` in order.  A field name that an earlier class
     already contributed is skipped -- or, with `prefixes` (one per class), taken as "<prefix>_<name>"; a name that is still

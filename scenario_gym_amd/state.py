@@ -4,8 +4,15 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from . import _lib as L
 from .entity import Entity
+from .observation import EntityStatus
+from .road_network import LAYER_CROSSING, LAYER_IMPENETRABLE, LAYER_INTERSECTION, LAYER_LANE, LAYER_PAVEMENT, LAYER_ROAD
 from .scenario import Scenario
+
+# the class names State.get_road_info_at_entity gives the geometries of each layer (EntityStatus.layers)
+LAYER_CLASS_NAMES = ((LAYER_ROAD, "Road"), (LAYER_INTERSECTION, "Intersection"), (LAYER_LANE, "Lane"), (LAYER_PAVEMENT, "Pavement"),
+                     (LAYER_CROSSING, "Crossing"), (LAYER_IMPENETRABLE, "Building"))
 
 
 class State:
@@ -225,6 +232,22 @@ class State:
                                                float(max_range))
         ents = self._scenario.entities
         return feat[row, :, 0].copy(), feat[row, :, 1].copy(), [ents[j] if j >= 0 else None for j in slots[row]]
+
+    def entity_status(self, entity: Optional[Entity] = None):
+        """The episode status of `entity` (any entity of the scenario, default the ego) at the current state, computed on the
+        device (sg_entity_status / sg_entity_status_observers): an EntityStatus -- in the scene, in a collision and with whom,
+        off the road, box corners on the road, the road geometry classes under it, the nearest other box and the clearance
+        to it, speed and distance travelled."""
+        observers, row = self._sensor_row(entity)
+        flags, info, feat = self._gym._entity_status(observers)
+        ents = self._scenario.entities
+        entity = self._scenario.ego if entity is None else entity
+        f, near = int(flags[row]), int(info[row, 3])
+        present = bool(f & L.ST_PRESENT)
+        return EntityStatus(entity, present, bool(f & L.ST_COLLISION), bool(f & L.ST_OFF_ROAD), int(info[row, 2]),
+                            [name for bit, name in LAYER_CLASS_NAMES if (f >> L.ST_LAYER_SHIFT) & bit],
+                            list(self.collisions().get(entity, [])) if present else [], ents[near] if near >= 0 else None,
+                            float(feat[row, 2]), float(feat[row, 0]), float(feat[row, 1]))
 
     def lane_observation(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf"),
                          entity: Optional[Entity] = None):

@@ -32,9 +32,11 @@ class VectorScenarioEnv:
                  terminal_conditions: Optional[Sequence[str]] = None, layers: Optional[Sequence[str]] = None,
                  height: float = 30.0, width: float = 30.0, n: int = 128, max_steer: float = 0.9, max_accel: float = 5.0,
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
-                 drivers: Optional[Sequence[Sequence[int]]] = None):
+                 drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
-        VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment."""
+        VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
+        driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
+        and a reward and a done flag per driver in `info`; False: nothing is added and nothing is launched."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -42,6 +44,7 @@ class VectorScenarioEnv:
         self._codes = [LAYER_CODES[l] for l in self.layers]
         self.height, self.width, self.n = float(height), float(width), int(n)
         self.auto_reset, self.torch_obs = auto_reset, torch_obs
+        self.driver_status = bool(driver_status)
 
         if drivers is not None and len(drivers) != len(self.scenarios):
             raise ValueError("drivers: one list of entity indices per environment")
@@ -125,7 +128,10 @@ class VectorScenarioEnv:
     def _step_drivers(self, actions):
         """step() with a driver list: actions [n_drivers, 2] in list order (environment by environment, each in the order of
         its `drivers` entry).  sg_step_drivers, then sg_terminal_flags; reward, done and auto-reset per environment as without
-        drivers; obs [n_observers, n_layers, n, n] of the observer list (observe_entities)."""
+        drivers; with driver_status, info also holds driver_flags [n_drivers], driver_info [n_drivers, 4], driver_feat
+        [n_drivers, 3] (sg_entity_status_observers on the stepped state, before an auto-reset), driver_reward [n_drivers] (-1 for
+        a driver that is off the road or in a collision, else 0.01) and driver_done [n_drivers] (that, or its environment
+        done); obs [n_observers, n_layers, n, n] of the observer list (observe_entities)."""
         if not hasattr(actions, "data_ptr"):
             actions = np.asarray(actions, np.float64).reshape(self.n_drivers, 2)
         self.engine.step_drivers(actions, 1)
@@ -133,11 +139,42 @@ class VectorScenarioEnv:
         done = (flags & self._mask) != 0
         bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
         reward = np.where(done & bad, -1.0, 0.01)  # RLAgent.reward, openaigym.py:300-310
+        info = {"terminal_flags": flags}
+        if self.driver_status and self.n_drivers:  # the stepped state, before an auto-reset replaces it
+            d_flags, d_info, d_feat = self._driver_status()
+            d_bad = (d_flags & (L.ST_OFF_ROAD | L.ST_COLLISION)) != 0
+            info.update(driver_flags=d_flags, driver_info=d_info, driver_feat=d_feat,
+                        driver_reward=np.where(d_bad, -1.0, 0.01),  # RLAgent.reward asked per driver, without its is_done gate
+                        driver_done=d_bad | done[self._drv_env])
         self.done = done
         if self.auto_reset and done.any():
             self.engine.reset_scenarios(done)  # (the reset restarts the drivers' controller speeds with the rest of the state)
             self.done = np.zeros(self.n_envs, bool)
-        return self._observe(), reward, done, {"terminal_flags": flags}
+        return self._observe(), reward, done, info
+
+    def _driver_status(self):
+        """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays: read
+        through the observer list when that is the driver list (the default); otherwise the drivers are the engine's observers
+        for this one call and the caller's list is put back."""
+        same = np.array_equal(self._obs_env, self._drv_env) and np.array_equal(self._obs_slot, self._drv_slot)
+        if not same:
+            self.engine.set_observers(self._drv_env, self._drv_slot)
+        try:
+            return self.engine.entity_status_observers()
+        finally:
+            if not same:
+                self.engine.set_observers(self._obs_env, self._obs_slot)
+
+    def status(self):
+        """The episode status of the ego of every environment at the current state (sg_entity_status): (flags [R] ST_* bits, info
+        [R, 4], feat [R, 3]: RolloutEngine.entity_status).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        return self.engine.entity_status(torch_out=self.torch_obs)
+
+    def observe_entities_status(self):
+        """The episode status of every observer of set_observers at the current state (sg_entity_status_observers): (flags [n],
+        info [n, 4], feat [n, 3], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        out = self.engine.entity_status_observers(torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
 
     def road_info(self, cap: int = 32):
         """State.get_road_info_at_entity for the ego of every environment (sg_road_info): count [R], geoms [R, cap] indices
