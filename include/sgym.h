@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers; sg_entity_status, sg_entity_status_observers) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers; sg_entity_status, sg_entity_status_observers; sg_set_driver_policy, sg_driver_policy_actions, sg_step_drivers_policy) */
 
 typedef enum {
     SG_OK = 0,
@@ -376,6 +376,77 @@ int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, const int32
  * SG_ERR_INVALID: n_steps < 1.  One short launch ahead of every step; not part of the sg_tick graph (sg_tick and sg_rollout
  * keep refusing batches with SG_KIND_AGENT_EXTERNAL slots). */
 int sg_step_drivers(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device);
+
+/* The built-in driver policy: traffic that reacts.  A listed driver follows a path (a polyline) with a Stanley-style steering law
+ * and takes its acceleration from the Intelligent Driver Model (IDM) against the nearest box in a straight corridor ahead of it
+ * and against the end of its path.  The reference has no such agent (its agents are replay, PID, pedestrian or caller-run); the
+ * device evaluates the policy on the current state, so reactive traffic runs for any number of steps with no host in the loop.
+ * Plain fp64, IEEE division and square root, nothing fused.
+ * Policy driver j is driver driver[j] of the list of sg_set_drivers, slot so of scenario r, with the parameter row params[j]
+ * (SG_DP_*) and the path pts[pt_off[j] .. pt_off[j + 1]), in driving order, used as given.  The path's segments a -> b are the rows
+ * sg_set_lanes builds: e = b - a, L2 = ex*ex + ey*ey, len = sqrt(L2), cum = the sequential fp64 sum of the lens before it;
+ * total = cum + len of the last segment.  A path of fewer than two points has no segments.
+ * The driver has pose (x, y, h), (s, c) = sin, cos of h, v = its SG_F_CTRL + 0 cell (the controller speed of sg_step_drivers), box
+ * (Wo, Lo, cxo, cyo) and front = cxo + 0.5*Lo.  A driver that is NOT in State.poses gets actions (+0.0, +0.0), info -1, -1 and feat
+ * +0.0; sg_step_drivers_policy then does with it what sg_step_drivers does.  Otherwise:
+ *   the path term: over the segments i of its path, (d2, dx, dy, t) by the point-to-segment rule of sg_lane_observation; a d2 that
+ *   is not finite is skipped; the best segment g is the smallest (d2, i).  With it:
+ *     (ux, uy) = (ex/len, ey/len), or (0, 0) when len == 0;   off = ux*dy - uy*dx
+ *     se = s*ux - c*uy,  ce = c*ux + s*uy;   ce < 0 (facing against the path): se = (se >= 0 ? 1.0 : -1.0)
+ *     s0 = cum + t*len,  rem = total - s0
+ *     steer = -(K_PSI*se + (K_E*off) / (K_SOFT + fabs(v)))          (not clamped: VehicleController._step clamps it)
+ *   With no segment: steer = +0.0, off = se = s0 = +0.0, rem = +inf.
+ *   the lead: every OTHER slot e of r that is in State.poses (the presence rule of sg_nearest_entities), with pose (xe, ye, he),
+ *   (sn, cn) = sin, cos of he and box (We, Le, cxe, cye):
+ *     qx = xe + (cxe*cn - cye*sn),  qy = ye + (cxe*sn + cye*cn);   dx = qx - x,  dy = qy - y
+ *     lon = dx*c + dy*s,  lat = dy*c - dx*s;   cr = cn*c + sn*s,  sr = sn*c - cn*s
+ *     hl = 0.5*(fabs(Le*cr) + fabs(We*sr)),  hw = 0.5*(fabs(Le*sr) + fabs(We*cr));   gap = (lon - hl) - front
+ *   e is a candidate iff  lat - hw <= (cyo + 0.5*Wo) + HALF  and  lat + hw >= (cyo - 0.5*Wo) - HALF  and  lon + hl > front  and
+ *   gap <= REACH (inclusive); a NaN anywhere fails.  The lead is the smallest (gap, slot), the gaps compared as fp64 values (a gap
+ *   may be negative; ties, -0.0 against +0.0 included, go to the lower slot);  dv = v - (vxe*c + vye*s).  With no lead: gap = +inf,
+ *   dv = +0.0.  The corridor is straight, in the driver's heading frame.
+ *   the acceleration: vr = v / V0, free = 1.0 - (vr*vr)*(vr*vr), root = 2.0*sqrt(A*B), and
+ *     idm(g, d):  q = v*T + (v*d)/root;  ss = S0 + (q > 0 ? q : 0.0);  gg = g > GAP_MIN ? g : GAP_MIN;  rr = ss/gg;
+ *                 idm = A*(free - rr*rr)
+ *     acc = lead ? idm(gap, dv) : A*free;   with a segment: ae = idm(rem, v), acc = ae < acc ? ae : acc
+ *   (ae: the end of the path as a standing obstacle).  actions = (acc, steer).
+ * sg_set_driver_policy: HOST arrays, copied by the call into buffers the handle owns; NULL or m == 0 clears the policy.  The call
+ * waits for the work queued on sg_stream(h) first, as sg_set_drivers does.  SG_ERR_STATE before sg_upload or with no driver list.
+ * SG_ERR_INVALID: m < 0; a NULL array that is needed; a driver index outside [0, n_drivers) or not strictly ascending; pt_off not
+ * starting at 0 or not monotone; a parameter that is NaN; V0, A, B, K_SOFT or GAP_MIN not > 0 or infinite; T, S0, HALF or REACH
+ * < 0 (REACH alone may be +inf, T, S0 and HALF may not); K_PSI or K_E infinite; a NaN in pts.  A refused call leaves the previous
+ * policy in place.  sg_set_drivers forgets the policy, whether it replaces or clears the list, and so does sg_upload; sg_reset /
+ * sg_reset_scenarios / sg_step / sg_step_drivers keep it, and sg_step_drivers never reads it. */
+enum { SG_DP_V0, SG_DP_T, SG_DP_S0, SG_DP_A, SG_DP_B, SG_DP_HALF, SG_DP_REACH,
+       SG_DP_K_PSI, SG_DP_K_E, SG_DP_K_SOFT, SG_DP_GAP_MIN, SG_DP_NPARAM = 12 };
+#define SG_DP_NINFO 2
+#define SG_DP_NFEAT 6
+typedef struct sg_driver_policy {
+    int64_t m;              /* policy-run drivers */
+    const int64_t *driver;  /* [m] positions in the list of sg_set_drivers, strictly ascending */
+    const double *params;   /* [m][SG_DP_NPARAM] */
+    const int64_t *pt_off;  /* [m + 1] ranges of pts, starting at 0, monotone */
+    const double *pts;      /* [n_pts][2] x, y: the path of each, in driving order, used as given */
+} sg_driver_policy;
+int sg_set_driver_policy(sg_handle *h, const sg_driver_policy *pol);
+
+/* The policy evaluated on the current state, for the m policy drivers in their order: actions [m][2] (acc, steer), required;
+ * info [m][SG_DP_NINFO]: the lead's slot and the best segment's index within its path, -1 when none, may be NULL; feat
+ * [m][SG_DP_NFEAT]: gap, dv, off, se, s0, rem, may be NULL.  Every byte of the arrays given is written.  HOST (outputs_device == 0,
+ * synchronous, through a scratch of the handle) or DEVICE (queued on sg_stream(h), not waited for), as in sg_entity_status, and a
+ * persistent rollout launch that gave up is reported as there.  With no policy set: SG_OK, nothing is written (actions may be NULL
+ * then).  SG_ERR_INVALID: actions NULL.  SG_ERR_STATE before sg_upload.  One wavefront per policy driver: lane = path segment, then
+ * lane = entity over the scenario's slots in blocks of 64; any scenario width.  Not part of the sg_tick graph. */
+int sg_driver_policy_actions(sg_handle *h, double *actions, int32_t *info, double *feat, int32_t outputs_device);
+
+/* sg_step_drivers with the policy in the loop: the same actions [n_steps][n_drivers][2] (HOST, DEVICE or NULL), the same order on
+ * the stream, the same single wait at the end.  For each step k the action rows of the policy drivers are replaced by the policy
+ * evaluated on the state before that step, ahead of the drivers' controller step; the rows of the other drivers pass through
+ * untouched.  The replacement happens in a buffer of the handle: a caller's device buffer is never written.  The result is that of
+ *   sg_driver_policy_actions; merge its rows into actions[k]; sg_step_drivers(h, 1, merged, ...)
+ * run n_steps times, bit for bit on everything a caller can read.  One short launch more per step than sg_step_drivers.
+ * SG_ERR_STATE before sg_upload, without a driver list or without a policy; SG_ERR_INVALID: n_steps < 1. */
+int sg_step_drivers_policy(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device);
 
 /* ScenarioGym.rollout(): reset, then step each scenario while it is not done, at most max_steps
  * (scenario_gym.py:256-267).  The time loop runs inside the kernels: one launch for short runs; long runs of batches with

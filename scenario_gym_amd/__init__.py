@@ -27,7 +27,7 @@ from .agent import (  # noqa: F401
     TeleportAction,
     VehicleAction,
 )
-from .engine import PackedScenarios, RolloutEngine  # noqa: F401
+from .engine import PackedScenarios, RolloutEngine, idm_params  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
     RangeScanObservation, SingleEntityObservation,

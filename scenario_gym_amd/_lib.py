@@ -18,6 +18,9 @@ TERM_MAX_LENGTH, TERM_COLLISION, TERM_EGO_COLLISION, TERM_EGO_OFF_ROAD = 1, 2, 4
 # SG_ST_* of sg_entity_status: the flag bits, the shift of the layer bits, the widths of the info and feature rows
 ST_PRESENT, ST_COLLISION, ST_OFF_ROAD, ST_CORNER_OFF, ST_HIT_VEHICLE, ST_HIT_PEDESTRIAN, ST_HIT_OTHER = 1, 2, 4, 8, 16, 32, 64
 ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
+# SG_DP_* of sg_set_driver_policy: the columns of a parameter row, its width, the widths of the info and feature rows
+(DP_V0, DP_T, DP_S0, DP_A, DP_B, DP_HALF, DP_REACH, DP_K_PSI, DP_K_E, DP_K_SOFT, DP_GAP_MIN) = range(11)
+DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
 NCTRL = 16
 NOISE_OFF, NOISE_STREAM, NOISE_DEVICE = 0, 1, 2  # sg_set_ped_noise
 PED_SOCIAL_FORCE, PED_RANDOM_WALK = 0, 1         # sg_set_ped_behaviour
@@ -42,6 +45,7 @@ SYMBOLS = (
     "sg_range_scan", "sg_range_scan_observers",
     "sg_set_drivers", "sg_step_drivers",
     "sg_entity_status", "sg_entity_status_observers",
+    "sg_set_driver_policy", "sg_driver_policy_actions", "sg_step_drivers_policy",
 )
 
 
@@ -65,6 +69,10 @@ class SgRoadNetworks(C.Structure):
 
 class SgLanes(C.Structure):  # include/sgym.h sg_lanes
     _fields_ = [("n_networks", C.c_int32)] + [(n, C.c_void_p) for n in ("lane_off", "pt_off", "pts", "succ_off", "succ")]
+
+
+class SgDriverPolicy(C.Structure):  # include/sgym.h sg_driver_policy
+    _fields_ = [("m", C.c_int64)] + [(n, C.c_void_p) for n in ("driver", "params", "pt_off", "pts")]
 
 
 class SgSocialForce(C.Structure):
@@ -221,6 +229,9 @@ def load():
     lib.sg_entity_status_observers.argtypes = lib.sg_entity_status.argtypes
     lib.sg_set_drivers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sg_step_drivers.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
+    lib.sg_set_driver_policy.argtypes = [H, C.POINTER(SgDriverPolicy)]
+    lib.sg_driver_policy_actions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_step_drivers_policy.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -156,6 +156,9 @@ extern "C" int sg_destroy(sg_handle *h)
     h->observers.release();
     h->drivers.release();
     h->drv_actions.release();
+    h->policy.release();
+    h->pol_actions.release();
+    h->pol_out.release();
     if (h->d_reset_mask) (void)hipFree(h->d_reset_mask);
     h->term_flags.release();
     if (h->d_rss_state) (void)hipFree(h->d_rss_state);

@@ -1,4 +1,6 @@
-// k_drive.hip -- drive_kernel: the VehicleController step of the drivers of sg_set_drivers (sgym_drive.hpp).
+// k_drive.hip -- drive_kernel: the VehicleController step of the drivers of sg_set_drivers (sgym_drive.hpp); driver_policy_kernel: the
+// built-in policy of sg_set_driver_policy, which makes their actions (sgym_policy.hpp).
+#define SG_UNIT_DRIVE
 #include "sgym_launch.hpp"
 #include "sgym_drive.hpp"
 
@@ -9,5 +11,12 @@ void drive(hipStream_t s, const sg::Params &p, double timestep, const int32_t *s
     if (n <= 0) return;
     sg::drive_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(p.stat, p.dyn, p.sdyn, p.EP, p.FROWS, timestep, scen, slot, n,
                                                                              actions, ext);
+}
+
+void driver_policy(hipStream_t s, const sg::Params &p, const sg::PolicyIndex &P, const int32_t *scen, const int32_t *slot, int64_t m,
+                   const int32_t *row_of, double *actions, int32_t *info, double *feat)
+{
+    if (m <= 0) return;
+    sg::driver_policy_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
 }
 } // namespace sgl

@@ -203,6 +203,13 @@ struct sg_handle {
     int64_t n_drv = 0;                                 // drivers set (0: none); sg_upload forgets them
     sgh::GrowBuf drv_actions{sgh::GrowBuf::DEVICE};    // host actions of sg_step_drivers ([n_steps][n_drv][2] doubles): not `actions`, whose
                                                        // address the captured tick graph holds
+    sgh::GrowBuf policy{sgh::GrowBuf::DEVICE};         // sg_set_driver_policy: the parameter rows, the path totals, the segment rows, the policy
+                                                       // list and the segment ranges, one behind the other (grown on demand)
+    sg::PolicyIndex pol{};                             // ... its pointers into that buffer (driver == nullptr: no policy)
+    int64_t n_pol = 0;                                 // policy drivers set (0: none); sg_set_drivers and sg_upload forget them
+    sgh::GrowBuf pol_actions{sgh::GrowBuf::DEVICE};    // sg_step_drivers_policy: the caller's actions with the policy's rows merged in
+                                                       // ([n_steps][n_drv][2] doubles; a caller's device buffer is never written)
+    sgh::GrowBuf pol_out{sgh::GrowBuf::DEVICE_POISONED}; // device scratch of sg_driver_policy_actions with host outputs
 
     // ---- h_read.hip ----
     // page-locked staging of sg_read_metrics (the per-scenario state and the event table travel every time metrics are read:
@@ -351,6 +358,13 @@ inline void forget_lanes(sg_handle *h)
 {
     free_pool(h->lane_allocs);
     h->lanes = sg::LaneIndex{};
+}
+
+// the policy of sg_set_driver_policy goes with the driver list it indexes (sg_set_drivers, sg_upload); the buffer stays for the next one
+inline void forget_driver_policy(sg_handle *h)
+{
+    h->n_pol = 0;
+    h->pol = sg::PolicyIndex{};
 }
 
 // one group holding every block: an ordinary launch of a table variant

@@ -10,6 +10,7 @@
 #include "sgym_device.hpp"
 #include "sgym_wide.hpp"
 #include "sgym_queue.hpp"
+#include "sgym_policy.hpp"
 
 namespace sgl {
 
@@ -79,6 +80,11 @@ void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, cons
 // All pointers DEVICE.
 void drive(hipStream_t s, const sg::Params &p, double timestep, const int32_t *scen, const int32_t *slot, int64_t n, const double *actions,
            double *ext);
+// driver_policy_kernel (sgym_policy.hpp): the built-in policy for policy driver o < m, driver P.driver[o] of the list (scen, slot): its
+// (accel, steer) on the current state into row (row_of ? row_of[o] : o) of actions [..][2], info [m][SG_DP_NINFO] (or nullptr), feat
+// [m][SG_DP_NFEAT] (or nullptr).  One wavefront per policy driver, any scenario width.  All pointers DEVICE.
+void driver_policy(hipStream_t s, const sg::Params &p, const sg::PolicyIndex &P, const int32_t *scen, const int32_t *slot, int64_t m,
+                   const int32_t *row_of, double *actions, int32_t *info, double *feat);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -105,8 +105,21 @@ def _social_force(who, params):
     return L.SgSocialForce(**d)
 
 
+def idm_params(v0, T=1.5, s0=2.0, a=1.5, b=2.0, half=0.2, reach=80.0, k_psi=1.0, k_e=0.5, k_soft=1.0, gap_min=0.1):
+    """One parameter row of set_driver_policy ([DP_NPARAM] doubles): desired speed v0, time headway T, standstill gap s0, maximum
+    acceleration a and comfortable deceleration b of the Intelligent Driver Model; the corridor's extra half width `half` and its
+    length `reach` (inf: no limit); the steering gains on the heading error (k_psi) and on the lateral offset (k_e, softened by
+    k_soft at low speed); the smallest gap the model divides by (gap_min)."""
+    row = np.zeros(L.DP_NPARAM)
+    row[[L.DP_V0, L.DP_T, L.DP_S0, L.DP_A, L.DP_B, L.DP_HALF, L.DP_REACH, L.DP_K_PSI, L.DP_K_E, L.DP_K_SOFT, L.DP_GAP_MIN]] = (
+        v0, T, s0, a, b, half, reach, k_psi, k_e, k_soft, gap_min)
+    return row
+
+
 class RolloutEngine:
     """ScenarioGym's step loop for a whole batch, resident on one MI355X."""
+
+    idm_params = staticmethod(idm_params)
 
     def __init__(self, n_scenarios, n_entities, timestep=1.0 / 30.0, persist=False,
                  terminal_conditions=None, record_capacity=0, event_capacity=16, device=0, social_force=None):
@@ -267,6 +280,7 @@ class RolloutEngine:
         sc = L.SgScenarios(*[None if arrs[n] is None else arrs[n].ctypes.data for n, _ in L.SgScenarios._fields_])
         self._n_obs = 0  # (sg_upload forgets the observers)
         self._n_drv = 0  # (... and the drivers)
+        self._n_pol = 0  # (... and their policy)
         self._check(self.lib.sg_upload(self.h, C.byref(sc)), "sg_upload")
         self._view = L.SgStateView()
         self._check(self.lib.sg_state_view_get(self.h, C.byref(self._view)), "sg_state_view_get")
@@ -300,6 +314,7 @@ class RolloutEngine:
         self._check(self.lib.sg_set_drivers(self.h, len(scen), scen.ctypes.data if len(scen) else None,
                                             slot.ctypes.data if len(scen) else None), "sg_set_drivers")
         self._n_drv = len(scen)
+        self._n_pol = 0  # (sg_set_drivers forgets the policy)
 
     def step_drivers(self, actions=None, n=1):
         """n x ScenarioGym.step() with the drivers' controllers run on the device (sg_step_drivers): actions [n, n_drivers, 2]
@@ -316,6 +331,56 @@ class RolloutEngine:
             actions = np.ascontiguousarray(actions, np.float64).reshape(n, nd, 2)
             ptr = actions.ctypes.data
         self._check(self.lib.sg_step_drivers(self.h, n, ptr, on_device), "sg_step_drivers")
+
+    def set_driver_policy(self, driver, params, paths):
+        """sg_set_driver_policy: the built-in policy (IDM car-following along a path) runs driver[j] of the set_drivers list with
+        the parameter row params[j] (idm_params) along paths[j], a [k, 2] array of x, y in driving order.  driver: positions in
+        the driver list, strictly ascending.  An empty list clears the policy; set_drivers and upload() forget it; a refused
+        call leaves the previous one in place."""
+        driver = np.ascontiguousarray(driver, np.int64).ravel()
+        m = len(driver)
+        if m == 0:
+            self._check(self.lib.sg_set_driver_policy(self.h, None), "sg_set_driver_policy")
+            self._n_pol = 0
+            return
+        params = np.ascontiguousarray(params, np.float64).reshape(m, L.DP_NPARAM)
+        paths = [np.ascontiguousarray(q, np.float64).reshape(-1, 2) for q in paths]
+        if len(paths) != m:
+            raise ValueError("set_driver_policy: one path per policy driver")
+        pt_off = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int64)
+        pts = np.ascontiguousarray(np.concatenate(paths, axis=0)) if pt_off[-1] else np.zeros((0, 2))
+        pol = L.SgDriverPolicy(m, driver.ctypes.data, params.ctypes.data, pt_off.ctypes.data, pts.ctypes.data if len(pts) else None)
+        self._check(self.lib.sg_set_driver_policy(self.h, C.byref(pol)), "sg_set_driver_policy")
+        self._n_pol = m
+
+    def driver_policy_actions(self, torch_out=False):
+        """The policy of set_driver_policy evaluated on the current state (sg_driver_policy_actions): (actions [m, 2] (accel,
+        steer), info [m, 2] the lead's slot and the best path segment (-1: none), feat [m, 6] gap, closing speed, lateral offset,
+        sine of the heading error, arclength along the path, remaining path).  Empty arrays when no policy is set.  torch_out:
+        torch tensors in HBM the kernel writes directly (waited for, as in entity_status)."""
+        m = getattr(self, "_n_pol", 0)
+        outs, ptrs = self._outputs(torch_out, ((m, 2), "float64"), ((m, L.DP_NINFO), "int32"), ((m, L.DP_NFEAT), "float64"))
+        self._check(self.lib.sg_driver_policy_actions(self.h, *ptrs, int(bool(torch_out))), "sg_driver_policy_actions")
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
+
+    def step_drivers_policy(self, actions=None, n=1):
+        """step_drivers with the built-in policy in the loop (sg_step_drivers_policy): actions [n, n_drivers, 2] as for
+        step_drivers; ahead of every step the rows of the policy drivers are replaced, in a buffer of the handle, by the policy
+        evaluated on the state before that step.  The caller's array is never written."""
+        n, nd = int(n), getattr(self, "_n_drv", 0)
+        ptr, on_device = None, 0
+        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
+            import torch
+
+            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * nd * 2
+            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
+            ptr, on_device = actions.data_ptr(), 1
+        elif actions is not None:
+            actions = np.ascontiguousarray(actions, np.float64).reshape(n, nd, 2)
+            ptr = actions.ctypes.data
+        self._check(self.lib.sg_step_drivers_policy(self.h, n, ptr, on_device), "sg_step_drivers_policy")
 
     def future_collision(self, horizon=5.0, n_samples=10):
         """FutureCollisionDetector (sensor/common.py:59-106) for the ego of every scenario at the current time: bool [R]."""

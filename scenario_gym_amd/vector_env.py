@@ -14,6 +14,10 @@ otherwise (:300-310).  `VectorScenarioEnv` is that loop for R scenarios at once:
 VehicleController in one scenario).  Every listed entity is a driver of the engine (`sg_set_drivers`); a tick is
 `sg_step_drivers` with one (acceleration, steering) per driver, then `sg_terminal_flags`; the observations are those of the
 observer list, which the drivers form by default.
+
+`traffic=`: background traffic that reacts.  Every listed entity is run by the engine's built-in policy (IDM car-following)
+along its own recorded trajectory (`sg_set_driver_policy`): a driver appended behind the caller's drivers, whose actions the
+device makes itself.  A tick is then one `sg_step_drivers_policy`; `step` keeps taking the caller's drivers' actions alone.
 """
 from typing import Optional, Sequence
 
@@ -32,11 +36,17 @@ class VectorScenarioEnv:
                  terminal_conditions: Optional[Sequence[str]] = None, layers: Optional[Sequence[str]] = None,
                  height: float = 30.0, width: float = 30.0, n: int = 128, max_steer: float = 0.9, max_accel: float = 5.0,
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
-                 drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True):
+                 drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True,
+                 traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
         VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
         driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
-        and a reward and a done flag per driver in `info`; False: nothing is added and nothing is launched."""
+        and a reward and a done flag per driver in `info`; False: nothing is added and nothing is launched.
+        traffic: per environment the entity indices the engine's built-in policy runs along their own recorded trajectory
+        (trajectory.data[:, 1:3] as given), each with the same VehicleController; needs `drivers`, and no entity may be in both.
+        traffic_params: None, keyword arguments of idm_params for every traffic entity (a dict), or one parameter row per traffic
+        entity ([n_traffic, DP_NPARAM], environment by environment); v0 defaults to the largest knot-to-knot speed of the
+        entity's recording, floored at 1 m/s."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -48,6 +58,15 @@ class VectorScenarioEnv:
 
         if drivers is not None and len(drivers) != len(self.scenarios):
             raise ValueError("drivers: one list of entity indices per environment")
+        if traffic is not None:
+            if drivers is None:
+                raise ValueError("traffic: needs a driver list (drivers=...)")
+            if len(traffic) != len(self.scenarios):
+                raise ValueError("traffic: one list of entity indices per environment")
+            for i, (ds, ts) in enumerate(zip(drivers, traffic)):
+                both = {int(k) for k in ds} & {int(k) for k in ts}
+                if both:
+                    raise ValueError(f"traffic: entities {sorted(both)} of environment {i} are listed as drivers too")
 
         def create_agent(scenario, entity):  # openaigym.py:280-293: the ego is driven by the policy
             if entity is scenario.ego:
@@ -57,11 +76,15 @@ class VectorScenarioEnv:
 
         packed, _ = pack_scenarios(self.scenarios, create_agent)
         self._drv_env = self._drv_slot = None
+        self._trf_env = self._trf_slot = np.zeros(0, np.int32)
         if drivers is not None:
             # the driven slots: caller-run slots whose VehicleController the device steps itself (sg_set_drivers)
             self._drv_env = np.array([i for i, ks in enumerate(drivers) for _ in ks], np.int32)
             self._drv_slot = np.array([int(k) for ks in drivers for k in ks], np.int32)
-            for i, k in zip(self._drv_env, self._drv_slot):
+            # ... and behind them the traffic, whose actions the built-in policy makes (sg_set_driver_policy)
+            self._trf_env = np.array([i for i, ks in enumerate(traffic or []) for _ in ks], np.int32)
+            self._trf_slot = np.array([int(k) for ks in (traffic or []) for k in ks], np.int32)
+            for i, k in zip(np.concatenate([self._drv_env, self._trf_env]), np.concatenate([self._drv_slot, self._trf_slot])):
                 agent = ExternalVehicleAgent(self.scenarios[i].entities[k], max_steer=max_steer, max_accel=max_accel)
                 packed.kind[int(i) * packed.n_entities + int(k)] = L.KIND_AGENT_EXTERNAL
                 packed.ctrl[int(i) * packed.n_entities + int(k)] = agent.controller.ctrl_row()
@@ -76,12 +99,38 @@ class VectorScenarioEnv:
         self.done = np.zeros(self.n_envs, bool)
         self._obs_env, self._obs_slot = np.zeros(0, np.int32), np.zeros(0, np.int32)  # set_observers
         if drivers is not None:
-            self.engine.set_drivers(self._drv_env, self._drv_slot)
-            self.set_observers(drivers)  # (the default: every driver observes)
+            self.engine.set_drivers(np.concatenate([self._drv_env, self._trf_env]), np.concatenate([self._drv_slot, self._trf_slot]))
+            self.set_observers(drivers)  # (the default: every driver of the caller's observes)
+            if self.n_traffic:
+                self._set_traffic_policy(traffic_params)
+
+    def _set_traffic_policy(self, traffic_params):
+        """The policy rows and paths of the traffic entities: each along its own recorded trajectory."""
+        from .engine import idm_params
+
+        paths, rows = [], []
+        for i, k in zip(self._trf_env, self._trf_slot):
+            data = np.asarray(self.scenarios[i].entities[k].trajectory.data, np.float64)
+            paths.append(data[:, 1:3])
+            dt = np.diff(data[:, 0])
+            speed = np.hypot(np.diff(data[:, 1]), np.diff(data[:, 2]))[dt > 0] / dt[dt > 0]
+            kw = dict(v0=max(1.0, float(speed.max()) if len(speed) else 0.0))
+            if isinstance(traffic_params, dict):
+                kw.update(traffic_params)
+            rows.append(idm_params(**kw))
+        if traffic_params is not None and not isinstance(traffic_params, dict):
+            rows = np.asarray(traffic_params, np.float64).reshape(self.n_traffic, L.DP_NPARAM)
+        self.engine.set_driver_policy(self.n_drivers + np.arange(self.n_traffic), np.array(rows), paths)
 
     @property
     def n_drivers(self):
+        """The caller's drivers (the traffic is not counted: its actions are the engine's)."""
         return 0 if self._drv_env is None else len(self._drv_env)
+
+    @property
+    def n_traffic(self):
+        """The entities the built-in policy runs (`traffic=`)."""
+        return len(self._trf_env)
 
     @property
     def observation_shape(self):
@@ -127,14 +176,24 @@ class VectorScenarioEnv:
 
     def _step_drivers(self, actions):
         """step() with a driver list: actions [n_drivers, 2] in list order (environment by environment, each in the order of
-        its `drivers` entry).  sg_step_drivers, then sg_terminal_flags; reward, done and auto-reset per environment as without
+        its `drivers` entry).  sg_step_drivers (with traffic: sg_step_drivers_policy), then sg_terminal_flags; reward, done and auto-reset per environment as without
         drivers; with driver_status, info also holds driver_flags [n_drivers], driver_info [n_drivers, 4], driver_feat
         [n_drivers, 3] (sg_entity_status_observers on the stepped state, before an auto-reset), driver_reward [n_drivers] (-1 for
         a driver that is off the road or in a collision, else 0.01) and driver_done [n_drivers] (that, or its environment
         done); obs [n_observers, n_layers, n, n] of the observer list (observe_entities)."""
         if not hasattr(actions, "data_ptr"):
             actions = np.asarray(actions, np.float64).reshape(self.n_drivers, 2)
-        self.engine.step_drivers(actions, 1)
+        if self.n_traffic:
+            # the traffic's rows follow the caller's; the policy fills them on the device (one sg_step_drivers_policy per tick)
+            if hasattr(actions, "data_ptr"):
+                import torch
+
+                full = torch.cat([actions.reshape(self.n_drivers, 2), actions.new_zeros((self.n_traffic, 2))]).contiguous()
+            else:
+                full = np.concatenate([actions, np.zeros((self.n_traffic, 2))])
+            self.engine.step_drivers_policy(full, 1)
+        else:
+            self.engine.step_drivers(actions, 1)
         flags = self.engine.terminal_flags()
         done = (flags & self._mask) != 0
         bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
