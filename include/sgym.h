@@ -729,6 +729,65 @@ int sg_entity_status(sg_handle *h, uint32_t *flags, int32_t *info, double *feat,
  * (flags may be NULL then). */
 int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device);
 
+/* Routes: where an entity is supposed to go.  Route j belongs to entity (scenario[j], slot[j]) -- a slot of any kind -- and is
+ * the polyline pts[pt_off[j] .. pt_off[j+1]) ([n_pts][2] doubles, in driving order, used as given; pt_off: [n + 1]).  The
+ * arrays are HOST arrays; the call copies them into buffers the handle owns.  It waits for the work queued on sg_stream(h) (a
+ * queued sg_route_observation may still read the previous routes) and builds one device row per segment a -> b, route by route
+ * in point order, exactly as sg_set_lanes and sg_set_driver_policy build theirs -- a, e = b - a, L2 = ex*ex + ey*ey (unfused),
+ * len = sqrt(L2), cum = the arclength of a within its route as the sequential fp64 sum of the preceding len (0 for the first
+ * segment), b -- per route total = cum + len of its last segment (0 without segments), and a map from the entity to its route:
+ * observers are looked up by entity, not by their position in a list.  A route of fewer than two points has no segments.
+ * n == 0 clears the routes (the arrays may be NULL then).  sg_upload forgets them; sg_reset, sg_reset_scenarios, sg_step*,
+ * sg_set_observers, sg_set_drivers and sg_set_driver_policy keep them (the policy's own paths are separate).
+ * SG_ERR_STATE before sg_upload.  SG_ERR_INVALID: n < 0, a NULL array that is needed, a scenario or slot out of range, a
+ * (scenario, slot) pair listed twice, pt_off not starting at 0 or not monotone, 2^31 or more segments, a coordinate that is not
+ * finite, a route whose total is not finite.  A refused call leaves the previous routes in place. */
+#define SG_ROUTE_MAX_AHEAD 16 /* route points ahead per observer */
+#define SG_RT_NINFO 2
+#define SG_RT_NFEAT 11        /* + 2 * n_ahead */
+int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot, const int64_t *pt_off, const double *pts);
+
+/* The route and recorded-track observation of the ego of every scenario (n = n_scenarios observers): where the vehicle is
+ * along its route of sg_set_routes, where the route goes next, and how far the vehicle is from where its own recording has it
+ * at the current time (the "log divergence" of log-replay simulators).  The reference has no such sensor; the recorded pose is
+ * its Trajectory.position_at_t.  Plain fp64 with IEEE division and square root, no fused operation.
+ * The observer is slot so of scenario r with pose (px, py, h) and (s, c) = sin, cos of h; t is sg_scenario_state.t of r.  An
+ * observer that is NOT in State.poses (the presence rule of sg_nearest_entities) gets info -1, -1 and every feature +0.0.  For
+ * an observer that is in State.poses:
+ *   the recorded track -- with kn the observer's own knots and n_k their number, (xr, yr, ., hr, ., .) is
+ *     Trajectory.position_at_t(t) with the default extrapolate=(False, False): the first knot before its time, the last knot
+ *     after its time, the linear interpolation between (a single knot: that knot).  X = xr - px, Y = yr - py, (sr, cr) = sin,
+ *     cos of hr:
+ *     feat[o][0] X*c + Y*s and feat[o][1] Y*c - X*s, where the recording is in the observer's frame; feat[o][2] sqrt(X*X + Y*Y);
+ *     feat[o][3] cr*c + sr*s and feat[o][4] sr*c - cr*s, cos and sin of the recorded heading relative to the observer's
+ *     info[o][1]  0 when kn[0].t <= t <= kn[n_k - 1].t, -1 when t is before the first knot, 1 when it is after the last;
+ *                 2 with n_k == 0, and feat[o][0..4] are +0.0 then
+ *   the route -- over the segments of the observer's route, (d2, dx, dy, t_seg) by the point-to-segment rule of
+ *     sg_lane_observation (a segment whose d2 is not finite is skipped); the best segment g is the smallest (d2, index within
+ *     the route).  With (ux, uy) = (ex/len, ey/len), or (0, 0) when len == 0:
+ *     feat[o][5] ux*dy - uy*dx, the lateral offset, left of the route direction positive; feat[o][6] c*ux + s*uy and feat[o][7]
+ *     s*ux - c*uy, cos and sin of the observer's heading relative to the route (not saturated: feat[o][6] < 0 says wrong way);
+ *     feat[o][8] s0 = cum + t_seg*len, the arclength along the route; feat[o][9] total - s0; feat[o][10] sqrt(d2)
+ *     info[o][0]  g's index within the route
+ *     Without a route, or with a route that has no (finite) segment: info[o][0] = -1 and feat[o][5 ..] are +0.0
+ *   the look-ahead -- for m = 1..n_ahead, target = s0 + (double)m * spacing.  If target > total the point is b of the route's
+ *     last segment.  Otherwise with g' the last segment of the route with cum[g'] <= target (cum is non-decreasing and
+ *     cum[0] == 0 <= s0: a binary search) and u = (target - cum[g']) / len[g'] (0 when len[g'] == 0) the point is b of g' when
+ *     u >= 1, else (ax + u*ex, ay + u*ey).  With X = x - px, Y = y - py: feat[o][11 + 2(m-1)] = X*c + Y*s and
+ *     feat[o][12 + 2(m-1)] = Y*c - X*s.  The rule of sg_lane_observation without the successor walk.
+ * feat: [n][SG_RT_NFEAT + 2*n_ahead] doubles, required; info: [n][SG_RT_NINFO], may be NULL.  Every byte of the arrays given is
+ * written.  HOST (outputs_device == 0, synchronous, through the observation scratch) or DEVICE (queued on sg_stream(h), not
+ * waited for), as in sg_nearest_entities, and a persistent rollout launch that gave up is reported as in sg_entity_status.
+ * SG_ERR_INVALID: n_ahead outside 0..SG_ROUTE_MAX_AHEAD, spacing NaN, negative or infinite, feat NULL.  SG_ERR_STATE before
+ * sg_upload.  Without sg_set_routes the call succeeds: the track part is filled, the route part is -1 / zeros.  One wavefront
+ * per observer tests every segment of its route, 64 at a time; any scenario width.  Not part of the sg_tick graph. */
+int sg_route_observation(sg_handle *h, int32_t n_ahead, double spacing, double *feat, int32_t *info, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_route_observation for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_route_observation_observers(sg_handle *h, int32_t n_ahead, double spacing, double *feat, int32_t *info, int32_t outputs_device);
+
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).
  * actions: [n_scenarios][2] HOST (actions_device = 0) or DEVICE, or NULL for (0, 0).  Asynchronous: the work is queued on

@@ -30,7 +30,7 @@ from .agent import (  # noqa: F401
 from .engine import PackedScenarios, RolloutEngine, idm_params  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
-    RangeScanObservation, SingleEntityObservation,
+    RangeScanObservation, RouteObservation, SingleEntityObservation,
     combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401

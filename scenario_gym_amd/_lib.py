@@ -21,6 +21,8 @@ ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
 # SG_DP_* of sg_set_driver_policy: the columns of a parameter row, its width, the widths of the info and feature rows
 (DP_V0, DP_T, DP_S0, DP_A, DP_B, DP_HALF, DP_REACH, DP_K_PSI, DP_K_E, DP_K_SOFT, DP_GAP_MIN) = range(11)
 DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
+# SG_ROUTE_MAX_AHEAD / SG_RT_* of sg_route_observation: the points ahead, the widths of the info row and of the feature row (+ 2 * n_ahead)
+ROUTE_MAX_AHEAD, RT_NINFO, RT_NFEAT = 16, 2, 11
 NCTRL = 16
 NOISE_OFF, NOISE_STREAM, NOISE_DEVICE = 0, 1, 2  # sg_set_ped_noise
 PED_SOCIAL_FORCE, PED_RANDOM_WALK = 0, 1         # sg_set_ped_behaviour
@@ -46,6 +48,7 @@ SYMBOLS = (
     "sg_set_drivers", "sg_step_drivers",
     "sg_entity_status", "sg_entity_status_observers",
     "sg_set_driver_policy", "sg_driver_policy_actions", "sg_step_drivers_policy",
+    "sg_set_routes", "sg_route_observation", "sg_route_observation_observers",
 )
 
 
@@ -232,6 +235,9 @@ def load():
     lib.sg_set_driver_policy.argtypes = [H, C.POINTER(SgDriverPolicy)]
     lib.sg_driver_policy_actions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_step_drivers_policy.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
+    lib.sg_set_routes.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sg_route_observation.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_route_observation_observers.argtypes = lib.sg_route_observation.argtypes
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -119,20 +119,7 @@ extern "C" int sg_set_driver_policy(sg_handle *h, const sg_driver_policy *pol)
         ints[(size_t)j] = (int32_t)pol->driver[j];
         const int32_t first = (int32_t)segs.size();
         ints[(size_t)(m + j)] = first;
-        double cum = 0.0;
-        for (int64_t i = pol->pt_off[j]; i + 1 < pol->pt_off[j + 1]; ++i) {
-            const double *a = pol->pts + 2 * i, *b = a + 2;
-            sg::LaneSeg g{};
-            g.ax = a[0]; g.ay = a[1]; g.bx = b[0]; g.by = b[1];
-            g.ex = g.bx - g.ax; g.ey = g.by - g.ay;
-            g.L2 = g.ex * g.ex + g.ey * g.ey;
-            g.len = std::sqrt(g.L2);
-            g.cum = cum;
-            g.lane = (int32_t)j; g.first = first;
-            cum = cum + g.len;
-            segs.push_back(g);
-        }
-        dbl[(size_t)m * SG_DP_NPARAM + j] = (int32_t)segs.size() > first ? segs.back().cum + segs.back().len : 0.0;
+        dbl[(size_t)m * SG_DP_NPARAM + j] = append_segments(segs, pol->pts, pol->pt_off[j], pol->pt_off[j + 1], (int32_t)j, first);
     }
     ints[(size_t)(2 * m)] = (int32_t)segs.size();
     HIP_TRY(h, hipSetDevice(h->cfg.device));

@@ -154,6 +154,7 @@ extern "C" int sg_destroy(sg_handle *h)
     h->obs.release();
     h->road_info.release();
     h->observers.release();
+    h->routes.release();
     h->drivers.release();
     h->drv_actions.release();
     h->policy.release();

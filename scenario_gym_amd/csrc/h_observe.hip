@@ -1,5 +1,5 @@
 // h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity,
-// lane-frame and range-scan observations and the episode status of the ego and of a list of observers.
+// lane-frame, range-scan and route observations and the episode status of the ego and of a list of observers; the routes.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -409,4 +409,96 @@ extern "C" int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t
 {
     if (!h) return SG_ERR_INVALID;
     return status_call(h, "sg_entity_status_observers", true, flags, info, feat, outputs_device);
+}
+
+// ---- routes and the route / recorded-track observation (route_observation_kernel, sgym_observers.hpp) ------------------------
+extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot, const int64_t *pt_off, const double *pts)
+{
+    const char *who = "sg_set_routes";
+    if (!h) return SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    // (a refused call leaves the routes as they were: everything is checked before anything is changed)
+    if (n < 0 || (n > 0 && (!scenario || !slot || !pt_off))) return fail(h, SG_ERR_INVALID, "%s: n < 0 or null array", who);
+    if (n == 0) {
+        forget_routes(h);
+        return SG_OK;
+    }
+    if (n > (int64_t)h->R * h->E) return fail(h, SG_ERR_INVALID, "%s: more routes than entity slots: a pair is listed twice", who);
+    std::vector<int32_t> ints((size_t)(n + 1) + (size_t)h->R * h->EP, -1); // seg_off [n + 1], then route_of [R * EP]
+    int32_t *const route_of = ints.data() + (n + 1);
+    int64_t n_seg = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        if (scenario[j] < 0 || scenario[j] >= h->R) return fail(h, SG_ERR_INVALID, "%s: scenario[%lld]=%d out of range", who, (long long)j, scenario[j]);
+        if (slot[j] < 0 || slot[j] >= h->E) return fail(h, SG_ERR_INVALID, "%s: slot[%lld]=%d out of range", who, (long long)j, slot[j]);
+        int32_t &of = route_of[(size_t)scenario[j] * h->EP + slot[j]];
+        if (of >= 0) return fail(h, SG_ERR_INVALID, "%s: slot %d of scenario %d is listed twice", who, slot[j], scenario[j]);
+        of = (int32_t)j;
+        if (pt_off[0] != 0 || pt_off[j + 1] < pt_off[j]) return fail(h, SG_ERR_INVALID, "%s: pt_off not monotone from 0", who);
+        n_seg += std::max<int64_t>(pt_off[j + 1] - pt_off[j] - 1, 0);
+        if (n_seg >= 0x80000000LL) return fail(h, SG_ERR_INVALID, "%s: 2^31 or more segments", who);
+    }
+    const int64_t n_pts = pt_off[n];
+    if (n_pts > 0 && !pts) return fail(h, SG_ERR_INVALID, "%s: null pts", who);
+    for (int64_t i = 0; i < 2 * n_pts; ++i)
+        if (!std::isfinite(pts[i])) return fail(h, SG_ERR_INVALID, "%s: pts[%lld] is not finite", who, (long long)(i / 2));
+    // the rows of sg_set_lanes (h_road.hip), route by route
+    std::vector<sg::LaneSeg> segs;
+    segs.reserve((size_t)n_seg);
+    std::vector<double> total((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+        const int32_t first = (int32_t)segs.size();
+        ints[(size_t)j] = first;
+        total[(size_t)j] = append_segments(segs, pts, pt_off[j], pt_off[j + 1], (int32_t)j, first);
+        if (!std::isfinite(total[(size_t)j])) return fail(h, SG_ERR_INVALID, "%s: the length of route %lld is not finite", who, (long long)j);
+    }
+    ints[(size_t)n] = (int32_t)segs.size();
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued sg_route_observation may still read the previous routes)
+    forget_routes(h); // (from here on the old routes are gone: a failure of the runtime leaves the handle without any)
+    const size_t b_dbl = total.size() * sizeof(double), b_seg = segs.size() * sizeof(sg::LaneSeg), b_int = ints.size() * sizeof(int32_t);
+    if (const int rc = h->routes.ensure(h, b_dbl + b_seg + b_int)) return rc;
+    unsigned char *base = h->routes.as<unsigned char>();
+    HIP_TRY(h, hipMemcpy(base, total.data(), b_dbl, hipMemcpyHostToDevice));
+    if (b_seg) HIP_TRY(h, hipMemcpy(base + b_dbl, segs.data(), b_seg, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(base + b_dbl + b_seg, ints.data(), b_int, hipMemcpyHostToDevice));
+    h->route.total = reinterpret_cast<const double *>(base);
+    h->route.seg = reinterpret_cast<const sg::LaneSeg *>(base + b_dbl);
+    h->route.seg_off = reinterpret_cast<const int32_t *>(base + b_dbl + b_seg);
+    h->route.route_of = h->route.seg_off + (n + 1);
+    return SG_OK;
+}
+
+// n observers as above.  Host outputs pass through the observation scratch, the doubles first: [n][SG_RT_NFEAT + 2 * n_ahead]
+// doubles, then [n][SG_RT_NINFO] ints (only when asked for).
+static int route_call(sg_handle *h, const char *who, bool observers, int32_t n_ahead, double spacing, double *feat, int32_t *info,
+                      int32_t outputs_device)
+{
+    if (n_ahead < 0 || n_ahead > SG_ROUTE_MAX_AHEAD) return fail(h, SG_ERR_INVALID, "%s: n_ahead=%d outside 0..%d", who, n_ahead, SG_ROUTE_MAX_AHEAD);
+    if (!(spacing >= 0.0) || std::isinf(spacing)) return fail(h, SG_ERR_INVALID, "%s: spacing is negative, infinite or NaN", who);
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
+    return deliver(h, who, outputs_device, obs_scratch,
+                   {{feat, (size_t)n * (SG_RT_NFEAT + 2 * (size_t)n_ahead) * sizeof(double)}, {info, (size_t)n * SG_RT_NINFO * sizeof(int32_t)}}, 0,
+                   [&](void *const *d) {
+                       sgl::route_observation(h->stream, h->p, h->route, d_scen, d_slot, n, n_ahead, spacing, static_cast<double *>(d[0]),
+                                              static_cast<int32_t *>(d[1]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_route_observation(sg_handle *h, int32_t n_ahead, double spacing, double *feat, int32_t *info, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return route_call(h, "sg_route_observation", false, n_ahead, spacing, feat, info, outputs_device);
+}
+
+extern "C" int sg_route_observation_observers(sg_handle *h, int32_t n_ahead, double spacing, double *feat, int32_t *info,
+                                              int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return route_call(h, "sg_route_observation_observers", true, n_ahead, spacing, feat, info, outputs_device);
 }

@@ -292,8 +292,9 @@ extern "C" int sg_set_road_networks(sg_handle *h, const sg_road_networks *in)
 }
 
 // ---- lane centre lines (lane_observation_kernel, sgym_observers.hpp) --------------------------------------------------
-// One device row per centre-line segment, lane by lane in point order.  This unit is compiled with -ffp-contract=off like the
-// rest of the library: the products and sums below are the unfused ones the definition in include/sgym.h names.
+// One device row per centre-line segment, lane by lane in point order, built by append_segments (sgym_host.hpp).  This unit is
+// compiled with -ffp-contract=off like the rest of the library: its products and sums are the unfused ones the definition in
+// include/sgym.h names.
 extern "C" int sg_set_lanes(sg_handle *h, const sg_lanes *in)
 {
     if (!h || !in) return h ? fail(h, SG_ERR_INVALID, "sg_set_lanes: null argument") : SG_ERR_INVALID;
@@ -332,21 +333,8 @@ extern "C" int sg_set_lanes(sg_handle *h, const sg_lanes *in)
         for (int64_t q = l0; q < l1; ++q) {
             sg::LaneRow &row = rows[(size_t)q];
             row.seg0 = (int32_t)segs.size();
-            double cum = 0.0;
-            for (int64_t i = in->pt_off[q]; i + 1 < in->pt_off[q + 1]; ++i) {
-                const double *a = in->pts + 2 * i, *b = a + 2;
-                sg::LaneSeg g{};
-                g.ax = a[0]; g.ay = a[1]; g.bx = b[0]; g.by = b[1];
-                g.ex = g.bx - g.ax; g.ey = g.by - g.ay;
-                g.L2 = g.ex * g.ex + g.ey * g.ey;
-                g.len = std::sqrt(g.L2);
-                g.cum = cum;
-                g.lane = (int32_t)q; g.first = row.seg0;
-                cum = cum + g.len;
-                segs.push_back(g);
-            }
+            row.total = append_segments(segs, in->pts, in->pt_off[q], in->pt_off[q + 1], (int32_t)q, row.seg0);
             row.seg1 = (int32_t)segs.size();
-            row.total = row.seg1 > row.seg0 ? segs.back().cum + segs.back().len : 0.0;
             row.succ0 = (int32_t)succ.size();
             for (int64_t m = in->succ_off[q]; m < in->succ_off[q + 1]; ++m) succ.push_back((int32_t)(l0 + in->succ[m]));
             std::sort(succ.begin() + row.succ0, succ.end()); // ascending, each once: "the lowest-index successor" is the first that has segments

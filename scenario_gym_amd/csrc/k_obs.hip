@@ -1,6 +1,7 @@
 // k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel /
-// entity_status_kernel: the map, look-ahead, nearest-entity, lane-frame and range-scan observations and the episode status of the
-// ego of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
+// entity_status_kernel / route_observation_kernel: the map, look-ahead, nearest-entity, lane-frame, range-scan and route
+// observations and the episode status of the ego of every scenario or of a list of observers (scenario, slot), any entity of its
+// scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -59,5 +60,12 @@ void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, cons
 {
     if (n <= 0) return;
     sg::entity_status_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, flags, info, feat);
+}
+
+void route_observation(hipStream_t s, const sg::Params &p, const sg::RouteIndex &P, const int32_t *scen, const int32_t *slot, int64_t n,
+                       int n_ahead, double spacing, double *feat, int32_t *info)
+{
+    if (n <= 0) return;
+    sg::route_observation_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, P, scen, slot, n, n_ahead, spacing, feat, info);
 }
 } // namespace sgl

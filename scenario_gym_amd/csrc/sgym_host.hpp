@@ -196,6 +196,10 @@ struct sg_handle {
     // ---- h_observe.hip: the observers ----
     sgh::GrowBuf observers{sgh::GrowBuf::DEVICE};      // sg_set_observers: [2][capacity] int32_t, scenario and slot of every observer (grown on demand)
     int64_t n_obs = 0;                                 // observers set (0: none); sg_upload forgets them
+    sgh::GrowBuf routes{sgh::GrowBuf::DEVICE};         // sg_set_routes: the route totals, the segment rows, the segment ranges and the
+                                                       // entity -> route map, one behind the other (grown on demand)
+    sg::RouteIndex route{};                            // ... its pointers into that buffer (route_of == nullptr: no routes); sg_upload
+                                                       // forgets them (forget_routes)
 
     // ---- h_drive.hip: the drivers ----
     std::vector<uint8_t> slot_external;                // [R * E] the slot is SG_KIND_AGENT_EXTERNAL in the uploaded batch (what sg_set_drivers asks for)
@@ -365,6 +369,34 @@ inline void forget_driver_policy(sg_handle *h)
 {
     h->n_pol = 0;
     h->pol = sg::PolicyIndex{};
+}
+
+// the routes of sg_set_routes belong to entities of a batch (sg_upload); the buffer stays for the next ones
+inline void forget_routes(sg_handle *h) { h->route = sg::RouteIndex{}; }
+
+// The device rows of one polyline pts[i0 .. i1) ([..][2] doubles), appended to segs: one row per segment a -> b in point order -- a,
+// e = b - a, L2 = ex*ex + ey*ey, len = sqrt(L2), cum = the sequential sum of the preceding len, b -- tagged (lane, first).  Returns
+// the polyline's total, cum + len of its last segment (0 without segments).  What sg_set_lanes, sg_set_driver_policy and
+// sg_set_routes build their rows with; the host units are compiled with -ffp-contract=off: the products and sums are the unfused
+// ones the definitions in include/sgym.h name.
+inline double append_segments(std::vector<sg::LaneSeg> &segs, const double *pts, int64_t i0, int64_t i1, int32_t lane, int32_t first)
+{
+    double cum = 0.0;
+    bool any = false;
+    for (int64_t i = i0; i + 1 < i1; ++i) {
+        const double *a = pts + 2 * i, *b = a + 2;
+        sg::LaneSeg g{};
+        g.ax = a[0]; g.ay = a[1]; g.bx = b[0]; g.by = b[1];
+        g.ex = g.bx - g.ax; g.ey = g.by - g.ay;
+        g.L2 = g.ex * g.ex + g.ey * g.ey;
+        g.len = std::sqrt(g.L2);
+        g.cum = cum;
+        g.lane = lane; g.first = first;
+        cum = cum + g.len;
+        segs.push_back(g);
+        any = true;
+    }
+    return any ? segs.back().cum + segs.back().len : 0.0;
 }
 
 // one group holding every block: an ordinary launch of a table variant

@@ -74,6 +74,11 @@ void range_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const i
 // nullptr), feat [n][SG_ST_NFEAT] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
 void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, uint32_t *flags, int32_t *info,
                    double *feat);
+// route_observation_kernel: where observer o < n (the same two lists) is relative to its route of sg_set_routes (P.route_of ==
+// nullptr: none set) with n_ahead <= SG_ROUTE_MAX_AHEAD points ahead, and relative to its own recording at the scenario's time.
+// feat [n][SG_RT_NFEAT + 2 * n_ahead], info [n][SG_RT_NINFO] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
+void route_observation(hipStream_t s, const sg::Params &p, const sg::RouteIndex &P, const int32_t *scen, const int32_t *slot, int64_t n,
+                       int n_ahead, double spacing, double *feat, int32_t *info);
 // k_drive.hip (sgym_drive.hpp): drive_kernel, one lane per driver d < n: the VehicleController step of entity (scen[d], slot[d]) with
 // actions[d] = (accel, steer) (nullptr: (0, 0)) from its current pose, into row (scen[d] * EP + slot[d]) of ext, the handle's
 // external-pose buffer [NE][6] -- NaN for a driver that is not in the scene; the controller speed in the slot's SG_F_CTRL + 0 cell.

@@ -836,4 +836,131 @@ static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, con
 }
 #endif // SG_UNIT_OBS
 
+// ------------------------------------------------------------------------------------------------
+// The route and recorded-track observation: where an observer is relative to the route it was given (sg_set_routes) and to
+// where its own recording has it at the scenario's time -- progress along the route, what is left of it, points ahead, and the
+// displacement from the log (no counterpart in the reference, whose entities replay or are driven, never compared).  The
+// definition is in include/sgym.h at sg_route_observation: plain unfused fp64 with IEEE division and square root.  The route
+// rows are LaneSeg rows built by sg_set_routes exactly as sg_set_lanes builds its own; the point-to-segment rule is lane_project
+// and the recorded pose own_position_clamped, called, not restated; presence and the entity frame are those of nearest_kernel.
+// ------------------------------------------------------------------------------------------------
+struct RouteIndex {      // device pointers, by value; route_of == nullptr: no routes set
+    const int32_t *route_of; // [R * EP] padded entity index -> route, -1 where the entity has none
+    const int32_t *seg_off;  // [n_routes + 1] ranges of seg
+    const double *total;     // [n_routes] cum + len of the route's last segment (0 without segments)
+    const LaneSeg *seg;      // the segments of every route, route by route
+};
+
+// Observer o < n as in nearest_kernel; feat [n][SG_RT_NFEAT + 2 * n_ahead], info [n][SG_RT_NINFO] (may be nullptr), every byte
+// written.  One wavefront per observer, four per workgroup, no LDS, no barrier, no atomics.  What belongs to the observer alone
+// -- its pose, its recorded pose, the best row -- is the same in every lane: each lane loads and computes it for itself, as in
+// entity_status_kernel.
+//   phase one, lane = route segment: the lanes stride over the route's rows (a load is 64 consecutive 80-byte rows) and keep the
+//     smallest (d2 bits, index within the route); near_wave_min makes it the wavefront's.  Every lane then projects onto the best
+//     row again: the same operations on the same operands, so the same bits.
+//   phase two, lane m - 1 = look-ahead point m: its own binary search over cum, its own point.
+//   the store, lane = feature: the row is at most 11 + 2 * 16 = 43 doubles, one pass; the look-ahead pairs come from their lanes
+//     by a cross-lane read.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void route_observation_kernel(Params p, RouteIndex P, const int32_t *obs_scen, const int32_t *obs_slot,
+                                                                       int64_t n, int n_ahead, double spacing, double *feat, int32_t *info)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t o = (int64_t)blockIdx.x * 4 + w;
+    if (o >= n) return; // (the whole wavefront, which meets no barrier)
+    const int W = SG_RT_NFEAT + 2 * n_ahead;
+    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    double *row = feat + (size_t)o * W;
+    if (!f.present) { // not in State.poses
+        if (lane < W) row[lane] = 0.0;
+        if (info && lane < SG_RT_NINFO) info[(size_t)o * SG_RT_NINFO + lane] = -1;
+        return;
+    }
+    const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)f.slot;
+
+    // the recorded track
+    const int64_t *sti = reinterpret_cast<const int64_t *>(near_stat(p, idx));
+    const int n_k = (int)(sti[ST_META * 64] >> 32);
+    double tr0 = 0.0, tr1 = 0.0, tr2 = 0.0, tr3 = 0.0, tr4 = 0.0;
+    int when = 2;
+    if (n_k > 0) {
+        const double *kn = p.knots + sti[ST_KNOT_OFF * 64] * 7;
+        const double t = p.sdyn[f.r].t;
+        double rec[6], sr, cr;
+        own_position_clamped(kn, n_k, t, rec);
+        const double X = rec[0] - f.x, Y = rec[1] - f.y;
+        sg_sincos(rec[3], sr, cr);
+        tr0 = X * f.c + Y * f.s;
+        tr1 = Y * f.c - X * f.s;
+        tr2 = __builtin_sqrt(X * X + Y * Y);
+        tr3 = cr * f.c + sr * f.s;
+        tr4 = sr * f.c - cr * f.s;
+        when = t < kn[0] ? -1 : t > kn[(size_t)(n_k - 1) * 7] ? 1 : 0;
+    }
+
+    // the route: phase one
+    const int route = P.route_of ? P.route_of[idx] : -1;
+    const int s0i = route >= 0 ? P.seg_off[route] : 0, s1i = route >= 0 ? P.seg_off[route + 1] : 0;
+    uint64_t bk = NEAR_NONE;
+    int bs = NEAR_NO_SLOT;
+    for (int i0 = s0i; i0 < s1i; i0 += 64) {
+        const int i = i0 + lane;
+        const LaneSeg g = P.seg[min(i, s1i - 1)];
+        double dx, dy, t;
+        const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
+        const bool take = i < s1i && d2 < __builtin_inf() && (uint64_t)__double_as_longlong(d2) < bk; // (a NaN fails; ascending i per lane)
+        bk = take ? (uint64_t)__double_as_longlong(d2) : bk;
+        bs = take ? i - s0i : bs;
+    }
+    near_wave_min(bk, bs);
+    const bool on_route = bk != NEAR_NONE; // (the same in every lane)
+    double rt0 = 0.0, rt1 = 0.0, rt2 = 0.0, rt3 = 0.0, rt4 = 0.0, rt5 = 0.0, ah0 = 0.0, ah1 = 0.0;
+    if (on_route) {
+        const LaneSeg g = P.seg[s0i + bs];
+        double dx, dy, t;
+        const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
+        const double ux = g.len == 0.0 ? 0.0 : g.ex / g.len, uy = g.len == 0.0 ? 0.0 : g.ey / g.len;
+        const double total = P.total[route];
+        rt0 = ux * dy - uy * dx;
+        rt1 = f.c * ux + f.s * uy;
+        rt2 = f.s * ux - f.c * uy;
+        rt3 = g.cum + t * g.len;
+        rt4 = total - rt3;
+        rt5 = __builtin_sqrt(d2);
+        // phase two
+        if (lane < n_ahead) {
+            const double target = rt3 + (double)(lane + 1) * spacing;
+            double x, y;
+            if (target > total) { // beyond the end: the route's last point
+                x = P.seg[s1i - 1].bx; y = P.seg[s1i - 1].by;
+            } else {
+                int lo = s0i, hi = s1i; // the last segment with cum <= target (cum[s0i] = 0 <= s0 <= target)
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (P.seg[mid].cum <= target) lo = mid; else hi = mid;
+                }
+                const LaneSeg q = P.seg[lo];
+                const double u = q.len == 0.0 ? 0.0 : (target - q.cum) / q.len;
+                if (u >= 1.0) { x = q.bx; y = q.by; }
+                else { x = q.ax + u * q.ex; y = q.ay + u * q.ey; }
+            }
+            const double X = x - f.x, Y = y - f.y;
+            ah0 = X * f.c + Y * f.s;
+            ah1 = Y * f.c - X * f.s;
+        }
+    }
+
+    // the store (the cross-lane reads are the whole wavefront's)
+    const int from = lane >= SG_RT_NFEAT ? (lane - SG_RT_NFEAT) >> 1 : 0; // (< 64)
+    const double a0 = __shfl(ah0, from, 64), a1 = __shfl(ah1, from, 64);
+    if (lane < W) {
+        const double v = lane == 0 ? tr0 : lane == 1 ? tr1 : lane == 2 ? tr2 : lane == 3 ? tr3 : lane == 4 ? tr4
+                       : lane == 5 ? rt0 : lane == 6 ? rt1 : lane == 7 ? rt2 : lane == 8 ? rt3 : lane == 9 ? rt4 : lane == 10 ? rt5
+                       : ((lane - SG_RT_NFEAT) & 1) ? a1 : a0;
+        row[lane] = v;
+    }
+    if (info && lane < SG_RT_NINFO) info[(size_t)o * SG_RT_NINFO + lane] = lane == 0 ? (on_route ? bs : -1) : when;
+}
+#endif // SG_UNIT_OBS
+
 } // namespace sg

@@ -476,7 +476,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -634,6 +634,44 @@ class RolloutEngine:
         """entity_status for every observer of set_observers (sg_entity_status_observers): (flags [n], info [n, 4], feat
         [n, 3]); empty arrays when no observers are set."""
         return self._entity_status(self.lib.sg_entity_status_observers, self._n_obs, torch_out)
+
+    def set_routes(self, scenario, slot, paths):
+        """sg_set_routes: where entities are supposed to go.  Route j belongs to entity slot[j] of scenario scenario[j] (any
+        entity, each at most once) and is the polyline paths[j] ([n_pts, 2], in driving order, used as given; fewer than two
+        points: no segments).  Needed by the route part of route_observation; an empty list clears the routes, upload() forgets
+        them, and a refused call leaves the previous ones in place."""
+        scen = np.ascontiguousarray(scenario, np.int32).ravel()
+        slot = np.ascontiguousarray(slot, np.int32).ravel()
+        paths = [np.ascontiguousarray(q, np.float64).reshape(-1, 2) for q in paths]
+        if not (len(scen) == len(slot) == len(paths)):
+            raise ValueError("set_routes: one scenario, one slot and one path per route")
+        if len(scen) == 0:
+            self._check(self.lib.sg_set_routes(self.h, 0, None, None, None, None), "sg_set_routes")
+            return
+        pt_off = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int64)
+        pts = np.ascontiguousarray(np.concatenate(paths, axis=0)) if pt_off[-1] else np.zeros((0, 2))
+        self._check(self.lib.sg_set_routes(self.h, len(scen), scen.ctypes.data, slot.ctypes.data, pt_off.ctypes.data,
+                                           pts.ctypes.data if len(pts) else None), "sg_set_routes")
+
+    def route_observation(self, n_ahead=4, spacing=2.0, observers=False, device=False):
+        """The route and recorded-track observation (sg_route_observation; observers: sg_route_observation_observers, for every
+        observer of set_observers instead of the ego of every scenario).  Returns (feat [n, 11 + 2 * n_ahead] float64, info
+        [n, 2] int32).  feat: [0:2] where the entity's own recording has it at the current time, in the entity's frame, [2] the
+        distance to it, [3:5] cos and sin of the recorded heading relative to the entity's; [5] the lateral offset from its route
+        of set_routes (left positive), [6:8] cos and sin of its heading relative to the route, [8] the arclength along the
+        route, [9] what is left of it, [10] the distance to it; then n_ahead <= 16 route points `spacing` apart ahead of the
+        entity, in its frame, held at the route's last point.  info: the best route segment (-1: no route, or none with
+        segments; features 5 and up are zero then), and where the current time lies in the recording (0 within, -1 before its
+        first knot, 1 after its last).  An entity that is not in the scene: info -1, -1 and zeros.  device: torch tensors in
+        HBM the kernel writes directly (waited for, as in entity_status)."""
+        n_ahead = int(n_ahead)
+        n = self._n_obs if observers else self.R
+        call = self.lib.sg_route_observation_observers if observers else self.lib.sg_route_observation
+        outs, ptrs = self._outputs(device, ((n, L.RT_NFEAT + 2 * max(n_ahead, 0)), "float64"), ((n, L.RT_NINFO), "int32"))
+        self._check(call(self.h, n_ahead, float(spacing), *ptrs, int(bool(device))), call.__name__)
+        if device:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

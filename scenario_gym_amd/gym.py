@@ -213,6 +213,7 @@ class BatchedScenarioGym:
         self.scenarios, self.states, self._host_agents, self._policy_agents, self._driver_agents = [], [], [], [], []
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
         self._roads_set, self._lanes_set = True, False
+        self._routes, self._routes_set = None, False
         self.metrics = [list(self.metric_factory()) for _ in range(packed.n_scenarios)]
         if any(not isinstance(m, _DeviceMetric) for m in self.metrics[0]):
             raise ValueError("set_packed: device metrics only")
@@ -279,6 +280,7 @@ class BatchedScenarioGym:
             self.engine.set_rss(True)
         self.engine.upload(packed)
         self._roads_set = self._lanes_set = False
+        self._routes, self._routes_set = None, False
         # the road network reaches the device when the rollout itself needs it: the ego_off_road terminal condition, and
         # pedestrian agents (the boundary terms of the social force, social_force.py:86-104)
         if "ego_off_road" in dev_terms or (sf is not None and any(sc.road_network is not None for sc in self.scenarios)):
@@ -430,6 +432,35 @@ class BatchedScenarioGym:
             return call(k, n_ahead, spacing, radius)
 
         return self._cached(("lane", observers, k, n_ahead, spacing, radius), compute, observers=observers)
+
+    def set_routes(self, paths=None):
+        """The routes of the route observation (State.route_observation): paths[i] = {entity index: polyline [n_pts, 2]} for
+        scenario i.  None (the default when a route observation is first asked for): every entity's own recorded
+        trajectory.data[:, 1:3].  They go down when a route observation is next asked for; set_scenarios forgets them."""
+        if paths is not None and len(paths) != len(self.scenarios):
+            raise ValueError("set_routes: one dict of entity index -> path per scenario")
+        self._routes, self._routes_set = paths, False
+        if self._fut:
+            self._fut = {key: ent for key, ent in self._fut.items() if key[0] != "route"}
+
+    def _set_routes(self):
+        if self._routes_set or not self.scenarios:
+            return
+        paths = self._routes
+        if paths is None:
+            paths = [{k: e.trajectory.data[:, 1:3] for k, e in enumerate(sc.entities)} for sc in self.scenarios]
+        scen = [i for i, d in enumerate(paths) for _ in d]
+        slot = [int(k) for d in paths for k in d]
+        self.engine.set_routes(scen, slot, [q for d in paths for q in d.values()])
+        self._routes_set = True
+
+    def _route_observation(self, observers: bool, n_ahead: int, spacing: float):
+        """(feat [n, 11 + 2 * n_ahead], info [n, 2]) of State.route_observation."""
+        def compute():
+            self._set_routes()
+            return self.engine.route_observation(n_ahead, spacing, observers=observers)
+
+        return self._cached(("route", observers, n_ahead, spacing), compute, observers=observers)
 
     def _raster(self, width, height, nw, nh):
         return self._cached(("raster", width, height, nw, nh), lambda: self.engine.raster_entities(width, height, nw, nh))

@@ -73,6 +73,36 @@ class LaneObservation(SingleEntityObservation):
 
 
 @dataclass
+class RouteObservation:
+    """The route and recorded-track observation of one entity (State.route_observation, sg_route_observation; no counterpart in
+    the reference): `present` -- it is in State.poses; `features` [11 + 2 * n_ahead] -- where its own recording has it at the
+    current time in its frame (2), the distance to that point, cos and sin of the recorded heading relative to its own, then
+    the lateral offset from its route (left positive), cos and sin of its heading relative to the route, the arclength along
+    the route, what is left of it, the distance to it, and the n_ahead route points ahead in its frame; `segment` -- the
+    route segment it is nearest to (-1: no route; the route features are zero then); `recording` -- where the current time
+    lies in its recording: 0 within, -1 before the first knot, 1 after the last.  `log_divergence`, `progress` and
+    `remaining` name features 2, 8 and 9.  Not present: zeros, -1, -1."""
+
+    entity: Any
+    present: bool
+    features: np.ndarray
+    segment: int
+    recording: int
+
+    @property
+    def log_divergence(self) -> float:
+        return float(self.features[2])
+
+    @property
+    def progress(self) -> float:
+        return float(self.features[8])
+
+    @property
+    def remaining(self) -> float:
+        return float(self.features[9])
+
+
+@dataclass
 class RangeScanObservation(SingleEntityObservation):
     """The range scan (no counterpart in the reference): per beam of the sensor's fan `ranges`, the distance from the entity's
     pose point to the first other entity's bounding box (the sensor's max_range without a hit, 0 from inside a box),

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .entity import Entity
-from .observation import EntityStatus
+from .observation import EntityStatus, RouteObservation
 from .road_network import LAYER_CROSSING, LAYER_IMPENETRABLE, LAYER_INTERSECTION, LAYER_LANE, LAYER_PAVEMENT, LAYER_ROAD
 from .scenario import Scenario
 
@@ -261,6 +261,17 @@ class State:
         rn = self._scenario.road_network
         lanes = rn.lanes if rn is not None else []
         return [lanes[j] for j in idx[row] if j >= 0], feat[row].copy()
+
+    def route_observation(self, n_ahead: int = 4, spacing: float = 2.0, entity: Optional[Entity] = None):
+        """The route and recorded-track observation of `entity` (any entity of the scenario, default the ego) at the current
+        state, computed on the device (sg_route_observation / sg_route_observation_observers): a RouteObservation -- how far
+        the entity is from where its own recording has it, and where it is along its route with n_ahead points of the route
+        ahead.  The routes are those of ScenarioGym.set_routes; by default every entity's own recorded trajectory."""
+        observers, row = self._sensor_row(entity)
+        feat, info = self._gym._route_observation(observers, int(n_ahead), float(spacing))
+        entity = self._scenario.ego if entity is None else entity
+        present = bool(self._s()["present"][self._i, self._scenario.entities.index(entity)])
+        return RouteObservation(entity, present, feat[row].copy(), int(info[row, 0]), int(info[row, 1]))
 
     def get_road_info_at_entity(self, e: Entity):
         """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's

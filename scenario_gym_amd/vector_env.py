@@ -37,7 +37,8 @@ class VectorScenarioEnv:
                  height: float = 30.0, width: float = 30.0, n: int = 128, max_steer: float = 0.9, max_accel: float = 5.0,
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
                  drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True,
-                 traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None):
+                 traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None,
+                 driver_progress: Optional[float] = None):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
         VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
         driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
@@ -46,7 +47,12 @@ class VectorScenarioEnv:
         (trajectory.data[:, 1:3] as given), each with the same VehicleController; needs `drivers`, and no entity may be in both.
         traffic_params: None, keyword arguments of idm_params for every traffic entity (a dict), or one parameter row per traffic
         entity ([n_traffic, DP_NPARAM], environment by environment); v0 defaults to the largest knot-to-knot speed of the
-        entity's recording, floored at 1 m/s."""
+        entity's recording, floored at 1 m/s.
+        driver_progress: None, or the weight w of a progress term in the per-driver reward (needs `drivers` and driver_status):
+        every driver gets a route -- its own recorded trajectory unless set_routes gave another -- and every step reports in
+        `info` driver_route (the rows of sg_route_observation_observers) and driver_progress (the arclength gained along the
+        route since the previous tick; 0 for a driver without a route, not in the scene at either tick, or when reset() or an
+        auto-reset of its environment came in between), and adds w * driver_progress to driver_reward."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -55,6 +61,9 @@ class VectorScenarioEnv:
         self.height, self.width, self.n = float(height), float(width), int(n)
         self.auto_reset, self.torch_obs = auto_reset, torch_obs
         self.driver_status = bool(driver_status)
+        self.driver_progress = None if driver_progress is None else float(driver_progress)
+        if self.driver_progress is not None and (drivers is None or not self.driver_status):
+            raise ValueError("driver_progress: needs a driver list (drivers=...) with driver_status")
 
         if drivers is not None and len(drivers) != len(self.scenarios):
             raise ValueError("drivers: one list of entity indices per environment")
@@ -103,6 +112,10 @@ class VectorScenarioEnv:
             self.set_observers(drivers)  # (the default: every driver of the caller's observes)
             if self.n_traffic:
                 self._set_traffic_policy(traffic_params)
+        self._routes_set = False     # the routes go down when a route observation is first asked for
+        self._route_s0 = None        # driver_progress: (arclength, on a route) of every driver at the previous tick
+        if self.driver_progress is not None:
+            self.set_routes()
 
     def _set_traffic_policy(self, traffic_params):
         """The policy rows and paths of the traffic entities: each along its own recorded trajectory."""
@@ -147,6 +160,7 @@ class VectorScenarioEnv:
         """Env.reset for every environment (openaigym.py:128-169): observations [R, n_layers, n, n]."""
         self.engine.reset()
         self.done[:] = False
+        self._route_s0 = None
         return self._observe()
 
     def step(self, actions):
@@ -180,7 +194,9 @@ class VectorScenarioEnv:
         drivers; with driver_status, info also holds driver_flags [n_drivers], driver_info [n_drivers, 4], driver_feat
         [n_drivers, 3] (sg_entity_status_observers on the stepped state, before an auto-reset), driver_reward [n_drivers] (-1 for
         a driver that is off the road or in a collision, else 0.01) and driver_done [n_drivers] (that, or its environment
-        done); obs [n_observers, n_layers, n, n] of the observer list (observe_entities)."""
+        done); with driver_progress=w also driver_route [n_drivers, 11] (sg_route_observation_observers on the stepped state) and
+        driver_progress [n_drivers], and driver_reward has w * driver_progress added; obs [n_observers, n_layers, n, n] of the
+        observer list (observe_entities)."""
         if not hasattr(actions, "data_ptr"):
             actions = np.asarray(actions, np.float64).reshape(self.n_drivers, 2)
         if self.n_traffic:
@@ -205,21 +221,35 @@ class VectorScenarioEnv:
             info.update(driver_flags=d_flags, driver_info=d_info, driver_feat=d_feat,
                         driver_reward=np.where(d_bad, -1.0, 0.01),  # RLAgent.reward asked per driver, without its is_done gate
                         driver_done=d_bad | done[self._drv_env])
+            if self.driver_progress is not None:
+                if self._route_s0 is None:  # (the first tick of the run: the arclengths of the reset state were not asked for)
+                    self._route_s0 = (np.zeros(self.n_drivers), np.zeros(self.n_drivers, bool))
+                feat, r_info = self._driver_call(lambda: self.engine.route_observation(0, 0.0, observers=True))
+                on = r_info[:, 0] >= 0  # (on a route, which says in the scene too)
+                progress = np.where(on & self._route_s0[1], feat[:, 8] - self._route_s0[0], 0.0)
+                info.update(driver_route=feat, driver_progress=progress)
+                info["driver_reward"] = info["driver_reward"] + self.driver_progress * progress
+                self._route_s0 = (feat[:, 8].copy(), on)
         self.done = done
         if self.auto_reset and done.any():
             self.engine.reset_scenarios(done)  # (the reset restarts the drivers' controller speeds with the rest of the state)
             self.done = np.zeros(self.n_envs, bool)
+            if self._route_s0 is not None:  # a new episode: its first tick has no previous arclength
+                self._route_s0[1][done[self._drv_env]] = False
         return self._observe(), reward, done, info
 
     def _driver_status(self):
-        """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays: read
-        through the observer list when that is the driver list (the default); otherwise the drivers are the engine's observers
-        for this one call and the caller's list is put back."""
+        """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays."""
+        return self._driver_call(self.engine.entity_status_observers)
+
+    def _driver_call(self, call):
+        """call() with the drivers as the engine's observers: through the observer list when that is the driver list (the
+        default); otherwise the drivers are the engine's observers for this one call and the caller's list is put back."""
         same = np.array_equal(self._obs_env, self._drv_env) and np.array_equal(self._obs_slot, self._drv_slot)
         if not same:
             self.engine.set_observers(self._drv_env, self._drv_slot)
         try:
-            return self.engine.entity_status_observers()
+            return call()
         finally:
             if not same:
                 self.engine.set_observers(self._obs_env, self._obs_slot)
@@ -317,6 +347,45 @@ class VectorScenarioEnv:
         torch_obs: torch tensors in HBM; else numpy arrays."""
         self._set_lanes()
         out = self.engine.lane_observation_observers(k, n_ahead, spacing, radius, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
+
+    def set_routes(self, paths=None):
+        """The routes of route_observation / observe_entities_routes and of the progress reward (sg_set_routes): paths[i] =
+        {entity index: polyline [n_pts, 2]} for environment i.  None: every observer and every driver (the traffic too) gets its
+        own recorded trajectory.data[:, 1:3], as the traffic policy takes it.  Replaces the previous routes."""
+        if paths is None:
+            envs = [self._obs_env, self._trf_env] + ([self._drv_env] if self._drv_env is not None else [])
+            slots = [self._obs_slot, self._trf_slot] + ([self._drv_slot] if self._drv_env is not None else [])
+            pairs = sorted({(int(i), int(k)) for i, k in zip(np.concatenate(envs), np.concatenate(slots))})
+            paths = [{} for _ in range(self.n_envs)]
+            for i, k in pairs:
+                paths[i][k] = np.asarray(self.scenarios[i].entities[k].trajectory.data, np.float64)[:, 1:3]
+        elif len(paths) != self.n_envs:
+            raise ValueError("set_routes: one dict of entity index -> path per environment")
+        env = [i for i, d in enumerate(paths) for _ in d]
+        slot = [int(k) for d in paths for k in d]
+        self.engine.set_routes(env, slot, [q for d in paths for q in d.values()])
+        self._routes_set = True
+        if self._route_s0 is not None:  # (arclengths along other routes)
+            self._route_s0[1][:] = False
+
+    def route_observation(self, n_ahead: int = 4, spacing: float = 2.0):
+        """The route and recorded-track observation of the ego of every environment at the current state
+        (sg_route_observation): (feat [R, 11 + 2 * n_ahead], info [R, 2]: RolloutEngine.route_observation).  The routes are those
+        of set_routes (before any: its default); an ego without one has its route part zero.  torch_obs: torch tensors in HBM;
+        else numpy arrays."""
+        if not self._routes_set:
+            self.set_routes()
+        return self.engine.route_observation(n_ahead, spacing, device=self.torch_obs)
+
+    def observe_entities_routes(self, n_ahead: int = 4, spacing: float = 2.0):
+        """The route and recorded-track observation of every observer of set_observers at the current state
+        (sg_route_observation_observers): (feat [n, 11 + 2 * n_ahead], info [n, 2], env_of_observer [n], slot [n]).  Before any
+        set_routes every observer and driver gets its own recording as its route.  torch_obs: torch tensors in HBM; else numpy
+        arrays."""
+        if not self._routes_set:
+            self.set_routes()
+        out = self.engine.route_observation(n_ahead, spacing, observers=True, device=self.torch_obs)
         return tuple(out) + self._observer_index(out[0])
 
     def close(self):
