@@ -313,6 +313,13 @@ int sg_reset(sg_handle *h);
  * starts a new episode (`Env.reset` of integrations/openaigym.py:128-169) while the others keep their state. */
 int sg_reset_scenarios(sg_handle *h, const uint8_t *mask);
 
+/* sg_reset_scenarios with a DEVICE mask d_mask [n_scenarios], for a caller whose done flags never leave the device: the same
+ * launches -- every kernel family, scenarios of more than 512 entities and sg_set_rss on included -- queued on sg_stream(h) and
+ * NOT waited for; the mask is read in stream order and must stay as it is until the reset has run.  (sg_reset_scenarios is: copy
+ * the mask to the device, this, wait.)  Both start the episode accounting of sg_tick_drivers anew for the masked scenarios and
+ * their drivers, and for nobody else.  SG_ERR_INVALID: d_mask NULL.  SG_ERR_STATE before sg_upload. */
+int sg_reset_scenarios_device(sg_handle *h, const uint8_t *d_mask);
+
 /* TERMINAL_CONDITIONS (state/state.py:397-408) evaluated on the current state of every scenario, all four of them
  * whatever the handle's terminal_mask: flags[r] = SG_TERM_* bits (EGO_OFF_ROAD against the networks of
  * sg_set_road_networks; none set = empty surfaces = off the road).  This is what the reward of the reference's RL agent
@@ -447,6 +454,79 @@ int sg_driver_policy_actions(sg_handle *h, double *actions, int32_t *info, doubl
  * run n_steps times, bit for bit on everything a caller can read.  One short launch more per step than sg_step_drivers.
  * SG_ERR_STATE before sg_upload, without a driver list or without a policy; SG_ERR_INVALID: n_steps < 1. */
 int sg_step_drivers_policy(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device);
+
+/* One tick of a multi-agent environment, entirely in stream order: the step of the drivers, the terminal conditions, the status
+ * (and, for a progress reward, the route observation) of every driver, reward, done, progress and episode statistics per scenario
+ * and per driver, and the auto-reset of the scenarios that finished.  What a vector environment otherwise does in five to eight
+ * synchronous calls with host arithmetic in between (scenario_gym_amd/vector_env.py, _step_drivers).  Nothing returns to the host.
+ *
+ * The rules -- with the defaults r_step = 0.01, r_bad = -1, bad_env_flags = SG_TERM_EGO_OFF_ROAD | SG_TERM_EGO_COLLISION,
+ * bad_driver_flags = SG_ST_OFF_ROAD | SG_ST_COLLISION the reward of the reference's RLAgent (integrations/openaigym.py:300-310)
+ * asked per scenario and per driver: */
+typedef struct sg_episode_rules {
+    uint32_t terminal_mask;    /* SG_TERM_* bits that end a scenario's episode */
+    uint32_t bad_env_flags;    /* SG_TERM_* bits that make the reward of a finished scenario r_bad */
+    uint32_t bad_driver_flags; /* SG_ST_* bits that make a driver's base reward r_bad and end its episode */
+    int32_t auto_reset;        /* != 0: the scenarios that finished are reset behind the tick (reset_mask = env_done) */
+    double r_step, r_bad;      /* finite */
+    double w_progress;         /* finite; the weight of the arclength a driver gained along its route of sg_set_routes; 0: no route
+                                  observation is launched */
+} sg_episode_rules;
+
+/* What a tick leaves behind: const DEVICE pointers into buffers the handle owns, written in stream order by the tick that returned
+ * them (sg_synchronize, or work queued on sg_stream(h), sees them complete) and valid until the next sg_tick_drivers,
+ * sg_set_drivers or sg_upload.  n_drv = the drivers of sg_set_drivers, rows in list order, policy-run drivers included.  The
+ * status and route rows are those of the stepped state, BEFORE the auto-reset replaced it. */
+typedef struct sg_episode_view {
+    const uint32_t *term_flags;     /* [n_scenarios] sg_terminal_flags of the stepped state */
+    const uint8_t *env_done;        /* [n_scenarios] */
+    const double *env_reward;       /* [n_scenarios] */
+    const uint8_t *reset_mask;      /* [n_scenarios] the scenarios the tick reset */
+    const int32_t *ep_length;       /* [n_scenarios] ticks of the scenario's episode, this one included */
+    const uint32_t *drv_flags;      /* [n_drv] sg_entity_status of every driver: flags, */
+    const int32_t *drv_info;        /* [n_drv][SG_ST_NINFO] info */
+    const double *drv_feat;         /* [n_drv][SG_ST_NFEAT] and feat */
+    const double *drv_route;        /* [n_drv][SG_RT_NFEAT] sg_route_observation with n_ahead = 0; NULL when w_progress == 0 */
+    const int32_t *drv_route_info;  /* [n_drv][SG_RT_NINFO]; NULL when w_progress == 0 */
+    const double *drv_progress;     /* [n_drv] */
+    const double *drv_reward;       /* [n_drv] */
+    const double *ep_return;        /* [n_drv] the sum of the driver's rewards over its scenario's episode, this tick included */
+    const uint8_t *drv_done;        /* [n_drv] */
+} sg_episode_view;
+
+/* actions: [n_drv][2] (acceleration, steering) in list order, HOST (actions_device == 0), DEVICE, or NULL for (0, 0); the rows of
+ * policy drivers are replaced by the policy's.  Queued on sg_stream(h), in this order:
+ *   1. with a policy set (sg_set_driver_policy): driver_policy_kernel into the merged action buffer of the handle
+ *   2. drive_kernel: the drivers' controller step
+ *   3. one forced step of the batch -- 1 to 3 are sg_step_drivers / sg_step_drivers_policy with n_steps = 1 without their wait
+ *   4. terminal_flags
+ *   5. entity_status on the DRIVER list (the observer list of sg_set_observers is neither read nor touched)
+ *   6. with w_progress != 0: route_observation on the driver list, n_ahead = 0
+ *   7. episode_kernel (csrc/sgym_episode.hpp), one lane per index i < max(n_scenarios, n_drv), plain unfused fp64:
+ *      scenario r, f = term_flags[r]:
+ *        env_done[r] = (f & terminal_mask) != 0;  env_reward[r] = env_done[r] && (f & bad_env_flags) ? r_bad : r_step
+ *        reset_mask[r] = auto_reset && env_done[r]
+ *        ep_length[r] = ++length[r] (the handle's counter), which is then zeroed when reset_mask[r]
+ *      driver d of scenario r:
+ *        bad = (drv_flags[d] & bad_driver_flags) != 0;  base = bad ? r_bad : r_step
+ *        w_progress == 0: drv_progress[d] = +0.0, drv_reward[d] = base, and the route memory below is left alone
+ *        otherwise: on = drv_route_info[d][0] >= 0, s0 = drv_route[d][8];
+ *          drv_progress[d] = on && prev_ok[d] ? s0 - prev_s[d] : +0.0;  drv_reward[d] = base + w_progress * drv_progress[d] (the
+ *          product rounded, then the sum);  prev_s[d] = s0;  prev_ok[d] = on && !reset_mask[r]
+ *        drv_done[d] = bad || env_done[r]
+ *        ep_return[d] = (return[d] += drv_reward[d]) (the handle's accumulator), which is then zeroed when reset_mask[r]
+ *   8. with auto_reset: sg_reset_scenarios_device on reset_mask
+ * prev_s, prev_ok, return and length live on the handle.  sg_reset, sg_upload, sg_set_drivers and sg_set_routes zero them for
+ * everybody, sg_reset_scenarios[_device] for the masked scenarios and their drivers; sg_step* leave them alone.  So the first tick
+ * of an episode has progress 0.
+ * The call never waits for the stream, except that HOST actions are copied before it returns (the caller's array is free then);
+ * the first call after the driver list changed allocates.  It is a sequence of plain stream-ordered launches, not a captured
+ * graph: it may be queued any number of times without a wait in between, and must not be called while sg_stream(h) is
+ * capturing.  A persistent rollout launch that gave up is reported as the DEVICE-output observation calls report it (what is
+ * known so far).  Every byte of every array of the view is written by every tick.
+ * SG_ERR_STATE before sg_upload or without a driver list; SG_ERR_INVALID: rules or out NULL, r_step, r_bad or w_progress NaN or
+ * infinite.  A refused call queues nothing and leaves state, accounting and *out as they were. */
+int sg_tick_drivers(sg_handle *h, const double *actions, int32_t actions_device, const sg_episode_rules *rules, sg_episode_view *out);
 
 /* ScenarioGym.rollout(): reset, then step each scenario while it is not done, at most max_steps
  * (scenario_gym.py:256-267).  The time loop runs inside the kernels: one launch for short runs; long runs of batches with
@@ -738,7 +818,8 @@ int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t *info, dou
  * segment), b -- per route total = cum + len of its last segment (0 without segments), and a map from the entity to its route:
  * observers are looked up by entity, not by their position in a list.  A route of fewer than two points has no segments.
  * n == 0 clears the routes (the arrays may be NULL then).  sg_upload forgets them; sg_reset, sg_reset_scenarios, sg_step*,
- * sg_set_observers, sg_set_drivers and sg_set_driver_policy keep them (the policy's own paths are separate).
+ * sg_set_observers, sg_set_drivers and sg_set_driver_policy keep them (the policy's own paths are separate).  A call that is not
+ * refused starts the episode accounting of sg_tick_drivers anew (its arclengths were along other routes).
  * SG_ERR_STATE before sg_upload.  SG_ERR_INVALID: n < 0, a NULL array that is needed, a scenario or slot out of range, a
  * (scenario, slot) pair listed twice, pt_off not starting at 0 or not monotone, 2^31 or more segments, a coordinate that is not
  * finite, a route whose total is not finite.  A refused call leaves the previous routes in place. */

@@ -49,6 +49,7 @@ SYMBOLS = (
     "sg_entity_status", "sg_entity_status_observers",
     "sg_set_driver_policy", "sg_driver_policy_actions", "sg_step_drivers_policy",
     "sg_set_routes", "sg_route_observation", "sg_route_observation_observers",
+    "sg_reset_scenarios_device", "sg_tick_drivers",
 )
 
 
@@ -76,6 +77,23 @@ class SgLanes(C.Structure):  # include/sgym.h sg_lanes
 
 class SgDriverPolicy(C.Structure):  # include/sgym.h sg_driver_policy
     _fields_ = [("m", C.c_int64)] + [(n, C.c_void_p) for n in ("driver", "params", "pt_off", "pts")]
+
+
+class SgEpisodeRules(C.Structure):  # include/sgym.h sg_episode_rules
+    _fields_ = [("terminal_mask", C.c_uint32), ("bad_env_flags", C.c_uint32), ("bad_driver_flags", C.c_uint32), ("auto_reset", C.c_int32),
+                ("r_step", C.c_double), ("r_bad", C.c_double), ("w_progress", C.c_double)]
+
+
+# the arrays of sg_episode_view in its order: (name, numpy typestr, columns; 0: one value per row), the first five per scenario
+EPISODE_VIEW = (("term_flags", "<i4", 0), ("env_done", "|u1", 0), ("env_reward", "<f8", 0), ("reset_mask", "|u1", 0), ("ep_length", "<i4", 0),
+                ("drv_flags", "<i4", 0), ("drv_info", "<i4", ST_NINFO), ("drv_feat", "<f8", ST_NFEAT), ("drv_route", "<f8", RT_NFEAT),
+                ("drv_route_info", "<i4", RT_NINFO), ("drv_progress", "<f8", 0), ("drv_reward", "<f8", 0), ("ep_return", "<f8", 0),
+                ("drv_done", "|u1", 0))
+EPISODE_VIEW_PER_SCENARIO = 5
+
+
+class SgEpisodeView(C.Structure):  # include/sgym.h sg_episode_view
+    _fields_ = [(name, C.c_void_p) for name, _, _ in EPISODE_VIEW]
 
 
 class SgSocialForce(C.Structure):
@@ -238,6 +256,8 @@ def load():
     lib.sg_set_routes.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sg_route_observation.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_route_observation_observers.argtypes = lib.sg_route_observation.argtypes
+    lib.sg_reset_scenarios_device.argtypes = [H, C.c_void_p]
+    lib.sg_tick_drivers.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(SgEpisodeRules), C.POINTER(SgEpisodeView)]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

@@ -6,10 +6,6 @@
 
 using namespace sgh;
 
-// the driver list on the device: the scenarios in the first half of the buffer, the slots in the second
-static int32_t *driver_scenarios(const sg_handle *h) { return h->drivers.as<int32_t>(); }
-static int32_t *driver_slots(const sg_handle *h) { return h->drivers.as<int32_t>() + h->drivers.cap / (2 * sizeof(int32_t)); }
-
 extern "C" int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot)
 {
     if (!h) return SG_ERR_INVALID;
@@ -27,6 +23,7 @@ extern "C" int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, 
             return fail(h, SG_ERR_INVALID, "sg_set_drivers: slot %d of scenario %d is listed twice", slot[k], scenario[k]);
         listed[i] = 1;
     }
+    forget_episodes(h); // (the accounting of sg_tick_drivers is per position in the list)
     if (n == 0) {
         h->n_drv = 0;
         forget_driver_policy(h);
@@ -200,4 +197,42 @@ extern "C" int sg_step_drivers_policy(sg_handle *h, int32_t n_steps, const doubl
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return check_queue(h);
+}
+
+// ---- one queued step: the body of sg_step_drivers / sg_step_drivers_policy for n_steps = 1 (sg_tick_drivers, h_episode.hip) ---------
+int sgh::drivers_step_queued(sg_handle *h, const char *who, const double *actions, int32_t actions_device)
+{
+    const size_t per_step = (size_t)h->n_drv * 2, bytes = per_step * sizeof(double);
+    const auto host_copy = [&](void *dst) { // (the caller's array is free when the call returns)
+        HIP_TRY(h, hipMemcpyAsync(dst, actions, bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return (int)SG_OK;
+    };
+    const double *d_act = nullptr; // (null: every driver gets (0, 0))
+    if (h->n_pol > 0) {
+        // the merged actions live in a buffer of the handle: the caller's rows are copied in, the policy's rows written over them
+        if (const int rc = h->pol_actions.ensure(h, bytes)) return rc;
+        double *merged = h->pol_actions.as<double>();
+        if (actions && !actions_device) { if (const int rc = host_copy(merged)) return rc; }
+        else if (actions) HIP_TRY(h, hipMemcpyAsync(merged, actions, bytes, hipMemcpyDeviceToDevice, h->stream));
+        else HIP_TRY(h, hipMemsetAsync(merged, 0, bytes, h->stream));
+        d_act = merged;
+    } else if (actions && actions_device) {
+        d_act = actions;
+    } else if (actions) {
+        if (const int rc = h->drv_actions.ensure(h, bytes)) return rc;
+        if (const int rc = host_copy(h->drv_actions.ptr)) return rc;
+        d_act = h->drv_actions.as<double>();
+    }
+    // the SG_KIND_AGENT_VEHICLE slots of the batch get (0, 0), as under sg_step(h, 1, NULL, 0)
+    if (const int rc = ensure_actions(h, (size_t)h->R * 2)) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->actions.ptr, 0, (size_t)h->R * 2 * sizeof(double), h->stream));
+    if (h->n_pol > 0) {
+        sgl::driver_policy(h->stream, h->p, h->pol, driver_scenarios(h), driver_slots(h), h->n_pol, h->pol.driver, h->pol_actions.as<double>(), nullptr,
+                           nullptr);
+        if (hipGetLastError() != hipSuccess) return fail(h, SG_ERR_HIP, "%s: launching driver_policy_kernel failed", who);
+    }
+    sgl::drive(h->stream, h->p, h->cfg.timestep, driver_scenarios(h), driver_slots(h), h->n_drv, d_act, h->d_ext);
+    if (hipGetLastError() != hipSuccess) return fail(h, SG_ERR_HIP, "%s: launching drive_kernel failed", who);
+    return step_forced(h, 1, h->actions.as<double>());
 }

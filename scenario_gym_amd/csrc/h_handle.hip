@@ -160,6 +160,7 @@ extern "C" int sg_destroy(sg_handle *h)
     h->policy.release();
     h->pol_actions.release();
     h->pol_out.release();
+    h->episode.release();
     if (h->d_reset_mask) (void)hipFree(h->d_reset_mask);
     h->term_flags.release();
     if (h->d_rss_state) (void)hipFree(h->d_rss_state);

@@ -421,6 +421,7 @@ extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, c
     if (n < 0 || (n > 0 && (!scenario || !slot || !pt_off))) return fail(h, SG_ERR_INVALID, "%s: n < 0 or null array", who);
     if (n == 0) {
         forget_routes(h);
+        forget_episodes(h);
         return SG_OK;
     }
     if (n > (int64_t)h->R * h->E) return fail(h, SG_ERR_INVALID, "%s: more routes than entity slots: a pair is listed twice", who);
@@ -455,6 +456,7 @@ extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, c
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued sg_route_observation may still read the previous routes)
     forget_routes(h); // (from here on the old routes are gone: a failure of the runtime leaves the handle without any)
+    forget_episodes(h); // (the arclengths sg_tick_drivers remembers were along the old routes)
     const size_t b_dbl = total.size() * sizeof(double), b_seg = segs.size() * sizeof(sg::LaneSeg), b_int = ints.size() * sizeof(int32_t);
     if (const int rc = h->routes.ensure(h, b_dbl + b_seg + b_int)) return rc;
     unsigned char *base = h->routes.as<unsigned char>();

@@ -616,6 +616,7 @@ extern "C" int sg_reset(sg_handle *h)
     if (!rc) rc = launch_rollout(h, 0, 1, 0, nullptr, fused);
     if (!rc && h->rss_enabled && !fused) rc = sg_rss_update(h, 1);
     if (rc) return rc;
+    forget_episodes(h); // (a new episode for everybody: the accounting of sg_tick_drivers starts anew)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SG_OK;
 }
@@ -627,13 +628,28 @@ extern "C" int sg_reset_scenarios(sg_handle *h, const uint8_t *mask)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->d_reset_mask) HIP_TRY(h, hipMalloc((void **)&h->d_reset_mask, (size_t)h->R));
     HIP_TRY(h, hipMemcpyAsync(h->d_reset_mask, mask, (size_t)h->R, hipMemcpyHostToDevice, h->stream));
-    h->p.reset_mask = h->d_reset_mask;
+    if (const int rc = reset_scenarios_queued(h, h->d_reset_mask, true)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SG_OK;
+}
+
+// (the reset launch reads its mask from device memory, Params::reset_mask, whoever filled it)
+int sgh::reset_scenarios_queued(sg_handle *h, const uint8_t *d_mask, bool clear_episodes)
+{
+    h->p.reset_mask = d_mask;
     bool fused = false; // (the flagged scenarios' RSS histories start anew as well)
     int rc = rss_fused_call(h, true, &fused);
     if (!rc) rc = launch_rollout(h, 0, 2, 0, nullptr, fused);
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SG_OK;
+    if (!rc && clear_episodes) rc = episode_clear_masked(h, d_mask);
+    return rc;
+}
+
+extern "C" int sg_reset_scenarios_device(sg_handle *h, const uint8_t *d_mask)
+{
+    if (!h || !d_mask) return h ? fail(h, SG_ERR_INVALID, "sg_reset_scenarios_device: null mask") : SG_ERR_INVALID;
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_reset_scenarios_device: no scenarios uploaded");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return reset_scenarios_queued(h, d_mask, true);
 }
 
 extern "C" int sg_set_external_poses(sg_handle *h, const double *poses)

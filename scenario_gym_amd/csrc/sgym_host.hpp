@@ -1,7 +1,7 @@
 // sgym_host.hpp -- what the host units of libsgym_hip.so share (private: the public side is include/sgym.h).
 // The handle, the error and allocation helpers, and the declarations of the few internal functions that cross unit
 // boundaries (namespace sgh).  The units: sgym_hip.hip (the dispatcher and the stepping entry points), h_handle.hip, h_upload.hip,
-// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_drive.hip, h_read.hip, h_group.hip.  None of them holds a
+// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_drive.hip, h_episode.hip, h_read.hip, h_group.hip.  None of them holds a
 // kernel: they launch through sgym_launch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -215,6 +215,16 @@ struct sg_handle {
                                                        // ([n_steps][n_drv][2] doubles; a caller's device buffer is never written)
     sgh::GrowBuf pol_out{sgh::GrowBuf::DEVICE_POISONED}; // device scratch of sg_driver_policy_actions with host outputs
 
+    // ---- h_episode.hip: the multi-agent tick (sg_tick_drivers) ----
+    sgh::GrowBuf episode{sgh::GrowBuf::DEVICE};        // the accounting (prev_s, return, length, prev_ok: one behind the other at the front, so
+                                                       // that one memset starts it anew) and every array of sg_episode_view
+    size_t ep_state_bytes = 0;                         // ... the bytes of that front part
+    int64_t ep_n = -1;                                 // the number of drivers the buffer is laid out for (-1: not laid out)
+    bool ep_live = false;                              // the accounting holds episodes in progress; false (sg_reset, sg_upload, sg_set_drivers,
+                                                       // sg_set_routes): the next tick zeroes it first
+    sg::EpisodeArgs ep{};                              // the kernel's pointers into the buffer
+    sg_episode_view ep_view{};                         // ... and the caller's
+
     // ---- h_read.hip ----
     // page-locked staging of sg_read_metrics (the per-scenario state and the event table travel every time metrics are read:
     // 0.5 + up to 6 MB for 4096 scenarios; pageable copies ran at a third of the PCIe rate)
@@ -374,6 +384,13 @@ inline void forget_driver_policy(sg_handle *h)
 // the routes of sg_set_routes belong to entities of a batch (sg_upload); the buffer stays for the next ones
 inline void forget_routes(sg_handle *h) { h->route = sg::RouteIndex{}; }
 
+// the driver list on the device: the scenarios in the first half of the buffer, the slots in the second
+inline int32_t *driver_scenarios(const sg_handle *h) { return h->drivers.as<int32_t>(); }
+inline int32_t *driver_slots(const sg_handle *h) { return h->drivers.as<int32_t>() + h->drivers.cap / (2 * sizeof(int32_t)); }
+
+// the episode accounting of sg_tick_drivers starts anew with the next tick (sg_reset, sg_upload, sg_set_drivers, sg_set_routes)
+inline void forget_episodes(sg_handle *h) { h->ep_live = false; }
+
 // The device rows of one polyline pts[i0 .. i1) ([..][2] doubles), appended to segs: one row per segment a -> b in point order -- a,
 // e = b - a, L2 = ex*ex + ey*ey, len = sqrt(L2), cum = the sequential sum of the preceding len, b -- tagged (lane, first).  Returns
 // the polyline's total, cum + len of its last segment (0 without segments).  What sg_set_lanes, sg_set_driver_policy and
@@ -450,6 +467,17 @@ int step_forced(sg_handle *h, int n_steps, const double *d_actions);
 void note_wide(sg_handle *h);
 void note_queue(sg_handle *h, bool rss);
 void note_slice(sg_handle *h, bool tab);
+// ---- h_upload.hip ----
+// State.reset of the scenarios with d_mask[r] != 0 (DEVICE [R]), enqueued, not waited for: what sg_reset_scenarios does between its
+// copy and its wait.  clear_episodes: their episode accounting starts anew too (sg_tick_drivers' own reset has done that already)
+int reset_scenarios_queued(sg_handle *h, const uint8_t *d_mask, bool clear_episodes);
+// ---- h_drive.hip ----
+// one step of the batch with the drivers' controllers ahead of it, the policy ahead of them when one is set: sg_step_drivers /
+// sg_step_drivers_policy for n_steps = 1 (actions [n_drv][2] HOST, DEVICE or null) without their wait -- HOST actions are on the
+// device when it returns, and that alone is waited for
+int drivers_step_queued(sg_handle *h, const char *who, const double *actions, int32_t actions_device);
+// ---- h_episode.hip ----
+int episode_clear_masked(sg_handle *h, const uint8_t *d_mask); // (enqueued; nothing when no episode is in progress)
 // ---- h_queue.hip ----
 int check_queue(sg_handle *h);
 void forget_queue_failure(sg_handle *h);

@@ -11,6 +11,7 @@
 #include "sgym_wide.hpp"
 #include "sgym_queue.hpp"
 #include "sgym_policy.hpp"
+#include "sgym_episode.hpp"
 
 namespace sgl {
 
@@ -90,6 +91,11 @@ void drive(hipStream_t s, const sg::Params &p, double timestep, const int32_t *s
 // [m][SG_DP_NFEAT] (or nullptr).  One wavefront per policy driver, any scenario width.  All pointers DEVICE.
 void driver_policy(hipStream_t s, const sg::Params &p, const sg::PolicyIndex &P, const int32_t *scen, const int32_t *slot, int64_t m,
                    const int32_t *row_of, double *actions, int32_t *info, double *feat);
+// episode_kernel (sgym_episode.hpp): reward, done, progress, episode statistics and the reset mask of one sg_tick_drivers, one lane per
+// index i < max(a.R, a.n_drv); episode_clear_kernel: the accounting of the scenarios with mask[r] != 0 and of their drivers zeroed.
+// All pointers DEVICE.
+void episode(hipStream_t s, const sg::EpisodeArgs &a);
+void episode_clear(hipStream_t s, const uint8_t *mask, const sg::EpisodeArgs &a);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

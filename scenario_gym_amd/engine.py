@@ -1,5 +1,6 @@
 """RolloutEngine: thin object wrapper over one sg_handle (one GPU, R scenarios x E entity slots)."""
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -401,6 +402,85 @@ class RolloutEngine:
         assert m.shape == (self.R,)
         self._check(self.lib.sg_reset_scenarios(self.h, m.ctypes.data), "sg_reset_scenarios")
 
+    def reset_scenarios_device(self, mask):
+        """reset_scenarios with the mask on the device (sg_reset_scenarios_device): a torch uint8 (or bool) tensor [R] on this
+        GPU.  Queued on the engine's stream behind the work of torch's current stream, not waited for; the tensor must stay as
+        it is until the reset has run (work queued on torch's current stream after this call is ordered behind it)."""
+        import torch
+
+        assert mask.is_cuda and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and mask.numel() == self.R
+        with self.ordered_with_torch():
+            self._check(self.lib.sg_reset_scenarios_device(self.h, mask.data_ptr()), "sg_reset_scenarios_device")
+
+    def _stream(self):
+        """The engine's stream (sg_stream) as a torch stream: what orders it against torch's streams without a host wait."""
+        import torch
+
+        if self.__dict__.get("_ext_stream") is None:
+            self._ext_stream = torch.cuda.ExternalStream(self.lib.sg_stream(self.h), device=f"cuda:{self.cfg.device}")
+        return self._ext_stream
+
+    @contextmanager
+    def ordered_with_torch(self, enabled=True):
+        """What is queued on the engine's stream inside the block runs behind the work torch's current stream holds at its start,
+        and what torch's current stream gets after the block runs behind that: two events, no host wait.  Around several queued
+        calls (tick_drivers, raster_map_observers_queued with ordered=False) it orders them as one."""
+        if not enabled:
+            yield
+            return
+        import torch
+
+        ext, cur = self._stream(), torch.cuda.current_stream(torch.device(f"cuda:{self.cfg.device}"))
+        ext.wait_stream(cur)
+        try:
+            yield
+        finally:
+            cur.wait_stream(ext)
+
+    def tick_drivers(self, actions=None, terminal_mask=None, bad_env_flags=L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION,
+                     bad_driver_flags=L.ST_OFF_ROAD | L.ST_COLLISION, auto_reset=True, r_step=0.01, r_bad=-1.0, w_progress=0.0, ordered=True):
+        """One tick of a multi-agent environment entirely on the device (sg_tick_drivers): the step of the drivers (the policy of
+        set_driver_policy ahead of it), the terminal conditions, the drivers' status and -- with w_progress != 0 -- route rows,
+        reward, done, progress and episode statistics per scenario and per driver, and with auto_reset the reset of the scenarios
+        that finished.  actions [n_drivers, 2]: a float64 torch tensor on this GPU (read in stream order behind torch's current
+        stream, no host wait), numpy (copied before the call returns), or None for (0, 0).  terminal_mask: the TERM_* bits that
+        end an episode (None: the engine's terminal conditions).  Returns a dict of zero-copy torch views of the arrays of
+        sg_episode_view -- term_flags, env_done, env_reward, reset_mask, ep_length [R]; drv_flags, drv_info, drv_feat, drv_progress,
+        drv_reward, ep_return, drv_done [n_drivers, ...], and with w_progress != 0 drv_route, drv_route_info (else None) -- written
+        in stream order: torch's current stream is ordered behind the tick, nothing waits on the host (ordered=False: the caller
+        orders the two streams itself, ordered_with_torch).  The views are valid until the next tick_drivers, set_drivers or
+        upload, and the same tensors come back while the addresses stay."""
+        import torch
+
+        nd = getattr(self, "_n_drv", 0)
+        ptr, on_device = None, 0
+        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
+            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == nd * 2
+            ptr, on_device = actions.data_ptr(), 1
+        elif actions is not None:
+            actions = np.ascontiguousarray(actions, np.float64).reshape(nd, 2)
+            ptr = actions.ctypes.data
+        rules = L.SgEpisodeRules(self.cfg.terminal_mask if terminal_mask is None else int(terminal_mask), int(bad_env_flags), int(bad_driver_flags),
+                                 int(bool(auto_reset)), float(r_step), float(r_bad), float(w_progress))
+        view = self.__dict__.setdefault("_ep_view", L.SgEpisodeView())
+        with self.ordered_with_torch(ordered):  # the policy's writes before the tick, what the caller queues next behind it
+            self._check(self.lib.sg_tick_drivers(self.h, ptr, on_device, C.byref(rules), C.byref(view)), "sg_tick_drivers")
+        cache = self.__dict__.setdefault("_ep_views", {})
+        out = {}
+        for k, (name, typestr, cols) in enumerate(L.EPISODE_VIEW):
+            p = getattr(view, name)
+            if not p:
+                out[name] = None
+                continue
+            rows = self.R if k < L.EPISODE_VIEW_PER_SCENARIO else nd
+            key = (name, p, rows)
+            if key not in cache:  # the buffer moved (first call, another driver list): wrap the new address once
+                for old in [q for q in cache if q[0] == name]:
+                    del cache[old]
+                cache[key] = self._device_view(p, (rows, cols) if cols else (rows,), typestr)
+            out[name] = cache[key]
+        return out
+
     def terminal_flags(self):
         """TERM_* bits of every scenario's current state, all four conditions evaluated: uint32 [R]."""
         out = np.zeros(self.R, np.uint32)
@@ -502,6 +582,19 @@ class RolloutEngine:
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
             return out
         return out.astype(bool)
+
+    def raster_map_observers_queued(self, out, layers, width=20.0, height=20.0, nw=20, nh=20, ordered=True):
+        """raster_map_observers into `out`, a contiguous torch uint8 tensor [n, n_layers, nh, nw] on this GPU, without any host
+        wait: the kernel is queued on the engine's stream behind the work of torch's current stream, and torch's current stream
+        is ordered behind it (ordered=False: the caller orders the two streams itself, ordered_with_torch).  Returns `out`."""
+        import torch
+
+        lay = np.ascontiguousarray(layers, np.int32)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (self._n_obs, len(lay), int(nh), int(nw))
+        with self.ordered_with_torch(ordered):
+            self._check(self.lib.sg_raster_map_observers(self.h, float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data,
+                                                         out.data_ptr() if out.numel() else None, 1), "sg_raster_map_observers")
+        return out
 
     def future_collision_observers(self, horizon=5.0, n_samples=10, torch_out=False):
         """FutureCollisionDetector._step (sensor/common.py:87-106) for every observer of set_observers at the current time of

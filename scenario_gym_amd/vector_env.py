@@ -18,6 +18,11 @@ observer list, which the drivers form by default.
 `traffic=`: background traffic that reacts.  Every listed entity is run by the engine's built-in policy (IDM car-following)
 along its own recorded trajectory (`sg_set_driver_policy`): a driver appended behind the caller's drivers, whose actions the
 device makes itself.  A tick is then one `sg_step_drivers_policy`; `step` keeps taking the caller's drivers' actions alone.
+
+With a driver list the reward, the done flags, the progress and the auto-reset of a tick are numpy on the host between synchronous
+calls -- unless `device_tick=True` (with torch_obs): then a tick is one `sg_tick_drivers`, which does all of that on the device in
+stream order, and the observation call queued behind it; actions, rewards, dones and info are tensors in HBM and the host waits for
+nothing.
 """
 from typing import Optional, Sequence
 
@@ -38,7 +43,7 @@ class VectorScenarioEnv:
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
                  drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True,
                  traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None,
-                 driver_progress: Optional[float] = None):
+                 driver_progress: Optional[float] = None, device_tick: bool = False):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
         VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
         driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
@@ -52,7 +57,15 @@ class VectorScenarioEnv:
         every driver gets a route -- its own recorded trajectory unless set_routes gave another -- and every step reports in
         `info` driver_route (the rows of sg_route_observation_observers) and driver_progress (the arclength gained along the
         route since the previous tick; 0 for a driver without a route, not in the scene at either tick, or when reset() or an
-        auto-reset of its environment came in between), and adds w * driver_progress to driver_reward."""
+        auto-reset of its environment came in between), and adds w * driver_progress to driver_reward.
+        device_tick: with `drivers` and torch_obs, a tick is ONE sg_tick_drivers -- step, terminal conditions, driver status and
+        route rows, reward, done, progress, episode statistics and the auto-reset, all on the device in stream order -- and the
+        observation call behind it.  `step` takes a float64 tensor [n_drivers, 2] on the device and returns torch tensors in HBM
+        alone, ordered on torch's current stream; nothing is copied to the host and nothing waits for the device.  The values are
+        those of the default path, bit for bit; `info` also carries episode_return [n_drivers] and episode_length [R] (of the
+        episode up to and including this tick).  The tensors are views of buffers the engine owns: the next step overwrites
+        them.  No `done` bookkeeping is kept on the host: auto_reset=False never resets and never raises -- a finished environment
+        simply goes on stepping, and the caller decides (reset(), engine.reset_scenarios_device)."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -64,6 +77,12 @@ class VectorScenarioEnv:
         self.driver_progress = None if driver_progress is None else float(driver_progress)
         if self.driver_progress is not None and (drivers is None or not self.driver_status):
             raise ValueError("driver_progress: needs a driver list (drivers=...) with driver_status")
+
+        self.device_tick = bool(device_tick)
+        if self.device_tick and (drivers is None or not torch_obs):
+            raise ValueError("device_tick: needs a driver list (drivers=...) and torch_obs=True")
+        if self.device_tick and self.driver_progress == 0.0:
+            raise ValueError("device_tick: driver_progress=0 launches no route observation; pass None to switch the term off")
 
         if drivers is not None and len(drivers) != len(self.scenarios):
             raise ValueError("drivers: one list of entity indices per environment")
@@ -168,6 +187,8 @@ class VectorScenarioEnv:
         Returns (obs, reward [R], done [R], info).  With auto_reset the environments that finished are reset and their
         observation is the first of the new episode; without it, stepping a finished environment raises as the reference's
         `step` does."""
+        if self.device_tick:
+            return self._step_device(actions)
         if not self.auto_reset and self.done.any():
             raise ValueError("Step called when state is terminal.")
         if self._drv_env is not None:
@@ -237,6 +258,32 @@ class VectorScenarioEnv:
             if self._route_s0 is not None:  # a new episode: its first tick has no previous arclength
                 self._route_s0[1][done[self._drv_env]] = False
         return self._observe(), reward, done, info
+
+    def _step_device(self, actions):
+        """step() with device_tick: one sg_tick_drivers and the observation call, no host round trip (see __init__)."""
+        import torch
+
+        nd, nt = self.n_drivers, self.n_traffic
+        actions = actions.reshape(nd, 2)
+        if nt:  # the traffic's rows follow the caller's; the policy fills them on the device
+            if getattr(self, "_dev_actions", None) is None:
+                self._dev_actions = actions.new_zeros((nd + nt, 2))
+            self._dev_actions[:nd].copy_(actions)
+            actions = self._dev_actions
+        shape = (len(self._obs_env),) + self.observation_shape
+        if getattr(self, "_dev_obs", None) is None or tuple(self._dev_obs.shape) != shape:
+            self._dev_obs = torch.empty(shape, dtype=torch.uint8, device=actions.device)
+        with self.engine.ordered_with_torch():  # the tick and the observation behind the policy's writes, as one
+            v = self.engine.tick_drivers(actions.contiguous(), terminal_mask=self._mask, auto_reset=self.auto_reset,
+                                         w_progress=self.driver_progress or 0.0, ordered=False)
+            obs = self.engine.raster_map_observers_queued(self._dev_obs, self._codes, self.width, self.height, self.n, self.n, ordered=False)
+        info = {"terminal_flags": v["term_flags"], "episode_return": v["ep_return"][:nd], "episode_length": v["ep_length"]}
+        if self.driver_status and nd:
+            info.update(driver_flags=v["drv_flags"][:nd], driver_info=v["drv_info"][:nd], driver_feat=v["drv_feat"][:nd],
+                        driver_reward=v["drv_reward"][:nd], driver_done=v["drv_done"][:nd].view(torch.bool))
+            if self.driver_progress is not None:
+                info.update(driver_route=v["drv_route"][:nd], driver_progress=v["drv_progress"][:nd])
+        return obs, v["env_reward"], v["env_done"].view(torch.bool), info
 
     def _driver_status(self):
         """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays."""
