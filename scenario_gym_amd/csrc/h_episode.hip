@@ -1,6 +1,6 @@
-// h_episode.hip -- the multi-agent tick on the device (sg_tick_drivers): the step of the drivers, the terminal conditions, the drivers'
-// status and route rows, episode_kernel (sgym_episode.hpp) and the auto-reset, one behind the other on the handle's stream; the
-// buffer that holds the episode accounting and the arrays of sg_episode_view.
+// h_episode.hip -- the multi-agent tick on the device (sg_tick_drivers): the step of the drivers (drivers_step, h_drive.hip), the
+// terminal conditions, the drivers' status and route rows, episode_kernel (sgym_episode.hpp) and the auto-reset, one behind the other
+// on the handle's stream; the buffer that holds the episode accounting and the arrays of sg_episode_view.
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -10,8 +10,8 @@ using namespace sgh;
 // anything (sg_set_drivers has waited for the stream by then).
 static int episode_layout(sg_handle *h)
 {
-    const size_t n = (size_t)h->n_drv, R = (size_t)h->R;
-    if (h->ep_n == h->n_drv && h->episode.ptr) return SG_OK;
+    const size_t n = (size_t)h->drivers.n, R = (size_t)h->R;
+    if (h->ep_n == h->drivers.n && h->episode.ptr) return SG_OK;
     const auto pad8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
     const size_t state = pad8(2 * n * sizeof(double) + R * sizeof(int32_t) + n);
     const size_t doubles = R + n * (SG_ST_NFEAT + SG_RT_NFEAT + 3), ints = 2 * R + n * (1 + SG_ST_NINFO + SG_RT_NINFO), bytes = 2 * R + n;
@@ -42,7 +42,7 @@ static int episode_layout(sg_handle *h)
     v.drv_flags = drv_flags; v.drv_info = drv_info; v.drv_feat = drv_feat; v.drv_route = drv_route; v.drv_route_info = drv_route_info;
     v.drv_progress = a.drv_progress; v.drv_reward = a.drv_reward; v.ep_return = a.ep_return; v.drv_done = a.drv_done;
     h->ep_state_bytes = state;
-    h->ep_n = h->n_drv;
+    h->ep_n = h->drivers.n;
     return SG_OK;
 }
 
@@ -50,11 +50,11 @@ static int episode_layout(sg_handle *h)
 // episode in progress there is nothing to clear: the next tick zeroes everything.
 int sgh::episode_clear_masked(sg_handle *h, const uint8_t *d_mask)
 {
-    if (!h->ep_live || h->n_drv == 0 || h->ep_n != h->n_drv) return SG_OK;
+    if (!h->ep_live || h->drivers.n == 0 || h->ep_n != h->drivers.n) return SG_OK;
     sg::EpisodeArgs a = h->ep;
     a.R = h->R;
-    a.n_drv = h->n_drv;
-    a.scen = driver_scenarios(h);
+    a.n_drv = h->drivers.n;
+    a.scen = h->drivers.scenarios();
     sgl::episode_clear(h->stream, d_mask, a);
     HIP_TRY(h, hipGetLastError());
     return SG_OK;
@@ -68,7 +68,7 @@ extern "C" int sg_tick_drivers(sg_handle *h, const double *actions, int32_t acti
     if (!std::isfinite(rules->r_step) || !std::isfinite(rules->r_bad) || !std::isfinite(rules->w_progress))
         return fail(h, SG_ERR_INVALID, "%s: r_step, r_bad and w_progress must be finite", who);
     if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    if (h->n_drv == 0) return fail(h, SG_ERR_STATE, "%s: no drivers set (sg_set_drivers)", who);
+    if (h->drivers.n == 0) return fail(h, SG_ERR_STATE, "%s: no drivers set (sg_set_drivers)", who);
     if (const int rc = queue_gave_up(h)) return rc; // (sticky: nothing more is queued on a batch whose state is undefined)
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (const int rc = episode_layout(h)) return rc;
@@ -76,18 +76,18 @@ extern "C" int sg_tick_drivers(sg_handle *h, const double *actions, int32_t acti
         HIP_TRY(h, hipMemsetAsync(h->episode.ptr, 0, h->ep_state_bytes, h->stream));
     h->ep_live = true;
     const bool progress = rules->w_progress != 0.0;
-    const int32_t *d_scen = driver_scenarios(h), *d_slot = driver_slots(h);
+    const int32_t *d_scen = h->drivers.scenarios(), *d_slot = h->drivers.slots();
     // 1 - 3: the policy, the drivers' controllers, the step
-    if (const int rc = drivers_step_queued(h, who, actions, actions_device)) return rc;
+    if (const int rc = drivers_step(h, 1, actions, actions_device, h->n_pol > 0, true)) return rc;
     // 4 - 6: what the rules read, of the stepped state
     const sg_episode_view &v = h->ep_view;
     sgl::terminal_flags(dim3((unsigned)h->R), h->stream, h->p, h->cfg.timestep, const_cast<uint32_t *>(v.term_flags));
     HIP_TRY(h, hipGetLastError());
-    sgl::entity_status(h->stream, h->p, d_scen, d_slot, h->n_drv, const_cast<uint32_t *>(v.drv_flags), const_cast<int32_t *>(v.drv_info),
+    sgl::entity_status(h->stream, h->p, d_scen, d_slot, h->drivers.n, const_cast<uint32_t *>(v.drv_flags), const_cast<int32_t *>(v.drv_info),
                        const_cast<double *>(v.drv_feat));
     HIP_TRY(h, hipGetLastError());
     if (progress) {
-        sgl::route_observation(h->stream, h->p, h->route, d_scen, d_slot, h->n_drv, 0, 0.0, const_cast<double *>(v.drv_route),
+        sgl::route_observation(h->stream, h->p, h->route, d_scen, d_slot, h->drivers.n, 0, 0.0, const_cast<double *>(v.drv_route),
                                const_cast<int32_t *>(v.drv_route_info));
         HIP_TRY(h, hipGetLastError());
     }
@@ -97,7 +97,7 @@ extern "C" int sg_tick_drivers(sg_handle *h, const double *actions, int32_t acti
     a.auto_reset = rules->auto_reset;
     a.r_step = rules->r_step; a.r_bad = rules->r_bad; a.w_progress = rules->w_progress;
     a.R = h->R;
-    a.n_drv = h->n_drv;
+    a.n_drv = h->drivers.n;
     a.scen = d_scen;
     sgl::episode(h->stream, a);
     HIP_TRY(h, hipGetLastError());

@@ -1,21 +1,10 @@
-// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, map, look-ahead, nearest-entity,
-// lane-frame, range-scan and route observations and the episode status of the ego and of a list of observers; the routes.
+// h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, and -- each one observe() (sgym_host.hpp) behind its
+// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan and route observations and the episode status of the ego
+// and of a list of observers; the lists of (scenario, slot) pairs (check_pairs, EntityList::upload); the path tables (PathTable) and
+// the routes.
 #include "sgym_host.hpp"
 
 using namespace sgh;
-
-// device scratch shared by the observation entry points: a tick of an RL loop calls them once per step, a hipMalloc /
-// hipFree pair per call would cost more than the kernels
-static int obs_scratch(sg_handle *h, size_t bytes, unsigned char **out)
-{
-    if (bytes > h->obs.cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (const int rc = h->obs.ensure(h, bytes)) return rc;
-        ++h->generation;
-    }
-    *out = h->obs.as<unsigned char>();
-    return SG_OK;
-}
 
 // the layer codes of a map observation: 0 (the entities) or one SG_LAYER_* bit each
 static int check_layers(sg_handle *h, const char *who, int32_t n_layers, const int32_t *layers)
@@ -60,11 +49,11 @@ static int raster_map_launch(sg_handle *h, const char *who, double width, double
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t bytes = (size_t)h->R * n_layers * nw * nh;
     if (out)
-        return deliver(h, who, false, obs_scratch, {{out, bytes}}, 0, [&](void *const *d) {
+        return deliver(h, who, false, h->obs, {{out, bytes}}, 0, [&](void *const *d) {
             return enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, static_cast<unsigned char *>(d[0]));
         });
     unsigned char *d = nullptr;
-    if (const int rc = obs_scratch(h, bytes, &d)) return rc;
+    if (const int rc = scratch(h, h->obs, bytes, &d)) return rc;
     HIP_TRY(h, enqueue_map_layers(h, width, height, nw, nh, n_layers, layers, d));
     *d_out = d;
     return SG_OK;
@@ -115,7 +104,7 @@ extern "C" int sg_tick(sg_handle *h, const double *actions, int32_t actions_devi
     double *const d_actions = h->actions.as<double>();
     uint32_t *const d_term_flags = h->term_flags.as<uint32_t>();
     unsigned char *d = nullptr;
-    if ((rc = obs_scratch(h, (size_t)h->R * n_layers * nw * nh, &d))) return rc;
+    if ((rc = scratch(h, h->obs, (size_t)h->R * n_layers * nw * nh, &d))) return rc;
     // sg_set_rss: the callback runs after the step, inside the captured launch (like sg_step; without records of a reset --
     // the callback was switched on after sg_upload -- through sg_rss_update after the graph)
     if (h->wide && (rc = ensure_wide(h))) return rc;
@@ -190,64 +179,76 @@ extern "C" int sg_terminal_flags(sg_handle *h, uint32_t *out, const uint32_t **d
     return SG_OK;
 }
 
-// ---- observations for any entity: a list of observers (sgym_observers.hpp) -----------------------------------------------
-// the observer list on the device: the scenarios in the first half of the buffer, the slots in the second
-static int32_t *observer_scenarios(const sg_handle *h) { return h->observers.as<int32_t>(); }
-static int32_t *observer_slots(const sg_handle *h) { return h->observers.as<int32_t>() + h->observers.cap / (2 * sizeof(int32_t)); }
 
-extern "C" int sg_set_observers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot)
+// ---- lists of (scenario, slot) pairs: the observers here, the drivers in h_drive.hip, the owners of the routes below ----------------
+int sgh::check_pairs(sg_handle *h, const char *who, int64_t n, const int32_t *scenario, const int32_t *slot, unsigned rules)
 {
-    if (!h) return SG_ERR_INVALID;
-    h->n_obs = 0; // a refused call leaves the handle without observers
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_set_observers: no scenarios uploaded");
-    if (n < 0 || (n > 0 && (!scenario || !slot))) return fail(h, SG_ERR_INVALID, "sg_set_observers: n < 0 or null array");
-    if (n > 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "sg_set_observers: more than 2^31 - 1 observers (one workgroup each: the grid limit)");
+    std::vector<uint8_t> listed((rules & PAIR_ONCE) && n > 0 ? (size_t)h->R * h->E : 0, 0);
     for (int64_t k = 0; k < n; ++k) {
-        if (scenario[k] < 0 || scenario[k] >= h->R) return fail(h, SG_ERR_INVALID, "sg_set_observers: scenario[%lld]=%d out of range", (long long)k, scenario[k]);
-        if (slot[k] < 0 || slot[k] >= h->E) return fail(h, SG_ERR_INVALID, "sg_set_observers: slot[%lld]=%d out of range", (long long)k, slot[k]);
-        if (h->slot_empty[(size_t)scenario[k] * h->E + slot[k]])
-            return fail(h, SG_ERR_INVALID, "sg_set_observers: slot %d of scenario %d holds no entity (SG_KIND_NONE)", slot[k], scenario[k]);
+        if (scenario[k] < 0 || scenario[k] >= h->R) return fail(h, SG_ERR_INVALID, "%s: scenario[%lld]=%d out of range", who, (long long)k, scenario[k]);
+        if (slot[k] < 0 || slot[k] >= h->E) return fail(h, SG_ERR_INVALID, "%s: slot[%lld]=%d out of range", who, (long long)k, slot[k]);
+        const size_t i = (size_t)scenario[k] * h->E + slot[k];
+        if ((rules & PAIR_HOLDS_ENTITY) && h->slot_empty[i])
+            return fail(h, SG_ERR_INVALID, "%s: slot %d of scenario %d holds no entity (SG_KIND_NONE)", who, slot[k], scenario[k]);
+        if ((rules & PAIR_EXTERNAL) && !h->slot_external[i])
+            return fail(h, SG_ERR_INVALID, "%s: slot %d of scenario %d is not an SG_KIND_AGENT_EXTERNAL slot", who, slot[k], scenario[k]);
+        if (rules & PAIR_ONCE) { // (two drivers of one slot would race on one speed cell and one pose row)
+            if (listed[i]) return fail(h, SG_ERR_INVALID, "%s: slot %d of scenario %d is listed twice", who, slot[k], scenario[k]);
+            listed[i] = 1;
+        }
     }
-    if (n == 0) return SG_OK;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued observation call may still read the previous list)
-    if (const int rc = h->observers.ensure(h, (size_t)n * 2 * sizeof(int32_t))) return rc;
-    HIP_TRY(h, hipMemcpy(observer_scenarios(h), scenario, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(observer_slots(h), slot, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->n_obs = n;
     return SG_OK;
 }
 
+int sgh::EntityList::upload(sg_handle *h, int64_t n_new, const int32_t *scenario, const int32_t *slot)
+{
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    n = 0;
+    if (const int rc = buf.ensure(h, (size_t)n_new * 2 * sizeof(int32_t))) return rc;
+    HIP_TRY(h, hipMemcpy(scenarios(), scenario, (size_t)n_new * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(slots(), slot, (size_t)n_new * sizeof(int32_t), hipMemcpyHostToDevice));
+    n = n_new;
+    return SG_OK;
+}
+
+// ---- observations for any entity: a list of observers (sgym_observers.hpp) -----------------------------------------------
+extern "C" int sg_set_observers(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot)
+{
+    const char *who = "sg_set_observers";
+    if (!h) return SG_ERR_INVALID;
+    h->observers.n = 0; // a refused call leaves the handle without observers
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    if (n < 0 || (n > 0 && (!scenario || !slot))) return fail(h, SG_ERR_INVALID, "%s: n < 0 or null array", who);
+    if (n > 0x7fffffffLL) return fail(h, SG_ERR_INVALID, "%s: more than 2^31 - 1 observers (one workgroup each: the grid limit)", who);
+    if (const int rc = check_pairs(h, who, n, scenario, slot, PAIR_HOLDS_ENTITY)) return rc;
+    return n == 0 ? SG_OK : h->observers.upload(h, n, scenario, slot);
+}
+
+// Every observation below is observe() (sgym_host.hpp) behind its own argument checks: n observers -- the ego of every scenario
+// (observers == false) or the list of sg_set_observers --, the bytes of its output arrays per observer, its launch.  Host outputs
+// pass through the observation scratch, one array behind the other in the order of the list (the optional ones only when asked for).
 extern "C" int sg_raster_map_observers(sg_handle *h, double width, double height, int32_t nw, int32_t nh, int32_t n_layers,
                                        const int32_t *layers, uint8_t *out, int32_t outputs_device)
 {
+    const char *who = "sg_raster_map_observers";
     if (!h) return SG_ERR_INVALID;
-    if (bad_map_geometry(width, height, nw, nh, n_layers, layers) || n_layers > 8) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: bad argument");
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "sg_raster_map_observers: no scenarios uploaded");
-    if (const int rc = check_layers(h, "sg_raster_map_observers", n_layers, layers)) return rc;
-    if (h->n_obs == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!out) return fail(h, SG_ERR_INVALID, "sg_raster_map_observers: null out");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (bad_map_geometry(width, height, nw, nh, n_layers, layers) || n_layers > 8) return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
+    if (h->uploaded) // (the layer codes are judged behind the handle's state, which observe() refuses)
+        if (const int rc = check_layers(h, who, n_layers, layers)) return rc;
     const size_t bytes_each = (size_t)n_layers * nw * nh;
-    return deliver(h, "sg_raster_map_observers", outputs_device, obs_scratch, {{out, (size_t)h->n_obs * bytes_each}}, 0, [&](void *const *d) {
-        sgl::map_raster(h->stream, h->p, h->road, h->has_road, observer_scenarios(h), observer_slots(h), h->n_obs, width, height, nw, nh, n_layers,
-                        layers, static_cast<unsigned char *>(d[0]), (int64_t)bytes_each);
+    return observe(h, who, true, outputs_device, 0, "out", {{out, bytes_each}}, [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
+        sgl::map_raster(h->stream, h->p, h->road, h->has_road, d_scen, d_slot, n, width, height, nw, nh, n_layers, layers, static_cast<unsigned char *>(d[0]),
+                        (int64_t)bytes_each);
         return hipGetLastError();
     });
 }
 
-// ---- the look-ahead (look_ahead_kernel, sgym_observers.hpp) ---------------------------------------------------------------
-// n observers: the ego of every scenario (observers == false) or the list of sg_set_observers; one byte each
+// ---- the look-ahead (look_ahead_kernel, sgym_observers.hpp): one byte each ---------------------------------------------------
 static int future_call(sg_handle *h, const char *who, bool observers, double horizon, int32_t n_samples, uint8_t *out, int32_t outputs_device)
 {
     if (n_samples < 1 || !(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: bad argument", who);
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!out) return fail(h, SG_ERR_INVALID, "%s: null out", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    return deliver(h, who, outputs_device, obs_scratch, {{out, (size_t)n}}, 0, [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 0, "out", {{out, 1}}, [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
         sgl::look_ahead(h->stream, h->p, d_scen, d_slot, n, horizon, n_samples, static_cast<unsigned char *>(d[0]));
         return hipGetLastError();
     });
@@ -265,23 +266,14 @@ extern "C" int sg_future_collision_observers(sg_handle *h, double horizon, int32
     return future_call(h, "sg_future_collision_observers", true, horizon, n_samples, out, outputs_device);
 }
 
-// ---- the nearest-entity vector observation (nearest_kernel, sgym_observers.hpp) -------------------------------------------
-// n observers: the ego of every scenario (observers == false) or the list of sg_set_observers.  Host outputs pass through the
-// observation scratch: [n][k][8] doubles, then [n][k] slots, then [n] counts (the last two only when asked for).
+// ---- the nearest-entity vector observation (nearest_kernel, sgym_observers.hpp): [k][8] doubles, [k] slots, a count --------------
 static int nearest_call(sg_handle *h, const char *who, bool observers, int32_t k, double radius, double *feat, int32_t *slots,
                         int32_t *count, int32_t outputs_device)
 {
     if (k < 1 || k > SG_NEAR_MAX_K) return fail(h, SG_ERR_INVALID, "%s: k=%d outside 1..%d", who, k, SG_NEAR_MAX_K);
     if (!(radius >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: radius is negative or NaN", who);
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    const size_t nk = (size_t)n * k;
-    return deliver(h, who, outputs_device, obs_scratch, {{feat, nk * 8 * sizeof(double)}, {slots, nk * sizeof(int32_t)}, {count, (size_t)n * sizeof(int32_t)}}, 0,
-                   [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 0, "feat", {{feat, (size_t)k * 8 * sizeof(double)}, {slots, (size_t)k * sizeof(int32_t)}, {count, sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
                        sgl::nearest(h->stream, h->p, d_scen, d_slot, n, k, radius, static_cast<double *>(d[0]), static_cast<int32_t *>(d[1]),
                                     static_cast<int32_t *>(d[2]));
                        return hipGetLastError();
@@ -301,9 +293,8 @@ extern "C" int sg_nearest_entities_observers(sg_handle *h, int32_t k, double rad
     return nearest_call(h, "sg_nearest_entities_observers", true, k, radius, feat, slots, count, outputs_device);
 }
 
-// ---- the lane-frame vector observation (lane_observation_kernel, sgym_observers.hpp) ---------------------------------------
-// n observers as above.  Host outputs pass through the observation scratch: [n][k][6 + 2 * n_ahead] doubles, then [n][k] lane
-// indices, then [n] counts (the last two only when asked for).
+// ---- the lane-frame vector observation (lane_observation_kernel, sgym_observers.hpp): [k][6 + 2 * n_ahead] doubles, [k] lane
+// indices, a count ------------------------------------------------------------------------------------------------------------
 static int lane_call(sg_handle *h, const char *who, bool observers, int32_t k, int32_t n_ahead, double spacing, double radius, double *feat,
                      int32_t *lanes, int32_t *count, int32_t outputs_device)
 {
@@ -311,16 +302,9 @@ static int lane_call(sg_handle *h, const char *who, bool observers, int32_t k, i
     if (n_ahead < 0 || n_ahead > SG_LANE_MAX_AHEAD) return fail(h, SG_ERR_INVALID, "%s: n_ahead=%d outside 0..%d", who, n_ahead, SG_LANE_MAX_AHEAD);
     if (!(spacing >= 0.0) || std::isinf(spacing)) return fail(h, SG_ERR_INVALID, "%s: spacing is negative, infinite or NaN", who);
     if (!(radius >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: radius is negative or NaN", who);
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    const size_t nk = (size_t)n * k;
-    return deliver(h, who, outputs_device, obs_scratch,
-                   {{feat, nk * (6 + 2 * (size_t)n_ahead) * sizeof(double)}, {lanes, nk * sizeof(int32_t)}, {count, (size_t)n * sizeof(int32_t)}}, 0,
-                   [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 0, "feat",
+                   {{feat, (size_t)k * (6 + 2 * (size_t)n_ahead) * sizeof(double)}, {lanes, (size_t)k * sizeof(int32_t)}, {count, sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
                        sgl::lane_observation(h->stream, h->p, h->lanes, d_scen, d_slot, n, k, n_ahead, spacing, radius, static_cast<double *>(d[0]),
                                              static_cast<int32_t *>(d[1]), static_cast<int32_t *>(d[2]));
                        return hipGetLastError();
@@ -341,24 +325,15 @@ extern "C" int sg_lane_observation_observers(sg_handle *h, int32_t k, int32_t n_
     return lane_call(h, "sg_lane_observation_observers", true, k, n_ahead, spacing, radius, feat, lanes, count, outputs_device);
 }
 
-// ---- the range scan (range_scan_kernel, sgym_observers.hpp) ----------------------------------------------------------------
-// n observers as above.  Host outputs pass through the observation scratch: [n][n_rays][2] doubles, then [n][n_rays] slots, then
-// [n] hit counts (the last two only when asked for).
+// ---- the range scan (range_scan_kernel, sgym_observers.hpp): [n_rays][2] doubles, [n_rays] slots, a hit count ---------------------
 static int scan_call(sg_handle *h, const char *who, bool observers, int32_t n_rays, double angle0, double dangle, double max_range, double *feat,
                      int32_t *slots, int32_t *hits, int32_t outputs_device)
 {
     if (n_rays < 1 || n_rays > SG_SCAN_MAX_RAYS) return fail(h, SG_ERR_INVALID, "%s: n_rays=%d outside 1..%d", who, n_rays, SG_SCAN_MAX_RAYS);
     if (!std::isfinite(angle0) || !std::isfinite(dangle)) return fail(h, SG_ERR_INVALID, "%s: angle0 or dangle is infinite or NaN", who);
     if (!(max_range >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: max_range is negative or NaN", who);
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    const size_t nb = (size_t)n * n_rays;
-    return deliver(h, who, outputs_device, obs_scratch, {{feat, nb * 2 * sizeof(double)}, {slots, nb * sizeof(int32_t)}, {hits, (size_t)n * sizeof(int32_t)}}, 0,
-                   [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 0, "feat", {{feat, (size_t)n_rays * 2 * sizeof(double)}, {slots, (size_t)n_rays * sizeof(int32_t)}, {hits, sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
                        sgl::range_scan(h->stream, h->p, d_scen, d_slot, n, n_rays, angle0, dangle, max_range, static_cast<double *>(d[0]),
                                        static_cast<int32_t *>(d[1]), static_cast<int32_t *>(d[2]));
                        return hipGetLastError();
@@ -379,20 +354,12 @@ extern "C" int sg_range_scan_observers(sg_handle *h, int32_t n_rays, double angl
     return scan_call(h, "sg_range_scan_observers", true, n_rays, angle0, dangle, max_range, feat, slots, hits, outputs_device);
 }
 
-// ---- the entity status (entity_status_kernel, sgym_observers.hpp) ----------------------------------------------------------
-// n observers as above.  Host outputs pass through the observation scratch, the doubles first: [n][SG_ST_NFEAT] doubles, then
-// [n][SG_ST_NINFO] ints, then [n] flag words (the first two only when asked for).
+// ---- the entity status (entity_status_kernel, sgym_observers.hpp): the doubles first -- [SG_ST_NFEAT] doubles, [SG_ST_NINFO] ints,
+// a flag word ---------------------------------------------------------------------------------------------------------------------
 static int status_call(sg_handle *h, const char *who, bool observers, uint32_t *flags, int32_t *info, double *feat, int32_t outputs_device)
 {
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!flags) return fail(h, SG_ERR_INVALID, "%s: null flags", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    return deliver(h, who, outputs_device, obs_scratch,
-                   {{feat, (size_t)n * SG_ST_NFEAT * sizeof(double)}, {info, (size_t)n * SG_ST_NINFO * sizeof(int32_t)}, {flags, (size_t)n * sizeof(uint32_t)}}, 0,
-                   [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 2, "flags", {{feat, SG_ST_NFEAT * sizeof(double)}, {info, SG_ST_NINFO * sizeof(int32_t)}, {flags, sizeof(uint32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
                        sgl::entity_status(h->stream, h->p, d_scen, d_slot, n, static_cast<uint32_t *>(d[2]), static_cast<int32_t *>(d[1]),
                                           static_cast<double *>(d[0]));
                        return hipGetLastError();
@@ -411,6 +378,34 @@ extern "C" int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t
     return status_call(h, "sg_entity_status_observers", true, flags, info, feat, outputs_device);
 }
 
+// ---- path tables: the polylines of sg_set_routes below and of sg_set_driver_policy (h_drive.hip) -------------------------------------
+void sgh::PathTable::build(int64_t m, const int64_t *pt_off, const double *pts)
+{
+    const size_t d0 = dbl.size(), i0 = ints.size();
+    dbl.resize(d0 + (size_t)m);
+    ints.resize(i0 + (size_t)m + 1);
+    for (int64_t j = 0; j < m; ++j) { // the rows of sg_set_lanes (h_road.hip), path by path
+        const int32_t first = (int32_t)segs.size();
+        ints[i0 + (size_t)j] = first;
+        dbl[d0 + (size_t)j] = append_segments(segs, pts, pt_off[j], pt_off[j + 1], (int32_t)j, first);
+    }
+    ints[i0 + (size_t)m] = (int32_t)segs.size();
+}
+
+int sgh::PathTable::upload(sg_handle *h, GrowBuf &buf, const double **d_dbl, const sg::LaneSeg **d_seg, const int32_t **d_ints) const
+{
+    const size_t b_dbl = dbl.size() * sizeof(double), b_seg = segs.size() * sizeof(sg::LaneSeg), b_int = ints.size() * sizeof(int32_t);
+    if (const int rc = buf.ensure(h, b_dbl + b_seg + b_int)) return rc;
+    unsigned char *base = buf.as<unsigned char>();
+    HIP_TRY(h, hipMemcpy(base, dbl.data(), b_dbl, hipMemcpyHostToDevice));
+    if (b_seg) HIP_TRY(h, hipMemcpy(base + b_dbl, segs.data(), b_seg, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(base + b_dbl + b_seg, ints.data(), b_int, hipMemcpyHostToDevice));
+    *d_dbl = reinterpret_cast<const double *>(base);
+    *d_seg = reinterpret_cast<const sg::LaneSeg *>(base + b_dbl);
+    *d_ints = reinterpret_cast<const int32_t *>(base + b_dbl + b_seg);
+    return SG_OK;
+}
+
 // ---- routes and the route / recorded-track observation (route_observation_kernel, sgym_observers.hpp) ------------------------
 extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, const int32_t *slot, const int64_t *pt_off, const double *pts)
 {
@@ -425,15 +420,12 @@ extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, c
         return SG_OK;
     }
     if (n > (int64_t)h->R * h->E) return fail(h, SG_ERR_INVALID, "%s: more routes than entity slots: a pair is listed twice", who);
-    std::vector<int32_t> ints((size_t)(n + 1) + (size_t)h->R * h->EP, -1); // seg_off [n + 1], then route_of [R * EP]
-    int32_t *const route_of = ints.data() + (n + 1);
+    if (const int rc = check_pairs(h, who, n, scenario, slot, PAIR_ONCE)) return rc;
+    PathTable t; // doubles: total [n]; ints: route_of [R * EP], then seg_off [n + 1]
+    t.ints.assign((size_t)h->R * h->EP, -1);
     int64_t n_seg = 0;
     for (int64_t j = 0; j < n; ++j) {
-        if (scenario[j] < 0 || scenario[j] >= h->R) return fail(h, SG_ERR_INVALID, "%s: scenario[%lld]=%d out of range", who, (long long)j, scenario[j]);
-        if (slot[j] < 0 || slot[j] >= h->E) return fail(h, SG_ERR_INVALID, "%s: slot[%lld]=%d out of range", who, (long long)j, slot[j]);
-        int32_t &of = route_of[(size_t)scenario[j] * h->EP + slot[j]];
-        if (of >= 0) return fail(h, SG_ERR_INVALID, "%s: slot %d of scenario %d is listed twice", who, slot[j], scenario[j]);
-        of = (int32_t)j;
+        t.ints[(size_t)scenario[j] * h->EP + slot[j]] = (int32_t)j;
         if (pt_off[0] != 0 || pt_off[j + 1] < pt_off[j]) return fail(h, SG_ERR_INVALID, "%s: pt_off not monotone from 0", who);
         n_seg += std::max<int64_t>(pt_off[j + 1] - pt_off[j] - 1, 0);
         if (n_seg >= 0x80000000LL) return fail(h, SG_ERR_INVALID, "%s: 2^31 or more segments", who);
@@ -442,50 +434,29 @@ extern "C" int sg_set_routes(sg_handle *h, int64_t n, const int32_t *scenario, c
     if (n_pts > 0 && !pts) return fail(h, SG_ERR_INVALID, "%s: null pts", who);
     for (int64_t i = 0; i < 2 * n_pts; ++i)
         if (!std::isfinite(pts[i])) return fail(h, SG_ERR_INVALID, "%s: pts[%lld] is not finite", who, (long long)(i / 2));
-    // the rows of sg_set_lanes (h_road.hip), route by route
-    std::vector<sg::LaneSeg> segs;
-    segs.reserve((size_t)n_seg);
-    std::vector<double> total((size_t)n);
-    for (int64_t j = 0; j < n; ++j) {
-        const int32_t first = (int32_t)segs.size();
-        ints[(size_t)j] = first;
-        total[(size_t)j] = append_segments(segs, pts, pt_off[j], pt_off[j + 1], (int32_t)j, first);
-        if (!std::isfinite(total[(size_t)j])) return fail(h, SG_ERR_INVALID, "%s: the length of route %lld is not finite", who, (long long)j);
-    }
-    ints[(size_t)n] = (int32_t)segs.size();
+    t.segs.reserve((size_t)n_seg);
+    t.build(n, pt_off, pts);
+    for (int64_t j = 0; j < n; ++j)
+        if (!std::isfinite(t.dbl[(size_t)j])) return fail(h, SG_ERR_INVALID, "%s: the length of route %lld is not finite", who, (long long)j);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, hipStreamSynchronize(h->stream)); // (a queued sg_route_observation may still read the previous routes)
     forget_routes(h); // (from here on the old routes are gone: a failure of the runtime leaves the handle without any)
     forget_episodes(h); // (the arclengths sg_tick_drivers remembers were along the old routes)
-    const size_t b_dbl = total.size() * sizeof(double), b_seg = segs.size() * sizeof(sg::LaneSeg), b_int = ints.size() * sizeof(int32_t);
-    if (const int rc = h->routes.ensure(h, b_dbl + b_seg + b_int)) return rc;
-    unsigned char *base = h->routes.as<unsigned char>();
-    HIP_TRY(h, hipMemcpy(base, total.data(), b_dbl, hipMemcpyHostToDevice));
-    if (b_seg) HIP_TRY(h, hipMemcpy(base + b_dbl, segs.data(), b_seg, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(base + b_dbl + b_seg, ints.data(), b_int, hipMemcpyHostToDevice));
-    h->route.total = reinterpret_cast<const double *>(base);
-    h->route.seg = reinterpret_cast<const sg::LaneSeg *>(base + b_dbl);
-    h->route.seg_off = reinterpret_cast<const int32_t *>(base + b_dbl + b_seg);
-    h->route.route_of = h->route.seg_off + (n + 1);
+    sg::RouteIndex r{};
+    if (const int rc = t.upload(h, h->routes, &r.total, &r.seg, &r.route_of)) return rc;
+    r.seg_off = r.route_of + (size_t)h->R * h->EP;
+    h->route = r;
     return SG_OK;
 }
 
-// n observers as above.  Host outputs pass through the observation scratch, the doubles first: [n][SG_RT_NFEAT + 2 * n_ahead]
-// doubles, then [n][SG_RT_NINFO] ints (only when asked for).
+// [SG_RT_NFEAT + 2 * n_ahead] doubles, [SG_RT_NINFO] ints
 static int route_call(sg_handle *h, const char *who, bool observers, int32_t n_ahead, double spacing, double *feat, int32_t *info,
                       int32_t outputs_device)
 {
     if (n_ahead < 0 || n_ahead > SG_ROUTE_MAX_AHEAD) return fail(h, SG_ERR_INVALID, "%s: n_ahead=%d outside 0..%d", who, n_ahead, SG_ROUTE_MAX_AHEAD);
     if (!(spacing >= 0.0) || std::isinf(spacing)) return fail(h, SG_ERR_INVALID, "%s: spacing is negative, infinite or NaN", who);
-    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
-    const int64_t n = observers ? h->n_obs : (int64_t)h->R;
-    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
-    if (!feat) return fail(h, SG_ERR_INVALID, "%s: null feat", who);
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    const int32_t *d_scen = observers ? observer_scenarios(h) : nullptr, *d_slot = observers ? observer_slots(h) : nullptr;
-    return deliver(h, who, outputs_device, obs_scratch,
-                   {{feat, (size_t)n * (SG_RT_NFEAT + 2 * (size_t)n_ahead) * sizeof(double)}, {info, (size_t)n * SG_RT_NINFO * sizeof(int32_t)}}, 0,
-                   [&](void *const *d) {
+    return observe(h, who, observers, outputs_device, 0, "feat", {{feat, (SG_RT_NFEAT + 2 * (size_t)n_ahead) * sizeof(double)}, {info, SG_RT_NINFO * sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
                        sgl::route_observation(h->stream, h->p, h->route, d_scen, d_slot, n, n_ahead, spacing, static_cast<double *>(d[0]),
                                               static_cast<int32_t *>(d[1]));
                        return hipGetLastError();

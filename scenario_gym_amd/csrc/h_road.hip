@@ -1,5 +1,5 @@
 // h_road.hip -- road networks: the cell index built on the host, the lane centre lines, and which road geometries contain each
-// entity / point.
+// entity / point (delivered through deliver() and scratch(), sgym_host.hpp).
 #include "sgym_host.hpp"
 
 using namespace sgh;
@@ -361,25 +361,15 @@ extern "C" int sg_set_lanes(sg_handle *h, const sg_lanes *in)
 }
 
 // ---- which road geometries contain each entity / each point (sgym_geom.hpp) ------------------------------------------
-// Device scratch of its own: the observation scratch holds what sg_raster_map_device / sg_tick handed out, which stays valid.
-static int road_info_scratch(sg_handle *h, size_t bytes, unsigned char **out)
-{
-    if (bytes > h->road_info.cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (const int rc = h->road_info.ensure(h, bytes)) return rc;
-    }
-    *out = h->road_info.as<unsigned char>();
-    return SG_OK;
-}
-
-// n queries on the handle's stream (behind whatever rollout work is pending there) with HOST outputs, through the scratch as
+// n queries on the handle's stream (behind whatever rollout work is pending there) with HOST outputs, through a scratch of their own
+// (h->road_info; scratch(), sgym_host.hpp) as
 // [count][layers][geoms]; scen / xy: the n points on the host, which go into the scratch behind the outputs' room -- [n][2]
 // doubles, then [n] scenarios -- in front of the kernel (nullptr: the entity slots)
 static int road_info_host(sg_handle *h, const char *who, int64_t n, const int32_t *scen, const double *xy, int32_t cap, int32_t *count,
                           int32_t *geoms, uint32_t *layers)
 {
     const size_t nb = (size_t)n * 4;
-    return deliver(h, who, false, road_info_scratch, {{count, nb}, {layers, nb}, {geoms, nb * cap}}, xy ? nb * 5 : 0, [&](void *const *d) {
+    return deliver(h, who, false, h->road_info, {{count, nb}, {layers, nb}, {geoms, nb * cap}}, xy ? nb * 5 : 0, [&](void *const *d) {
         double *const d_xy = static_cast<double *>(d[3]);
         int32_t *const d_scen = xy ? reinterpret_cast<int32_t *>(d_xy + 2 * n) : nullptr;
         if (xy) {

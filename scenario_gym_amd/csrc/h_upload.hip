@@ -146,8 +146,8 @@ static void forget_batch(sg_handle *h)
     h->has_road = false;
     h->road = sg::RoadIndex{};
     h->geom = sg::RoadGeom{};
-    h->n_obs = 0; // the observers are slots of a batch
-    h->n_drv = 0; // ... and so are the drivers
+    h->observers.n = 0; // the observers are slots of a batch
+    h->drivers.n = 0; // ... and so are the drivers
     forget_driver_policy(h); // ... whose list the policy indexes
     forget_routes(h);        // the routes belong to entities of a batch
     h->uploaded = false; // (the controller table buffers stay: launch_rollout regrows them when the new batch needs more)

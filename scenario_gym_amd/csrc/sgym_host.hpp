@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <functional>
-#include <initializer_list>
 #include <atomic>
 #include <cassert>
 #include <cmath>
@@ -52,6 +51,19 @@ struct GrowBuf {
     int ensure(sg_handle *h, size_t bytes, bool *grew = nullptr); // room for `bytes`; *grew: the buffer is a new one
     void release();
     template <typename T> T *as() const { return static_cast<T *>(ptr); }
+};
+
+// A list of (scenario, slot) pairs on the device (sg_set_observers, sg_set_drivers): [2][capacity] int32_t, the scenarios in the
+// first half of the buffer, the slots in the second (grown on demand).  n: the pairs set (0: none); sg_upload forgets them.
+struct EntityList {
+    GrowBuf buf{GrowBuf::DEVICE};
+    int64_t n = 0;
+    int32_t *scenarios() const { return buf.as<int32_t>(); }
+    int32_t *slots() const { return buf.as<int32_t>() + buf.cap / (2 * sizeof(int32_t)); }
+    // replaces the list by n > 0 checked pairs (check_pairs): waits for the stream (something queued may still read the previous
+    // list); from there on the old list is gone: a failure of the runtime leaves an empty one (h_observe.hip)
+    int upload(sg_handle *h, int64_t n_new, const int32_t *scenario, const int32_t *slot);
+    void release() { buf.release(); }
 };
 
 } // namespace sgh
@@ -194,8 +206,7 @@ struct sg_handle {
                                                        // sg_set_road_networks forget them (forget_lanes)
 
     // ---- h_observe.hip: the observers ----
-    sgh::GrowBuf observers{sgh::GrowBuf::DEVICE};      // sg_set_observers: [2][capacity] int32_t, scenario and slot of every observer (grown on demand)
-    int64_t n_obs = 0;                                 // observers set (0: none); sg_upload forgets them
+    sgh::EntityList observers;                         // sg_set_observers
     sgh::GrowBuf routes{sgh::GrowBuf::DEVICE};         // sg_set_routes: the route totals, the segment rows, the segment ranges and the
                                                        // entity -> route map, one behind the other (grown on demand)
     sg::RouteIndex route{};                            // ... its pointers into that buffer (route_of == nullptr: no routes); sg_upload
@@ -203,16 +214,15 @@ struct sg_handle {
 
     // ---- h_drive.hip: the drivers ----
     std::vector<uint8_t> slot_external;                // [R * E] the slot is SG_KIND_AGENT_EXTERNAL in the uploaded batch (what sg_set_drivers asks for)
-    sgh::GrowBuf drivers{sgh::GrowBuf::DEVICE};        // sg_set_drivers: [2][capacity] int32_t, scenario and slot of every driver (grown on demand)
-    int64_t n_drv = 0;                                 // drivers set (0: none); sg_upload forgets them
-    sgh::GrowBuf drv_actions{sgh::GrowBuf::DEVICE};    // host actions of sg_step_drivers ([n_steps][n_drv][2] doubles): not `actions`, whose
+    sgh::EntityList drivers;                           // sg_set_drivers
+    sgh::GrowBuf drv_actions{sgh::GrowBuf::DEVICE};    // host actions of drivers_step ([n_steps][drivers.n][2] doubles): not `actions`, whose
                                                        // address the captured tick graph holds
     sgh::GrowBuf policy{sgh::GrowBuf::DEVICE};         // sg_set_driver_policy: the parameter rows, the path totals, the segment rows, the policy
                                                        // list and the segment ranges, one behind the other (grown on demand)
     sg::PolicyIndex pol{};                             // ... its pointers into that buffer (driver == nullptr: no policy)
     int64_t n_pol = 0;                                 // policy drivers set (0: none); sg_set_drivers and sg_upload forget them
-    sgh::GrowBuf pol_actions{sgh::GrowBuf::DEVICE};    // sg_step_drivers_policy: the caller's actions with the policy's rows merged in
-                                                       // ([n_steps][n_drv][2] doubles; a caller's device buffer is never written)
+    sgh::GrowBuf pol_actions{sgh::GrowBuf::DEVICE};    // drivers_step with the policy: the caller's actions with the policy's rows merged in
+                                                       // ([n_steps][drivers.n][2] doubles; a caller's device buffer is never written)
     sgh::GrowBuf pol_out{sgh::GrowBuf::DEVICE_POISONED}; // device scratch of sg_driver_policy_actions with host outputs
 
     // ---- h_episode.hip: the multi-agent tick (sg_tick_drivers) ----
@@ -384,10 +394,6 @@ inline void forget_driver_policy(sg_handle *h)
 // the routes of sg_set_routes belong to entities of a batch (sg_upload); the buffer stays for the next ones
 inline void forget_routes(sg_handle *h) { h->route = sg::RouteIndex{}; }
 
-// the driver list on the device: the scenarios in the first half of the buffer, the slots in the second
-inline int32_t *driver_scenarios(const sg_handle *h) { return h->drivers.as<int32_t>(); }
-inline int32_t *driver_slots(const sg_handle *h) { return h->drivers.as<int32_t>() + h->drivers.cap / (2 * sizeof(int32_t)); }
-
 // the episode accounting of sg_tick_drivers starts anew with the next tick (sg_reset, sg_upload, sg_set_drivers, sg_set_routes)
 inline void forget_episodes(sg_handle *h) { h->ep_live = false; }
 
@@ -415,6 +421,19 @@ inline double append_segments(std::vector<sg::LaneSeg> &segs, const double *pts,
     }
     return any ? segs.back().cum + segs.back().len : 0.0;
 }
+
+// The path table of sg_set_driver_policy and sg_set_routes on the host, and its upload (h_observe.hip).  The caller fills dbl and
+// ints with its own leading entries; build() puts the total of every path behind the doubles, seg_off [m + 1] behind the ints and the
+// rows of append_segments into segs, path by path.
+struct PathTable {
+    std::vector<double> dbl;
+    std::vector<sg::LaneSeg> segs;
+    std::vector<int32_t> ints;
+    void build(int64_t m, const int64_t *pt_off, const double *pts); // (pt_off monotone from 0: the caller has checked it)
+    // [doubles][LaneSeg rows][ints] into buf, behind a wait for the stream (something queued may still read the previous table; the
+    // caller has forgotten its pointers: a failure of the runtime leaves the handle without a table); the three parts' addresses
+    int upload(sg_handle *h, GrowBuf &buf, const double **d_dbl, const sg::LaneSeg **d_seg, const int32_t **d_ints) const;
+};
 
 // one group holding every block: an ordinary launch of a table variant
 inline sg::TabGroups one_group(const sg_handle *h, const double *tab, int n_steps)
@@ -471,11 +490,17 @@ void note_slice(sg_handle *h, bool tab);
 // State.reset of the scenarios with d_mask[r] != 0 (DEVICE [R]), enqueued, not waited for: what sg_reset_scenarios does between its
 // copy and its wait.  clear_episodes: their episode accounting starts anew too (sg_tick_drivers' own reset has done that already)
 int reset_scenarios_queued(sg_handle *h, const uint8_t *d_mask, bool clear_episodes);
+// ---- h_observe.hip ----
+// What a list of n (scenario, slot) pairs requires of every pair beyond being in range (check_pairs): the slot holds an entity, it is an
+// SG_KIND_AGENT_EXTERNAL slot, no pair is listed twice.
+enum PairRules : unsigned { PAIR_HOLDS_ENTITY = 1u, PAIR_EXTERNAL = 2u, PAIR_ONCE = 4u };
+int check_pairs(sg_handle *h, const char *who, int64_t n, const int32_t *scenario, const int32_t *slot, unsigned rules);
 // ---- h_drive.hip ----
-// one step of the batch with the drivers' controllers ahead of it, the policy ahead of them when one is set: sg_step_drivers /
-// sg_step_drivers_policy for n_steps = 1 (actions [n_drv][2] HOST, DEVICE or null) without their wait -- HOST actions are on the
-// device when it returns, and that alone is waited for
-int drivers_step_queued(sg_handle *h, const char *who, const double *actions, int32_t actions_device);
+// n_steps steps of the batch, each with the drivers' controllers ahead of it and -- policy -- the policy ahead of them, enqueued, not
+// waited for: what sg_step_drivers, sg_step_drivers_policy and sg_tick_drivers do between their checks and their end.  actions
+// [n_steps][drivers.n][2]: HOST (copied; wait_host_copy: on the device when this returns, and that alone is waited for), DEVICE (read
+// in place without the policy, never written) or null ((0, 0) for every driver)
+int drivers_step(sg_handle *h, int n_steps, const double *actions, int32_t actions_device, bool policy, bool wait_host_copy);
 // ---- h_episode.hip ----
 int episode_clear_masked(sg_handle *h, const uint8_t *d_mask); // (enqueued; nothing when no episode is in progress)
 // ---- h_queue.hip ----
@@ -507,42 +532,68 @@ struct OutPart {
     size_t bytes;
 };
 
+// Device scratch of the calls that deliver to the host, grown on demand behind a wait for the stream (something queued may still
+// write the old one): a tick of an RL loop asks once per step, a hipMalloc / hipFree pair per call would cost more than the kernels.
+// The observation scratch (h->obs) is the one whose address sg_tick's captured graph holds: its growth bumps the generation.  The
+// others (h->pol_out, h->road_info) are apart from it because it holds what sg_raster_map_device / sg_tick handed out, which stays valid.
+inline int scratch(sg_handle *h, GrowBuf &buf, size_t bytes, unsigned char **out)
+{
+    if (bytes > buf.cap) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (const int rc = buf.ensure(h, bytes)) return rc;
+        if (&buf == &h->obs) ++h->generation;
+    }
+    *out = buf.as<unsigned char>();
+    return SG_OK;
+}
+
 // Runs `launch(d)` -- hipError_t(void *const d[4]), the launches on the handle's stream -- with d[i] where part i is to be
-// written, and delivers the (at most three) parts.  outputs_device: d[i] is the caller's pointer; stream-ordered, not waited for, what is
-// known of the queue so far.  Else the parts lie one behind the other, in their order, from the start of the scratch that
-// `scratch(h, bytes, &base)` hands out (a part that was not asked for keeps its room and gets d[i] = null), with `tail` more bytes
+// written, and delivers the parts (unused ones at the end: {}).  outputs_device: d[i] is the caller's pointer; stream-ordered, not waited for, what is
+// known of the queue so far.  Else the parts lie one behind the other, in their order, from the start of the scratch `buf`
+// (a part that was not asked for keeps its room and gets d[i] = null), with `tail` more bytes
 // for the launch's own use behind them at the next multiple of 16, d[3]; one copy per part asked for, the wait for the stream,
 // check_queue.  A failure of the HIP runtime reads "<who>: <step> failed: <error string>".
 template <typename Launch>
-int deliver(sg_handle *h, const char *who, bool outputs_device, int (*scratch)(sg_handle *, size_t, unsigned char **),
-            std::initializer_list<OutPart> parts, size_t tail, Launch launch)
+int deliver(sg_handle *h, const char *who, bool outputs_device, GrowBuf &buf, const OutPart (&parts)[3], size_t tail, Launch launch)
 {
-    assert(parts.size() <= 3 && (tail == 0 || !outputs_device));
+    assert(tail == 0 || !outputs_device);
     const auto hip = [&](hipError_t e, const char *step) {
         return e == hipSuccess ? SG_OK : fail(h, SG_ERR_HIP, "%s: %s failed: %s", who, step, hipGetErrorString(e));
     };
-    void *d[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t n = 0, bytes = 0;
-    for (const OutPart &p : parts) { d[n++] = p.out; bytes += p.bytes; }
+    void *d[4] = {parts[0].out, parts[1].out, parts[2].out, nullptr};
     if (outputs_device) {
         if (const int rc = hip(launch(d), "the launch")) return rc;
         return queue_gave_up(h); // (not waited for: what is known so far)
     }
-    const size_t tail_off = (bytes + 15) & ~(size_t)15;
+    const size_t bytes = parts[0].bytes + parts[1].bytes + parts[2].bytes, tail_off = (bytes + 15) & ~(size_t)15;
     unsigned char *base = nullptr;
-    if (const int rc = scratch(h, tail ? tail_off + tail : bytes, &base)) return rc;
+    if (const int rc = scratch(h, buf, tail ? tail_off + tail : bytes, &base)) return rc;
     if (tail) d[3] = base + tail_off;
-    n = 0;
-    for (const OutPart &p : parts) { if (p.out) d[n] = base; ++n; base += p.bytes; }
+    for (int i = 0; i < 3; ++i) { if (parts[i].out) d[i] = base; base += parts[i].bytes; }
     if (const int rc = hip(launch(d), "the launch")) return rc;
-    n = 0;
-    for (const OutPart &p : parts) {
-        if (p.out && p.bytes)
-            if (const int rc = hip(hipMemcpyAsync(p.out, d[n], p.bytes, hipMemcpyDeviceToHost, h->stream), "hipMemcpyAsync")) return rc;
-        ++n;
-    }
+    for (int i = 0; i < 3; ++i)
+        if (parts[i].out && parts[i].bytes)
+            if (const int rc = hip(hipMemcpyAsync(parts[i].out, d[i], parts[i].bytes, hipMemcpyDeviceToHost, h->stream), "hipMemcpyAsync")) return rc;
     if (const int rc = hip(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) return rc;
     return check_queue(h); // (a persistent launch that gave up: sticky)
+}
+
+// What every observation of the egos or of the observers does behind its own argument checks: refuses a handle without a batch; n =
+// the observers of sg_set_observers, or the ego of every scenario; n == 0: nothing is written; refuses a null primary output (part
+// `primary` of `per`, named `primary_name`); then deliver() through the observation scratch with per[i].bytes PER OBSERVER, and
+// launch(d, d_scen, d_slot, n) -- d_scen, d_slot: the observer list, null for the egos.
+template <typename Launch>
+int observe(sg_handle *h, const char *who, bool observers, bool outputs_device, int primary, const char *primary_name, const OutPart (&per)[3],
+            Launch launch)
+{
+    if (!h->uploaded) return fail(h, SG_ERR_STATE, "%s: no scenarios uploaded", who);
+    const int64_t n = observers ? h->observers.n : (int64_t)h->R;
+    if (n == 0) return queue_gave_up(h); // no observers: nothing is written
+    if (!per[primary].out) return fail(h, SG_ERR_INVALID, "%s: null %s", who, primary_name);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const int32_t *d_scen = observers ? h->observers.scenarios() : nullptr, *d_slot = observers ? h->observers.slots() : nullptr;
+    const OutPart all[3] = {{per[0].out, (size_t)n * per[0].bytes}, {per[1].out, (size_t)n * per[1].bytes}, {per[2].out, (size_t)n * per[2].bytes}};
+    return deliver(h, who, outputs_device, h->obs, all, 0, [&](void *const *d) { return launch(d, d_scen, d_slot, n); });
 }
 
 } // namespace sgh

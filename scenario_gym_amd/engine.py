@@ -228,20 +228,48 @@ class RolloutEngine:
         arrs = tuple(np.empty(shape, dt) for shape, dt in specs)
         return arrs, tuple(a.ctypes.data if a.size else None for a in arrs)
 
-    def _actions(self, actions, n):
-        """The actions of n ticks ([n, R, 2]: numpy, a float64 torch tensor on the device, or None) for sg_step / sg_tick:
-        (the array the pointer points into, pointer, on_device)."""
+    def _actions(self, actions, n, rows=None, wait=True):
+        """The actions of n ticks ([n, rows, 2], rows = R unless given: numpy, a float64 torch tensor on the device, or None) for
+        the stepping calls: (the array the pointer points into, pointer, on_device).  wait=False: a tensor's writes are not waited
+        for (the caller orders the streams)."""
+        rows = self.R if rows is None else rows
         if actions is None:
             return None, None, 0
         if hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
             # a torch tensor on this GPU (fp64, contiguous): its device pointer goes down as it is
             import torch
 
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * self.R * 2
-            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
+            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * rows * 2
+            if wait:
+                torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
             return actions, actions.data_ptr(), 1
-        actions = np.ascontiguousarray(actions, np.float64).reshape(n, self.R, 2)
+        actions = np.ascontiguousarray(actions, np.float64).reshape(n, rows, 2)
         return actions, actions.ctypes.data, 0
+
+    def _observe(self, call, args, torch_out, *specs):
+        """The shared tail of the observation wrappers: the outputs of _outputs(torch_out, *specs), call(h, *args, their
+        addresses, torch_out), and with torch_out the wait for the kernel (sg_synchronize: the C call itself does not wait)."""
+        outs, ptrs = self._outputs(torch_out, *specs)
+        self._check(call(self.h, *args, *ptrs, int(bool(torch_out))), call.__name__)
+        if torch_out:
+            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
+        return outs
+
+    def _entity_list(self, scenario, slot, who):
+        """The (scenario, slot) pairs of a list call: ((the int32 arrays), n, their addresses -- None for an empty list)."""
+        scen = np.ascontiguousarray(scenario, np.int32).ravel()
+        slot = np.ascontiguousarray(slot, np.int32).ravel()
+        if scen.shape != slot.shape:
+            raise ValueError(f"{who}: scenario and slot must have the same length")
+        n = len(scen)
+        return (scen, slot), n, scen.ctypes.data if n else None, slot.ctypes.data if n else None
+
+    def _path_table(self, paths):
+        """The polylines of a path call: ((the arrays), the address of pt_off [len(paths) + 1] int64, of pts [pt_off[-1], 2] or None)."""
+        paths = [np.ascontiguousarray(q, np.float64).reshape(-1, 2) for q in paths]
+        pt_off = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int64)
+        pts = np.ascontiguousarray(np.concatenate(paths, axis=0)) if pt_off[-1] else np.zeros((0, 2))
+        return (pt_off, pts), pt_off.ctypes.data, pts.ctypes.data if len(pts) else None
 
     def _device_view(self, ptr, shape, typestr):
         """Zero-copy torch tensor over device memory of the handle."""
@@ -308,30 +336,16 @@ class RolloutEngine:
         scenario[k], a KIND_AGENT_EXTERNAL slot whose VehicleController (its ctrl row) the device runs itself.  Any number per
         scenario, no pair twice; the order is the order of the actions.  An empty list clears it; upload() forgets it; a
         refused list leaves the previous one in place."""
-        scen = np.ascontiguousarray(scenario, np.int32).ravel()
-        slot = np.ascontiguousarray(slot, np.int32).ravel()
-        if scen.shape != slot.shape:
-            raise ValueError("set_drivers: scenario and slot must have the same length")
-        self._check(self.lib.sg_set_drivers(self.h, len(scen), scen.ctypes.data if len(scen) else None,
-                                            slot.ctypes.data if len(scen) else None), "sg_set_drivers")
-        self._n_drv = len(scen)
+        _keep, n, p_scen, p_slot = self._entity_list(scenario, slot, "set_drivers")
+        self._check(self.lib.sg_set_drivers(self.h, n, p_scen, p_slot), "sg_set_drivers")
+        self._n_drv = n
         self._n_pol = 0  # (sg_set_drivers forgets the policy)
 
     def step_drivers(self, actions=None, n=1):
         """n x ScenarioGym.step() with the drivers' controllers run on the device (sg_step_drivers): actions [n, n_drivers, 2]
         (accel, steer) in the order of set_drivers -- numpy, a float64 torch tensor on the device, or None for (0, 0)."""
-        n, nd = int(n), getattr(self, "_n_drv", 0)
-        ptr, on_device = None, 0
-        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
-            import torch
-
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * nd * 2
-            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
-            ptr, on_device = actions.data_ptr(), 1
-        elif actions is not None:
-            actions = np.ascontiguousarray(actions, np.float64).reshape(n, nd, 2)
-            ptr = actions.ctypes.data
-        self._check(self.lib.sg_step_drivers(self.h, n, ptr, on_device), "sg_step_drivers")
+        _keep, ptr, on_device = self._actions(actions, int(n), getattr(self, "_n_drv", 0))
+        self._check(self.lib.sg_step_drivers(self.h, int(n), ptr, on_device), "sg_step_drivers")
 
     def set_driver_policy(self, driver, params, paths):
         """sg_set_driver_policy: the built-in policy (IDM car-following along a path) runs driver[j] of the set_drivers list with
@@ -345,12 +359,10 @@ class RolloutEngine:
             self._n_pol = 0
             return
         params = np.ascontiguousarray(params, np.float64).reshape(m, L.DP_NPARAM)
-        paths = [np.ascontiguousarray(q, np.float64).reshape(-1, 2) for q in paths]
         if len(paths) != m:
             raise ValueError("set_driver_policy: one path per policy driver")
-        pt_off = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int64)
-        pts = np.ascontiguousarray(np.concatenate(paths, axis=0)) if pt_off[-1] else np.zeros((0, 2))
-        pol = L.SgDriverPolicy(m, driver.ctypes.data, params.ctypes.data, pt_off.ctypes.data, pts.ctypes.data if len(pts) else None)
+        _keep, p_off, p_pts = self._path_table(paths)
+        pol = L.SgDriverPolicy(m, driver.ctypes.data, params.ctypes.data, p_off, p_pts)
         self._check(self.lib.sg_set_driver_policy(self.h, C.byref(pol)), "sg_set_driver_policy")
         self._n_pol = m
 
@@ -360,28 +372,14 @@ class RolloutEngine:
         sine of the heading error, arclength along the path, remaining path).  Empty arrays when no policy is set.  torch_out:
         torch tensors in HBM the kernel writes directly (waited for, as in entity_status)."""
         m = getattr(self, "_n_pol", 0)
-        outs, ptrs = self._outputs(torch_out, ((m, 2), "float64"), ((m, L.DP_NINFO), "int32"), ((m, L.DP_NFEAT), "float64"))
-        self._check(self.lib.sg_driver_policy_actions(self.h, *ptrs, int(bool(torch_out))), "sg_driver_policy_actions")
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(self.lib.sg_driver_policy_actions, (), torch_out, ((m, 2), "float64"), ((m, L.DP_NINFO), "int32"), ((m, L.DP_NFEAT), "float64"))
 
     def step_drivers_policy(self, actions=None, n=1):
         """step_drivers with the built-in policy in the loop (sg_step_drivers_policy): actions [n, n_drivers, 2] as for
         step_drivers; ahead of every step the rows of the policy drivers are replaced, in a buffer of the handle, by the policy
         evaluated on the state before that step.  The caller's array is never written."""
-        n, nd = int(n), getattr(self, "_n_drv", 0)
-        ptr, on_device = None, 0
-        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
-            import torch
-
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == n * nd * 2
-            torch.cuda.current_stream(actions.device).synchronize()  # the policy's writes before the handle's stream reads
-            ptr, on_device = actions.data_ptr(), 1
-        elif actions is not None:
-            actions = np.ascontiguousarray(actions, np.float64).reshape(n, nd, 2)
-            ptr = actions.ctypes.data
-        self._check(self.lib.sg_step_drivers_policy(self.h, n, ptr, on_device), "sg_step_drivers_policy")
+        _keep, ptr, on_device = self._actions(actions, int(n), getattr(self, "_n_drv", 0))
+        self._check(self.lib.sg_step_drivers_policy(self.h, int(n), ptr, on_device), "sg_step_drivers_policy")
 
     def future_collision(self, horizon=5.0, n_samples=10):
         """FutureCollisionDetector (sensor/common.py:59-106) for the ego of every scenario at the current time: bool [R]."""
@@ -450,16 +448,8 @@ class RolloutEngine:
         in stream order: torch's current stream is ordered behind the tick, nothing waits on the host (ordered=False: the caller
         orders the two streams itself, ordered_with_torch).  The views are valid until the next tick_drivers, set_drivers or
         upload, and the same tensors come back while the addresses stay."""
-        import torch
-
         nd = getattr(self, "_n_drv", 0)
-        ptr, on_device = None, 0
-        if actions is not None and hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
-            assert actions.dtype == torch.float64 and actions.is_contiguous() and actions.numel() == nd * 2
-            ptr, on_device = actions.data_ptr(), 1
-        elif actions is not None:
-            actions = np.ascontiguousarray(actions, np.float64).reshape(nd, 2)
-            ptr = actions.ctypes.data
+        _keep, ptr, on_device = self._actions(actions, 1, nd, wait=False)  # (a tensor is read in stream order: ordered_with_torch)
         rules = L.SgEpisodeRules(self.cfg.terminal_mask if terminal_mask is None else int(terminal_mask), int(bad_env_flags), int(bad_driver_flags),
                                  int(bool(auto_reset)), float(r_step), float(r_bad), float(w_progress))
         view = self.__dict__.setdefault("_ep_view", L.SgEpisodeView())
@@ -560,14 +550,10 @@ class RolloutEngine:
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
-        scen = np.ascontiguousarray(scenario, np.int32).ravel()
-        slot = np.ascontiguousarray(slot, np.int32).ravel()
-        if scen.shape != slot.shape:
-            raise ValueError("set_observers: scenario and slot must have the same length")
+        _keep, n, p_scen, p_slot = self._entity_list(scenario, slot, "set_observers")
         self._n_obs = 0
-        self._check(self.lib.sg_set_observers(self.h, len(scen), scen.ctypes.data if len(scen) else None,
-                                              slot.ctypes.data if len(scen) else None), "sg_set_observers")
-        self._n_obs = len(scen)
+        self._check(self.lib.sg_set_observers(self.h, n, p_scen, p_slot), "sg_set_observers")
+        self._n_obs = n
 
     def raster_map_observers(self, layers, width=20.0, height=20.0, nw=20, nh=20, torch_out=False):
         """RasterizedMapSensor._step (sensor/map.py:136-271) in the frame of every observer of set_observers
@@ -575,13 +561,9 @@ class RolloutEngine:
         gets zeros.  torch_out: a torch uint8 tensor in HBM the kernel writes directly; this wrapper waits for the kernel
         (sg_synchronize) before it returns, so the tensor can be used on any torch stream -- the C call itself does not wait."""
         lay = np.ascontiguousarray(layers, np.int32)
-        (out,), (ptr,) = self._outputs(torch_out, ((self._n_obs, len(lay), int(nh), int(nw)), "uint8"))
-        self._check(self.lib.sg_raster_map_observers(self.h, float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data,
-                                                     ptr, int(bool(torch_out))), "sg_raster_map_observers")
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-            return out
-        return out.astype(bool)
+        (out,) = self._observe(self.lib.sg_raster_map_observers, (float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data), torch_out,
+                               ((self._n_obs, len(lay), int(nh), int(nw)), "uint8"))
+        return out if torch_out else out.astype(bool)
 
     def raster_map_observers_queued(self, out, layers, width=20.0, height=20.0, nw=20, nh=20, ordered=True):
         """raster_map_observers into `out`, a contiguous torch uint8 tensor [n, n_layers, nh, nw] on this GPU, without any host
@@ -600,21 +582,12 @@ class RolloutEngine:
         """FutureCollisionDetector._step (sensor/common.py:87-106) for every observer of set_observers at the current time of
         its scenario (sg_future_collision_observers): bool [n], or with torch_out a torch uint8 tensor in HBM (waited for, as
         in raster_map_observers)."""
-        (out,), (ptr,) = self._outputs(torch_out, ((self._n_obs,), "uint8"))
-        self._check(self.lib.sg_future_collision_observers(self.h, float(horizon), int(n_samples), ptr, int(bool(torch_out))),
-                    "sg_future_collision_observers")
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-            return out
-        return out.astype(bool)
+        (out,) = self._observe(self.lib.sg_future_collision_observers, (float(horizon), int(n_samples)), torch_out, ((self._n_obs,), "uint8"))
+        return out if torch_out else out.astype(bool)
 
     def _nearest(self, call, n, k, radius, torch_out):
         k = int(k)
-        outs, ptrs = self._outputs(torch_out, ((n, k, 8), "float64"), ((n, k), "int32"), ((n,), "int32"))
-        self._check(call(self.h, k, float(radius), *ptrs, int(bool(torch_out))), call.__name__)
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(call, (k, float(radius)), torch_out, ((n, k, 8), "float64"), ((n, k), "int32"), ((n,), "int32"))
 
     def nearest_entities(self, k, radius=float("inf"), torch_out=False):
         """The vector observation of the ego of every scenario (sg_nearest_entities): the k <= 32 nearest other entities that are
@@ -654,11 +627,8 @@ class RolloutEngine:
 
     def _lane_observation(self, call, n, k, n_ahead, spacing, radius, torch_out):
         k, n_ahead = int(k), int(n_ahead)
-        outs, ptrs = self._outputs(torch_out, ((n, k, 6 + 2 * max(n_ahead, 0)), "float64"), ((n, k), "int32"), ((n,), "int32"))
-        self._check(call(self.h, k, n_ahead, float(spacing), float(radius), *ptrs, int(bool(torch_out))), call.__name__)
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(call, (k, n_ahead, float(spacing), float(radius)), torch_out,
+                             ((n, k, 6 + 2 * max(n_ahead, 0)), "float64"), ((n, k), "int32"), ((n,), "int32"))
 
     def lane_observation(self, k=3, n_ahead=4, spacing=2.0, radius=float("inf"), torch_out=False):
         """The lane-frame vector observation of the ego of every scenario (sg_lane_observation): the k <= 8 lanes of the
@@ -680,11 +650,8 @@ class RolloutEngine:
     def _range_scan(self, call, n, n_rays, angle0, dangle, max_range, torch_out):
         n_rays = int(n_rays)
         dangle = 2.0 * np.pi / max(n_rays, 1) if dangle is None else float(dangle)  # (n_rays < 1 is the library's to refuse)
-        outs, ptrs = self._outputs(torch_out, ((n, max(n_rays, 0), 2), "float64"), ((n, max(n_rays, 0)), "int32"), ((n,), "int32"))
-        self._check(call(self.h, n_rays, float(angle0), dangle, float(max_range), *ptrs, int(bool(torch_out))), call.__name__)
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(call, (n_rays, float(angle0), dangle, float(max_range)), torch_out,
+                             ((n, max(n_rays, 0), 2), "float64"), ((n, max(n_rays, 0)), "int32"), ((n,), "int32"))
 
     def range_scan(self, n_rays=64, angle0=-np.pi, dangle=None, max_range=100.0, torch_out=False):
         """The range scan of the ego of every scenario (sg_range_scan): n_rays <= 1024 beams from the ego's pose point, beam b at
@@ -703,11 +670,7 @@ class RolloutEngine:
         return self._range_scan(self.lib.sg_range_scan_observers, self._n_obs, n_rays, angle0, dangle, max_range, torch_out)
 
     def _entity_status(self, call, n, torch_out):
-        outs, ptrs = self._outputs(torch_out, ((n,), "int32" if torch_out else "uint32"), ((n, L.ST_NINFO), "int32"), ((n, L.ST_NFEAT), "float64"))
-        self._check(call(self.h, *ptrs, int(bool(torch_out))), call.__name__)
-        if torch_out:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(call, (), torch_out, ((n,), "int32" if torch_out else "uint32"), ((n, L.ST_NINFO), "int32"), ((n, L.ST_NFEAT), "float64"))
 
     def entity_status(self, torch_out=False):
         """The episode status of the ego of every scenario (sg_entity_status): what a per-agent reward and termination need in
@@ -733,18 +696,11 @@ class RolloutEngine:
         entity, each at most once) and is the polyline paths[j] ([n_pts, 2], in driving order, used as given; fewer than two
         points: no segments).  Needed by the route part of route_observation; an empty list clears the routes, upload() forgets
         them, and a refused call leaves the previous ones in place."""
-        scen = np.ascontiguousarray(scenario, np.int32).ravel()
-        slot = np.ascontiguousarray(slot, np.int32).ravel()
-        paths = [np.ascontiguousarray(q, np.float64).reshape(-1, 2) for q in paths]
-        if not (len(scen) == len(slot) == len(paths)):
+        if not (np.size(scenario) == np.size(slot) == len(paths)):
             raise ValueError("set_routes: one scenario, one slot and one path per route")
-        if len(scen) == 0:
-            self._check(self.lib.sg_set_routes(self.h, 0, None, None, None, None), "sg_set_routes")
-            return
-        pt_off = np.concatenate([[0], np.cumsum([len(q) for q in paths])]).astype(np.int64)
-        pts = np.ascontiguousarray(np.concatenate(paths, axis=0)) if pt_off[-1] else np.zeros((0, 2))
-        self._check(self.lib.sg_set_routes(self.h, len(scen), scen.ctypes.data, slot.ctypes.data, pt_off.ctypes.data,
-                                           pts.ctypes.data if len(pts) else None), "sg_set_routes")
+        _keep, n, p_scen, p_slot = self._entity_list(scenario, slot, "set_routes")
+        _keep_paths, p_off, p_pts = self._path_table(paths) if n else (None, None, None)
+        self._check(self.lib.sg_set_routes(self.h, n, p_scen, p_slot, p_off, p_pts), "sg_set_routes")
 
     def route_observation(self, n_ahead=4, spacing=2.0, observers=False, device=False):
         """The route and recorded-track observation (sg_route_observation; observers: sg_route_observation_observers, for every
@@ -760,11 +716,7 @@ class RolloutEngine:
         n_ahead = int(n_ahead)
         n = self._n_obs if observers else self.R
         call = self.lib.sg_route_observation_observers if observers else self.lib.sg_route_observation
-        outs, ptrs = self._outputs(device, ((n, L.RT_NFEAT + 2 * max(n_ahead, 0)), "float64"), ((n, L.RT_NINFO), "int32"))
-        self._check(call(self.h, n_ahead, float(spacing), *ptrs, int(bool(device))), call.__name__)
-        if device:
-            self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
-        return outs
+        return self._observe(call, (n_ahead, float(spacing)), device, ((n, L.RT_NFEAT + 2 * max(n_ahead, 0)), "float64"), ((n, L.RT_NINFO), "int32"))
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

@@ -199,15 +199,20 @@ class VectorScenarioEnv:
         obs, flags = self.engine.tick(actions, self._codes, self.width, self.height, self.n, self.n, torch_out=self.torch_obs)
         if self.torch_obs:
             flags = flags.cpu().numpy().astype(np.uint32)
-        done = (flags & self._mask) != 0
-        bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
-        reward = np.where(done & bad, -1.0, 0.01)  # RLAgent.reward, openaigym.py:300-310
+        done, reward = self._done_reward(flags)
         self.done = done
         if self.auto_reset and done.any():
             self.engine.reset_scenarios(done)
             self.done = np.zeros(self.n_envs, bool)
             obs = self._observe()  # the restarted environments return the first observation of their new episode
         return obs, reward, done, {"terminal_flags": flags}
+
+    def _done_reward(self, flags):
+        """(done [R], reward [R]) of the terminal flags of a tick: the engine's terminal conditions; RLAgent.reward
+        (openaigym.py:300-310), -1 for a done state that is off the road or in an ego collision and 0.01 otherwise."""
+        done = (flags & self._mask) != 0
+        bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
+        return done, np.where(done & bad, -1.0, 0.01)
 
     def _step_drivers(self, actions):
         """step() with a driver list: actions [n_drivers, 2] in list order (environment by environment, each in the order of
@@ -232,9 +237,7 @@ class VectorScenarioEnv:
         else:
             self.engine.step_drivers(actions, 1)
         flags = self.engine.terminal_flags()
-        done = (flags & self._mask) != 0
-        bad = (flags & (L.TERM_EGO_OFF_ROAD | L.TERM_EGO_COLLISION)) != 0
-        reward = np.where(done & bad, -1.0, 0.01)  # RLAgent.reward, openaigym.py:300-310
+        done, reward = self._done_reward(flags)
         info = {"terminal_flags": flags}
         if self.driver_status and self.n_drivers:  # the stepped state, before an auto-reset replaces it
             d_flags, d_info, d_feat = self._driver_status()

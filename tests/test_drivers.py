@@ -145,8 +145,45 @@ def test_twin_late_ego_spawns(sga):
     B.close()
 
 
+@gpu
+@pytest.mark.parametrize("policy", [False, True])
+def test_one_step_routine_behind_three_entry_points(sga, policy):
+    """Three twins of 2 scenarios x 4 entities with 2 drivers, 3 steps each: one call with host actions, one call with device actions,
+    three sg_tick_drivers (no auto-reset, no progress term) with the same rows -- byte-identical raw state.  policy: the built-in
+    policy runs the second driver, through sg_step_drivers_policy in the first two twins."""
+    import torch
+
+    E, n, steps = 4, 2, 3
+    scs = DS.batch(E, [[(0, "a")], [(2, "free")]], seed=21)
+    scen, slot = DS.driver_list(scs)
+    acts = np.ascontiguousarray(DS.actions(n, seed=3)[:steps])
+    d_acts = torch.as_tensor(acts, device="cuda:0").contiguous()
+    before = d_acts.clone()
+    twins = []
+    for how in ("host", "device", "ticks"):
+        eng = _engine(sga, E, n=2)
+        eng.upload(DS.pack(scs))
+        eng.set_drivers(scen, slot)
+        if policy:
+            sc = scs[1]
+            eng.set_driver_policy([1], np.array([sga.idm_params(v0=5.0)]), [sc["knots"][sc["knot_off"][2]:sc["knot_off"][3], 1:3]])
+        if how == "ticks":
+            for k in range(steps):
+                eng.tick_drivers(acts[k], auto_reset=False, w_progress=0.0)
+        else:
+            (eng.step_drivers_policy if policy else eng.step_drivers)(acts if how == "host" else d_acts, steps)
+        eng.synchronize()
+        twins.append(eng.state(raw=True))
+        eng.close()
+    assert torch.equal(d_acts, before)  # (the caller's device buffer is read, never written)
+    assert (twins[0]["n_steps"] == steps).all()
+    for how, st in zip(("device actions", "three ticks"), twins[1:]):
+        for key in twins[0]:
+            assert np.array_equal(_bits(twins[0][key]), _bits(st[key])), f"{how}: {key} differs"
+
+
 # ------------------------------------------------------------------------------------------ 2. several drivers, against the oracle
-CONFIGS = {"mixed65": (65, DS.mixed_config), "mixed520": (520, DS.mixed_config), "all65": (65, DS.all_config)}
+CONFIGS ={"mixed65": (65, DS.mixed_config), "mixed520": (520, DS.mixed_config), "all65": (65, DS.all_config)}
 _expected = {}
 
 
