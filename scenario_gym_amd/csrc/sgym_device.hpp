@@ -37,7 +37,9 @@
 #define SG_WAVES_PER_SIMD_TAB 2 // same for the variant without in-kernel controllers
 #endif
 
-// The device code lives in one part per subject; each part builds on the ones before it.
+// The device code lives in one part per subject; each part builds on the ones before it.  The parts that
+// sgym_launch.hpp adds behind this header (sgym_wide.hpp, sgym_queue.hpp, sgym_policy.hpp, sgym_episode.hpp) and sgym_drive.hpp
+// (k_drive.hip) build on all of these.
 #include "sgym_experiments.hpp" // instrumentation of experiment builds: empty in the product build
 #include "sgym_core.hpp"
 #include "sgym_agents.hpp"
@@ -50,4 +52,5 @@
 #include "sgym_rollout.hpp"
 #include "sgym_control.hpp"
 #include "sgym_sensors.hpp"
+#include "sgym_polyline.hpp"  // LaneSeg rows and their steps: sgym_observers.hpp and sgym_policy.hpp both call them
 #include "sgym_observers.hpp"

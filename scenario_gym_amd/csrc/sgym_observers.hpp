@@ -6,12 +6,16 @@
 
 namespace sg {
 
+// the first dynamic / static row of padded entity index idx = r * EP + slot: field f is at [f * 64]
+__device__ __forceinline__ const double *entity_dyn(const Params &p, uint32_t idx) { return p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64) + (idx & 63); }
+__device__ __forceinline__ const double *entity_stat(const Params &p, uint32_t idx) { return p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64) + (idx & 63); }
+__device__ __forceinline__ bool entity_present(const double *dyn) { return reinterpret_cast<const uint64_t *>(dyn)[SG_F_PRESENT * 64] != 0; }
+
 // ------------------------------------------------------------------------------------------------
 // The reference's sensors are per entity: RasterizedMapSensor(entity, ...) rasters the scene in that entity's frame
 // (sensor/map.py:120-271), FutureCollisionDetector(entity, horizon) looks ahead along that entity's trajectory
-// (sensor/common.py:60-106), SURVEY 8f N2.  One workgroup per observer k = blockIdx.x: (obs_scen[k], obs_slot[k]) of a list, or
-// -- without a list (obs_scen == nullptr) -- the ego of scenario k.  fp64 throughout, the operation sequences of the oracle
-// (np.linspace / numpy matmul arithmetic as probed there).
+// (sensor/common.py:60-106), SURVEY 8f N2.  One workgroup per observer k = blockIdx.x, listed or ego as in observer_of.
+// fp64 throughout, the operation sequences of the oracle (np.linspace / numpy matmul arithmetic as probed there).
 // ------------------------------------------------------------------------------------------------
 struct ObsLayers {
     int32_t code[8]; // layer codes of sg_raster_map: 0 the entity layer, else one SG_LAYER_* bit (by value: no device copy)
@@ -25,13 +29,12 @@ struct ObsFrame {
 
 __device__ __forceinline__ void obs_stage_frame(const Params &p, int r, int slot, ObsFrame &f)
 {
-    const uint32_t idx = (uint32_t)r * p.EP + (uint32_t)slot;
-    const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
+    const double *dy = entity_dyn(p, (uint32_t)r * p.EP + (uint32_t)slot);
     double s, c;
-    sg_sincos(fld(dy, SG_F_POSE + 3) + 3.14159265358979311600e+00 / 2, s, c); // pose[3] + math.pi / 2
-    f.x = fld(dy, SG_F_POSE + 0); f.y = fld(dy, SG_F_POSE + 1);
+    sg_sincos(dy[(SG_F_POSE + 3) * 64] + 3.14159265358979311600e+00 / 2, s, c); // pose[3] + math.pi / 2
+    f.x = dy[(SG_F_POSE + 0) * 64]; f.y = dy[(SG_F_POSE + 1) * 64];
     f.s = s; f.c = c;
-    f.present = fld<uint64_t>(dy, SG_F_PRESENT) != 0;
+    f.present = entity_present(dy);
 }
 
 __device__ __forceinline__ double sg_linspace_at(double start, double stop, int n, int j)
@@ -58,14 +61,13 @@ __device__ __forceinline__ void obs_stage_box(const Params &p, int r, int e, dou
                                               double (&cor)[8][512], int *near_n)
 {
     const uint32_t idx = (uint32_t)r * p.EP + (uint32_t)e;
-    const LanePtr st(p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64), (idx & 63) * 8u);
-    const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-    if (fld<uint64_t>(dy, SG_F_PRESENT) == 0) return;
+    const double *st = entity_stat(p, idx), *dy = entity_dyn(p, idx);
+    if (!entity_present(dy)) return;
     double C[8];
-    const double x = fld(dy, SG_F_POSE + 0), y = fld(dy, SG_F_POSE + 1), h = fld(dy, SG_F_POSE + 3);
+    const double x = dy[(SG_F_POSE + 0) * 64], y = dy[(SG_F_POSE + 1) * 64], h = dy[(SG_F_POSE + 3) * 64];
     double sh, ch;
     sg_sincos(h, sh, ch);
-    sg_corners(x, y, sh, ch, fld(st, ST_BW), fld(st, ST_BL), fld(st, ST_BCX), fld(st, ST_BCY), C);
+    sg_corners(x, y, sh, ch, st[ST_BW * 64], st[ST_BL * 64], st[ST_BCX * 64], st[ST_BCY * 64], C);
     const double reach = 0.5 * (__builtin_fabs(width) + __builtin_fabs(height)) * 1.0000001 + 1e-6;
     double far = 0.0;
 #pragma unroll
@@ -121,13 +123,12 @@ static __global__ __launch_bounds__(512) void map_raster_kernel(Params p, RoadIn
         bool any_coll = false, e0_present = false, e0_coll = false;
         double x0 = 0.0, y0 = 0.0;
         for (int e = tid; e < p.E; e += nthr) {
-            const uint32_t idx = (uint32_t)r * p.EP + (uint32_t)e;
-            const LanePtr dy(p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64), (idx & 63) * 8u);
-            const bool present = fld<uint64_t>(dy, SG_F_PRESENT) != 0;
+            const double *dy = entity_dyn(p, (uint32_t)r * p.EP + (uint32_t)e);
+            const bool present = entity_present(dy);
             bool mine = false;
-            for (int w = 0; w < W; ++w) mine = mine || fld<uint64_t>(dy, SG_F_COLL + w) != 0;
+            for (int w = 0; w < W; ++w) mine = mine || reinterpret_cast<const uint64_t *>(dy)[(SG_F_COLL + w) * 64] != 0;
             any_coll = any_coll || (present && mine);
-            if (e == 0) { e0_present = present; e0_coll = mine; x0 = fld(dy, SG_F_POSE + 0); y0 = fld(dy, SG_F_POSE + 1); }
+            if (e == 0) { e0_present = present; e0_coll = mine; x0 = dy[(SG_F_POSE + 0) * 64]; y0 = dy[(SG_F_POSE + 1) * 64]; }
         }
         const int any = __syncthreads_or(any_coll);
         if (tid == 0) flags[r] = sg_terminal_bits_of_entity0(p, r, e0_present, e0_coll, x0, y0) | (any ? SG_TERM_COLLISION : 0u);
@@ -188,16 +189,16 @@ static __global__ __launch_bounds__(256) void look_ahead_kernel(Params p, const 
     const double start = p.sdyn[r].t, stop = start + horizon;
     const double step = n_samples > 1 ? (stop - start) / (double)(n_samples - 1) : 0.0; // np.linspace
     auto corners_at = [&](int e, int j, double *C) -> bool {
-        const uint32_t idx = (uint32_t)r * p.EP + e;
-        const LanePtr st(p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64), (idx & 63) * 8u);
-        const int64_t meta = fld<int64_t>(st, ST_META);
+        const double *st = entity_stat(p, (uint32_t)r * p.EP + e);
+        const int64_t *sti = reinterpret_cast<const int64_t *>(st);
+        const int64_t meta = sti[ST_META * 64];
         if ((int)(meta & 0xff) == SG_KIND_NONE) return false;
         double tj = (double)j * step + start;
         if (n_samples > 1 && j == n_samples - 1) tj = stop;
         double pose[6], s, c;
-        own_position_clamped(p.knots + fld<int64_t>(st, ST_KNOT_OFF) * 7, (int)(meta >> 32), tj, pose);
+        own_position_clamped(p.knots + sti[ST_KNOT_OFF * 64] * 7, (int)(meta >> 32), tj, pose);
         sg_sincos(pose[3], s, c);
-        sg_corners(pose[0], pose[1], s, c, fld(st, ST_BW), fld(st, ST_BL), fld(st, ST_BCX), fld(st, ST_BCY), C);
+        sg_corners(pose[0], pose[1], s, c, st[ST_BW * 64], st[ST_BL * 64], st[ST_BCX * 64], st[ST_BCY * 64], C);
         return true;
     };
     bool hit = false;
@@ -228,97 +229,107 @@ static __global__ __launch_bounds__(256) void look_ahead_kernel(Params p, const 
 #endif // SG_UNIT_OBS
 
 // ------------------------------------------------------------------------------------------------
-// The vector observation: the k nearest entities around an observer, in the observer's frame (no counterpart in the
-// reference, whose State.get_entities_in_radius answers for one scenario on the host).  Candidates are the other present
-// entities of the observer's scenario with a finite squared distance d2 = dx * dx + dy * dy <= radius * radius (plain fp64,
-// unfused); the order is ascending (d2, slot).  A non-negative finite double orders as its bit pattern does, so the key of
-// the selection is d2 as a 64-bit integer and "no candidate" is the all-ones word, above every finite key.
+// The observer and its scenario, as the kernels below and driver_policy_kernel (sgym_policy.hpp) read them: one wavefront per
+// observer in workgroups of 256.  What belongs to the observer alone is the same in every lane: each lane loads and computes
+// it for itself (one address per load, one sg_sincos), which costs no more than staging it would, and what a kernel does not
+// use of it falls to the compiler.  The scenario's slots go by in blocks of 64, lane = entity.
 // ------------------------------------------------------------------------------------------------
-#define SG_NEAR_MAX_K 32
-constexpr uint64_t NEAR_NONE = ~0ull;
-constexpr int NEAR_NO_SLOT = 0x7fffffff;
-
-// the first dynamic / static row of padded entity index idx = r * EP + slot: field f is at [f * 64]
-__device__ __forceinline__ const double *near_dyn(const Params &p, uint32_t idx)
+// the thread's lane and its wavefront's item o = 4 * block + wave_index() (whole_group: o = block, the four wavefronts share it);
+// false: no item o < n -- for the whole wavefront, or workgroup
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ bool wave_item(int64_t n, int &lane, int64_t &o, bool whole_group = false)
 {
-    return p.dyn + (size_t)(idx >> 6) * ((size_t)p.FROWS * 64) + (idx & 63);
-}
-__device__ __forceinline__ const double *near_stat(const Params &p, uint32_t idx)
-{
-    return p.stat + (size_t)(idx >> 6) * (ST_COUNT * 64) + (idx & 63);
+    lane = threadIdx.x & 63;
+    o = whole_group ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave_index();
+    return o < n;
 }
 
-// the observer: scenario, slot, position, velocity, sin / cos of its heading, presence (the same for every lane of its wavefronts)
-struct NearObserver {
+// the observer: scenario, slot, position, velocity, sin / cos of its heading, presence (the reference's sensors need
+// state.poses[entity]: an observer that is not in the scene sees nothing); to_frame: a world vector in the observer's frame
+struct Observer {
     double x, y, vx, vy, s, c;
     int r, slot, present;
+    __device__ __forceinline__ void to_frame(double X, double Y, double &fx, double &fy) const { fx = X * c + Y * s; fy = Y * c - X * s; }
 };
 
-__device__ __forceinline__ NearObserver near_observer(const Params &p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t o)
+__device__ __forceinline__ Observer observer_at(const Params &p, int r, int slot)
 {
-    NearObserver f;
-    f.r = obs_scen ? obs_scen[o] : (int)o;
-    f.slot = obs_scen ? obs_slot[o] : p.sstat[o].ego;
-    const double *d = near_dyn(p, (uint32_t)f.r * p.EP + (uint32_t)f.slot);
-    f.present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
+    Observer f;
+    f.r = r; f.slot = slot;
+    const double *d = entity_dyn(p, (uint32_t)r * p.EP + (uint32_t)slot);
+    f.present = entity_present(d);
     f.x = d[(SG_F_POSE + 0) * 64]; f.y = d[(SG_F_POSE + 1) * 64];
     f.vx = d[(SG_F_VEL + 0) * 64]; f.vy = d[(SG_F_VEL + 1) * 64];
     sg_sincos(d[(SG_F_POSE + 3) * 64], f.s, f.c);
     return f;
 }
 
-// the key of slot e of the observer's scenario.  A lane without a slot (e >= E) reads the observer's own rows, which are
-// there, and gets NEAR_NONE like the observer itself.
-__device__ __forceinline__ uint64_t near_key(const Params &p, const NearObserver &f, int e, double r2)
+// observer o of a list: (obs_scen[o], obs_slot[o]), or -- without a list (obs_scen == nullptr) -- the ego of scenario o
+__device__ __forceinline__ Observer observer_of(const Params &p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t o)
 {
-    const bool other = e < p.E && e != f.slot;
-    const double *d = near_dyn(p, (uint32_t)f.r * p.EP + (uint32_t)(other ? e : f.slot));
-    const bool present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
-    const double dx = d[(SG_F_POSE + 0) * 64] - f.x, dy = d[(SG_F_POSE + 1) * 64] - f.y;
-    const double d2 = dx * dx + dy * dy;
-    const bool in = other && present && d2 <= r2 && d2 < __builtin_inf(); // (a NaN fails both)
-    return in ? (uint64_t)__double_as_longlong(d2) : NEAR_NONE;
+    return observer_at(p, obs_scen ? obs_scen[o] : (int)o, obs_scen ? obs_slot[o] : p.sstat[o].ego);
 }
 
-// the smallest (key, slot) of the wavefront, in every lane: a butterfly of cross-lane reads, no LDS
-__device__ __forceinline__ void near_wave_min(uint64_t &key, int &slot)
+// Slot e of the observer's scenario: its rows, whether it is an entity other than the observer, and (a load) whether it is in
+// the scene.  A lane without a slot (e >= E) reads the observer's own rows, which are there, as e == f.slot does: other == false.
+struct ObservedSlot {
+    const double *dyn, *stat; // entity_dyn / entity_stat
+    bool other;
+    __device__ __forceinline__ bool present() const { return entity_present(dyn); }
+};
+
+__device__ __forceinline__ ObservedSlot observed_slot(const Params &p, const Observer &f, int e)
 {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const uint64_t ok = __shfl_xor(key, m, 64);
-        const int os = __shfl_xor(slot, m, 64);
-        const bool take = ok < key || (ok == key && os < slot);
-        key = take ? ok : key;
-        slot = take ? os : slot;
-    }
+    const bool other = e < p.E && e != f.slot;
+    const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)(other ? e : f.slot);
+    return {entity_dyn(p, idx), entity_stat(p, idx), other};
+}
+
+// ------------------------------------------------------------------------------------------------
+// The vector observation: the k nearest entities around an observer, in the observer's frame (no counterpart in the
+// reference, whose State.get_entities_in_radius answers for one scenario on the host).  Candidates are the other present
+// entities of the observer's scenario with a finite squared distance d2 = dx * dx + dy * dy <= radius * radius (plain fp64,
+// unfused); the order is ascending (d2, slot), the key of the selection d2 as a 64-bit integer (KEY_NONE, sgym_polyline.hpp).
+// ------------------------------------------------------------------------------------------------
+#define SG_NEAR_MAX_K 32
+
+// the key of slot e of the observer's scenario; KEY_NONE for the observer itself and for a lane without a slot
+__device__ __forceinline__ uint64_t near_key(const Params &p, const Observer &f, int e, double r2)
+{
+    const ObservedSlot q = observed_slot(p, f, e);
+    const bool present = q.present();
+    const double dx = q.dyn[(SG_F_POSE + 0) * 64] - f.x, dy = q.dyn[(SG_F_POSE + 1) * 64] - f.y;
+    const double d2 = dx * dx + dy * dy;
+    const bool in = q.other && present && d2 <= r2 && d2 < __builtin_inf(); // (a NaN fails both)
+    return in ? (uint64_t)__double_as_longlong(d2) : KEY_NONE;
 }
 
 // k rounds over the N register entries of every lane: the wavefront's minimum, which its owner retires (slots are unique;
-// an entry that holds nothing has slot NEAR_NO_SLOT).  Lane j returns the slot of round j, -1 once the candidates ran out.
+// an entry that holds nothing has slot INDEX_NONE).  Lane j returns the slot of round j, -1 once the candidates ran out.
 template <int N>
 __device__ __forceinline__ int near_select(uint64_t (&key)[N], const int (&slot)[N], int k, int lane)
 {
     int mine = -1;
     for (int j = 0; j < k; ++j) {
-        uint64_t bk = NEAR_NONE;
-        int bs = NEAR_NO_SLOT;
+        uint64_t bk = KEY_NONE;
+        int bs = INDEX_NONE;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const bool take = key[i] < bk || (key[i] == bk && slot[i] < bs);
             bk = take ? key[i] : bk;
             bs = take ? slot[i] : bs;
         }
-        near_wave_min(bk, bs);
-        if (bk == NEAR_NONE) break; // (the same in every lane)
+        wave_min(bk, bs);
+        if (bk == KEY_NONE) break; // (the same in every lane)
 #pragma unroll
-        for (int i = 0; i < N; ++i) key[i] = slot[i] == bs ? NEAR_NONE : key[i];
+        for (int i = 0; i < N; ++i) key[i] = slot[i] == bs ? KEY_NONE : key[i];
         if (lane == j) mine = bs;
     }
     return mine;
 }
 
 // row `lane` of observer o: the eight features of neighbour nb (zeros for nb < 0), its slot, and the observer's count
-__device__ __forceinline__ void near_store(const Params &p, const NearObserver &f, int64_t o, int k, int lane, int nb, int total,
+__device__ __forceinline__ void near_store(const Params &p, const Observer &f, int64_t o, int k, int lane, int nb, int total,
                                            double *feat, int32_t *slots, int32_t *count)
 {
     if (lane == 0 && count) count[o] = total;
@@ -326,17 +337,12 @@ __device__ __forceinline__ void near_store(const Params &p, const NearObserver &
     double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (nb >= 0) {
         const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)nb;
-        const double *d = near_dyn(p, idx), *st = near_stat(p, idx);
-        const double dx = d[(SG_F_POSE + 0) * 64] - f.x, dy = d[(SG_F_POSE + 1) * 64] - f.y;
-        const double dvx = d[(SG_F_VEL + 0) * 64] - f.vx, dvy = d[(SG_F_VEL + 1) * 64] - f.vy;
+        const double *d = entity_dyn(p, idx), *st = entity_stat(p, idx);
         double se, ce;
         sg_sincos(d[(SG_F_POSE + 3) * 64], se, ce);
-        v[0] = dx * f.c + dy * f.s;
-        v[1] = dy * f.c - dx * f.s;
-        v[2] = ce * f.c + se * f.s;
-        v[3] = se * f.c - ce * f.s;
-        v[4] = dvx * f.c + dvy * f.s;
-        v[5] = dvy * f.c - dvx * f.s;
+        f.to_frame(d[(SG_F_POSE + 0) * 64] - f.x, d[(SG_F_POSE + 1) * 64] - f.y, v[0], v[1]);
+        f.to_frame(ce, se, v[2], v[3]);
+        f.to_frame(d[(SG_F_VEL + 0) * 64] - f.vx, d[(SG_F_VEL + 1) * 64] - f.vy, v[4], v[5]);
         v[6] = st[ST_BL * 64];
         v[7] = st[ST_BW * 64];
     }
@@ -346,7 +352,7 @@ __device__ __forceinline__ void near_store(const Params &p, const NearObserver &
     if (slots) slots[(size_t)o * k + lane] = nb;
 }
 
-// Observer o < n: (obs_scen[o], obs_slot[o]), or -- obs_scen == nullptr -- the ego of scenario o.  feat [n][k][8] fp64, slots
+// Observer o < n: observer_of.  feat [n][k][8] fp64, slots
 // [n][k] (-1 behind the last neighbour; may be nullptr), count [n] (candidates within the radius, it may exceed k; -1 for an
 // observer that is not present, whose rows are zeros; may be nullptr).  Every byte of the three is written.  1 <= k <= 32.
 // NB > 0 (scenarios of at most NB * 64 <= 512 entities): one wavefront per observer, four observers per workgroup.  Lane l owns
@@ -361,10 +367,10 @@ template <int NB>
 static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n, int k,
                                                              double r2, double *feat, int32_t *slots, int32_t *count)
 {
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t o = NB ? (int64_t)blockIdx.x * 4 + w : (int64_t)blockIdx.x;
-    if (o >= n) return; // (NB > 0: the whole wavefront, which meets no barrier)
-    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o, NB == 0)) return; // (NB > 0: the whole wavefront, which meets no barrier)
+    const int w = wave_index();
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
     if (!f.present) { // (the whole workgroup on the wide path)
         if (NB || w == 0) near_store(p, f, o, k, lane, -1, -1, feat, slots, count);
         return;
@@ -376,7 +382,7 @@ static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int
         for (int j = 0; j < NB; ++j) {
             slot[j] = lane + 64 * j;
             key[j] = near_key(p, f, slot[j], r2);
-            total += __popcll(__ballot(key[j] != NEAR_NONE));
+            total += __popcll(__ballot(key[j] != KEY_NONE));
         }
         const int nb = near_select<NB>(key, slot, k, lane);
         near_store(p, f, o, k, lane, nb, total, feat, slots, count);
@@ -385,22 +391,22 @@ static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int
         __shared__ int fin_slot[4 * SG_NEAR_MAX_K];
         __shared__ int fin_total[4];
         const int n_blocks = (p.E + 63) >> 6;
-        uint64_t last_key = 0, my_key = NEAR_NONE;
-        int last_slot = -1, my_slot = NEAR_NO_SLOT, total = 0;
+        uint64_t last_key = 0, my_key = KEY_NONE;
+        int last_slot = -1, my_slot = INDEX_NONE, total = 0;
         for (int j = 0; j < k; ++j) {
-            uint64_t bk = NEAR_NONE;
-            int bs = NEAR_NO_SLOT;
+            uint64_t bk = KEY_NONE;
+            int bs = INDEX_NONE;
             for (int b = w; b < n_blocks; b += 4) {
                 const int e = b * 64 + lane;
                 const uint64_t ke = near_key(p, f, e, r2);
-                if (j == 0) total += __popcll(__ballot(ke != NEAR_NONE));
+                if (j == 0) total += __popcll(__ballot(ke != KEY_NONE));
                 const bool after = ke > last_key || (ke == last_key && e > last_slot);
                 const bool take = after && (ke < bk || (ke == bk && e < bs));
                 bk = take ? ke : bk;
                 bs = take ? e : bs;
             }
-            near_wave_min(bk, bs);
-            if (bk == NEAR_NONE) break; // (the same in every lane: the stripe has run out)
+            wave_min(bk, bs);
+            if (bk == KEY_NONE) break; // (the same in every lane: the stripe has run out)
             if (lane == j) { my_key = bk; my_slot = bs; }
             last_key = bk; last_slot = bs;
         }
@@ -420,14 +426,10 @@ static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int
 // The lane-frame vector observation: where an observer sits relative to the k nearest lane centre lines of its scenario's
 // network, and where those lines go next (no counterpart in the reference, which only stores Lane.center and the successor
 // ids).  The definition is in include/sgym.h at sg_lane_observation; the rows below are built by sg_set_lanes (h_road.hip).
-// Segments are listed lane by lane, so a lane's segments are consecutive and segment order is lane order.
-// (SG_LANE_MAX_K, SG_LANE_MAX_AHEAD, SG_LANE_MAX_HOPS: include/sgym.h.)
+// Segments (LaneSeg rows, sgym_polyline.hpp) are listed lane by lane, so a lane's segments are consecutive and segment order is
+// lane order.  (SG_LANE_MAX_K, SG_LANE_MAX_AHEAD, SG_LANE_MAX_HOPS: include/sgym.h.)
 // ------------------------------------------------------------------------------------------------
 
-struct LaneSeg {      // one centre-line segment a -> b: 80 bytes
-    double ax, ay, ex, ey, L2, len, cum, bx, by; // e = b - a, L2 = ex*ex + ey*ey, len = sqrt(L2), cum = arclength of a within its lane
-    int32_t lane, first;                         // its lane and that lane's first segment (both indices over all networks)
-};
 struct LaneRow {      // one lane
     double total;           // its length: cum + len of its last segment (0 without segments)
     int32_t seg0, seg1;     // its segments [seg0, seg1)
@@ -444,19 +446,6 @@ struct LaneIndex {    // device pointers, by value; seg == nullptr: no lanes set
     const int32_t *net_of_scen; // the list of sg_set_road_networks
 };
 
-// the closest point of segment g to (px, py): the squared distance, the offsets from that point, the effective parameter
-__device__ __forceinline__ double lane_project(const LaneSeg &g, double px, double py, double &dx, double &dy, double &t)
-{
-    const double wx = px - g.ax, wy = py - g.ay;
-    t = (wx * g.ex + wy * g.ey) / g.L2;
-    double cx = g.ax, cy = g.ay;
-    if (g.L2 == 0.0 || !(t > 0.0)) t = 0.0;
-    else if (t >= 1.0) { t = 1.0; cx = g.bx; cy = g.by; }
-    else { cx = g.ax + t * g.ex; cy = g.ay + t * g.ey; }
-    dx = px - cx; dy = py - cy;
-    return dx * dx + dy * dy;
-}
-
 // the centre-line point at arclength `target` from the start of lane q, walked through the lowest-index successors that
 // have segments
 __device__ __forceinline__ void lane_point_ahead(const LaneIndex &L, int q, double target, double &x, double &y)
@@ -472,26 +461,14 @@ __device__ __forceinline__ void lane_point_ahead(const LaneIndex &L, int q, doub
         target -= row.total;
         row = L.lane[next];
     }
-    if (target > row.total) { // the end of the walk: the lane's last point
-        x = L.seg[row.seg1 - 1].bx; y = L.seg[row.seg1 - 1].by;
-        return;
-    }
-    int lo = row.seg0, hi = row.seg1; // the last segment with cum <= target (cum[seg0] = 0 <= target)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (L.seg[mid].cum <= target) lo = mid; else hi = mid;
-    }
-    const LaneSeg g = L.seg[lo];
-    const double u = g.len == 0.0 ? 0.0 : (target - g.cum) / g.len;
-    if (u >= 1.0) { x = g.bx; y = g.by; }
-    else { x = g.ax + u * g.ex; y = g.ay + u * g.ey; }
+    polyline_point_at(L.seg, row.seg0, row.seg1, row.total, target, x, y); // (beyond the end of the walk: the lane's last point)
 }
 
-// Observer o < n as in nearest_kernel; feat [n][k][6 + 2 * n_ahead], lanes [n][k] (may be nullptr), count [n] (may be nullptr),
+// Observer o < n: observer_of; feat [n][k][6 + 2 * n_ahead], lanes [n][k] (may be nullptr), count [n] (may be nullptr),
 // every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no atomics.
 // Selection: k rounds; in each the wavefront's lanes stride over the network's segment rows (a load is 64 consecutive 80-byte
 // rows), skip the segments of the road lanes chosen so far -- at most eight ids, the same in every lane of the wavefront --
-// and keep the smallest (d2 bits, segment index); near_wave_min makes it the wavefront's.  A rescan per round rather than a
+// and keep the smallest (d2 bits, segment index); wave_min makes it the wavefront's.  A rescan per round rather than a
 // table of per-road-lane minima in LDS: a network has no bound on its lanes, so the table would need a second path for
 // the networks that do not fit, and k times the segment tests of the largest committed network (11,040 points) is below the
 // launch overhead of the call.  Round 0 also counts the candidates: a segment within the radius counts for its road lane iff no
@@ -504,10 +481,9 @@ static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, 
                                                                       int64_t n, int k, int n_ahead, double spacing, double r2, double *feat,
                                                                       int32_t *lanes, int32_t *count)
 {
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t o = (int64_t)blockIdx.x * 4 + w;
-    if (o >= n) return; // (the whole wavefront, which meets no barrier)
-    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
     const int net = (f.present && L.seg) ? L.net_of_scen[f.r] : -1;
     int total = f.present ? 0 : -1, found = 0;
     int mine = 0; // lane j: the best segment of row j
@@ -518,8 +494,8 @@ static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, 
         for (int m = 0; m < SG_LANE_MAX_K; ++m) ch[m] = -1;
         int counted = -1; // round 0: the last road lane counted
         for (int j = 0; j < k; ++j) {
-            uint64_t bk = NEAR_NONE;
-            int bs = NEAR_NO_SLOT;
+            uint64_t bk = KEY_NONE;
+            int bs = INDEX_NONE;
             for (int i0 = N.seg0; i0 < N.seg1; i0 += 64) { // (uniform trip count: the ballot below is the whole wavefront's)
                 const int i = i0 + lane;
                 const LaneSeg g = L.seg[min(i, N.seg1 - 1)];
@@ -540,8 +516,8 @@ static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, 
                 bk = take ? key : bk;
                 bs = take ? i : bs;
             }
-            near_wave_min(bk, bs);
-            if (bk == NEAR_NONE) break; // (the same in every lane: no candidate is left)
+            wave_min(bk, bs);
+            if (bk == KEY_NONE) break; // (the same in every lane: no candidate is left)
             const int q = __builtin_amdgcn_readfirstlane(L.seg[bs].lane);
 #pragma unroll
             for (int m = 0; m < SG_LANE_MAX_K; ++m) ch[m] = m == j ? q : ch[m];
@@ -560,23 +536,14 @@ static __global__ __launch_bounds__(256) void lane_observation_kernel(Params p, 
         if (j < found) {
             const LaneSeg g = L.seg[best];
             q = g.lane;
-            double dx, dy, t;
-            const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
-            const double s0 = g.cum + t * g.len;
+            const SegmentView sv = segment_view(g, f.x, f.y, f.s, f.c);
             if (m == 0) {
-                const double ux = g.len == 0.0 ? 0.0 : g.ex / g.len, uy = g.len == 0.0 ? 0.0 : g.ey / g.len;
-                v[0] = ux * dy - uy * dx;
-                v[1] = f.c * ux + f.s * uy;
-                v[2] = f.s * ux - f.c * uy;
-                v[3] = s0;
-                v[4] = L.lane[q].total - s0;
-                v[5] = __builtin_sqrt(d2);
+                v[0] = sv.offset; v[1] = sv.cos_err; v[2] = sv.sin_err;
+                v[3] = sv.arc; v[4] = L.lane[q].total - sv.arc; v[5] = __builtin_sqrt(sv.d2);
             } else {
                 double x, y;
-                lane_point_ahead(L, q, s0 + (double)m * spacing, x, y);
-                const double X = x - f.x, Y = y - f.y;
-                v[0] = X * f.c + Y * f.s;
-                v[1] = Y * f.c - X * f.s;
+                lane_point_ahead(L, q, sv.arc + (double)m * spacing, x, y);
+                f.to_frame(x - f.x, y - f.y, v[0], v[1]);
             }
         }
         double *row = feat + ((size_t)o * k + j) * W;
@@ -615,7 +582,7 @@ __device__ __forceinline__ void scan_slab(double o, double l, double lo, double 
     tf = along ? (inside ? __builtin_inf() : -__builtin_inf()) : (up ? t2 : t1);
 }
 
-// Observer o < n as in nearest_kernel; feat [n][n_rays][2] (range, range rate), slots [n][n_rays] (may be nullptr), hits [n]
+// Observer o < n: observer_of; feat [n][n_rays][2] (range, range rate), slots [n][n_rays] (may be nullptr), hits [n]
 // (may be nullptr), every byte written.  One wavefront per observer, four observers per workgroup, no barrier.  The scenario's
 // slots go by in blocks of 64, ascending, through the wavefront's own LDS rows:
 //   phase one, lane = entity: presence, sin / cos of its heading, the ScanRow -- once per observer and block of beams, not once
@@ -632,10 +599,10 @@ static __global__ __launch_bounds__(256) void range_scan_kernel(Params p, const 
                                                                 int32_t *hits)
 {
     __shared__ ScanRow rows[4][64];
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t o = (int64_t)blockIdx.x * 4 + w;
-    if (o >= n) return; // (the whole wavefront, which meets no barrier)
-    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
+    const int w = wave_index();
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
     const double reach = max_range * 1.000000001;
     int total = f.present ? 0 : -1;
     for (int b0 = 0; b0 < n_rays; b0 += 64) {
@@ -647,10 +614,8 @@ static __global__ __launch_bounds__(256) void range_scan_kernel(Params p, const 
             sg_sincos(angle0 + (double)b * dangle, sb, cb);
             const double ux = cb * f.c - sb * f.s, uy = sb * f.c + cb * f.s;
             for (int e0 = 0; e0 < p.E; e0 += 64) {
-                const int e = e0 + lane;
-                const bool other = e < p.E && e != f.slot; // (a lane without a slot reads the observer's own rows, which are there)
-                const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)(other ? e : f.slot);
-                const double *d = near_dyn(p, idx), *st = near_stat(p, idx);
+                const ObservedSlot es = observed_slot(p, f, e0 + lane);
+                const double *d = es.dyn, *st = es.stat;
                 ScanRow q;
                 sg_sincos(d[(SG_F_POSE + 3) * 64], q.se, q.ce);
                 const double dx = f.x - d[(SG_F_POSE + 0) * 64], dy = f.y - d[(SG_F_POSE + 1) * 64];
@@ -664,11 +629,11 @@ static __global__ __launch_bounds__(256) void range_scan_kernel(Params p, const 
                 const double x1 = q.xlo - q.ox, x2 = q.xhi - q.ox, y1 = q.ylo - q.oy, y2 = q.yhi - q.oy;
                 const bool out_of_reach = (x1 > reach && x2 > reach) || (x1 < -reach && x2 < -reach) || (y1 > reach && y2 > reach) ||
                                           (y1 < -reach && y2 < -reach);
-                const bool present = reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] != 0;
+                const bool present = es.present();
                 tile_sync<1>(); // (the previous block's rows have been read)
                 rows[w][lane] = q;
                 tile_sync<1>();
-                for (uint64_t todo = __ballot(other && present && !out_of_reach); todo; todo &= todo - 1) {
+                for (uint64_t todo = __ballot(es.other && present && !out_of_reach); todo; todo &= todo - 1) {
                     const int j = __builtin_ctzll(todo);
                     const ScanRow g = rows[w][j];
                     const double lx = ux * g.ce + uy * g.se, ly = uy * g.ce - ux * g.se;
@@ -727,52 +692,48 @@ __device__ __forceinline__ double status_corners_to_edges(const double (&P)[8], 
     return best;
 }
 
-// Observer o < n as in nearest_kernel; flags [n], info [n][SG_ST_NINFO] (may be nullptr), feat [n][SG_ST_NFEAT] (may be nullptr),
-// every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no barrier, no atomics.  What belongs
-// to the observer alone -- its rows, its corners, its collision row's word of the block at hand -- is the same in every lane:
-// each lane loads and computes it for itself (one address per load, one sg_sincos), which costs no more than staging it would.
+// Observer o < n: observer_of; flags [n], info [n][SG_ST_NINFO] (may be nullptr), feat [n][SG_ST_NFEAT] (may be nullptr),
+// every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no barrier, no atomics.  Its corners
+// and its collision row's word of the block at hand belong to the observer alone, like its pose: every lane has them for itself.
 //   the row: lane l takes the words l, l + 64, ... (one word up to 64 slots, at most 256): set bits, the lowest, and the entity
 //     type of every set slot; a butterfly sums, takes the minimum and ORs.
 //   the clearance: the scenario's slots go by in blocks of 64, ascending, lane = entity.  A lane whose bit of the row is set
 //     has gap2 = +0.0; the other present ones get sin / cos of their heading, their corners, and the 32 corner-to-edge tests;
 //     a block in which no lane has such a test to run (nobody present, or everybody in the row) skips them.  Per lane a running
-//     (gap2 bits, slot) with a strict <, then near_wave_min: a finite non-negative double orders as its bit pattern does.
+//     (gap2 bits, slot) with a strict <, then wave_min: a finite non-negative double orders as its bit pattern does.
 //     No pre-filter: every candidate is tested, so the answers are those of the plain definition by construction.
 //   the surfaces: lane 0 looks up the pose point for all eight layers, lanes 1..4 a corner each for the driveable surface.
 #ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
 static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n,
                                                                    uint32_t *flags, int32_t *info, double *feat)
 {
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t o = (int64_t)blockIdx.x * 4 + w;
-    if (o >= n) return; // (the whole wavefront, which meets no barrier)
-    const int r = obs_scen ? obs_scen[o] : (int)o, slot = obs_scen ? obs_slot[o] : p.sstat[o].ego;
-    const uint32_t base = (uint32_t)r * p.EP;
-    const double *d = near_dyn(p, base + (uint32_t)slot), *st = near_stat(p, base + (uint32_t)slot);
-    if (reinterpret_cast<const uint64_t *>(d)[SG_F_PRESENT * 64] == 0) { // not in State.poses: the rule for an absent entities[0]
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
+    if (!f.present) { // not in State.poses: the rule for an absent entities[0]
         if (lane == 0) flags[o] = SG_ST_OFF_ROAD;
         if (info && lane < SG_ST_NINFO) info[(size_t)o * SG_ST_NINFO + lane] = -1;
         if (feat && lane < SG_ST_NFEAT) feat[(size_t)o * SG_ST_NFEAT + lane] = 0.0;
         return;
     }
-    const double x = d[(SG_F_POSE + 0) * 64], y = d[(SG_F_POSE + 1) * 64];
-    double A[8], sa, ca;
-    sg_sincos(d[(SG_F_POSE + 3) * 64], sa, ca);
-    sg_corners(x, y, sa, ca, st[ST_BW * 64], st[ST_BL * 64], st[ST_BCX * 64], st[ST_BCY * 64], A);
+    const ObservedSlot own = observed_slot(p, f, f.slot);
+    const double *d = own.dyn, *st = own.stat;
+    double A[8];
+    sg_corners(f.x, f.y, f.s, f.c, st[ST_BW * 64], st[ST_BL * 64], st[ST_BCX * 64], st[ST_BCY * 64], A);
 
     // the collision row
     const uint64_t *row = reinterpret_cast<const uint64_t *>(d) + SG_F_COLL * 64; // word q: row[q * 64]
     const int W = p.FROWS - SG_F_COLL;                                             // (64 * W >= E)
-    int pop = 0, low = NEAR_NO_SLOT;
+    int pop = 0, low = INDEX_NONE;
     uint32_t hit = 0u;
     for (int q = lane; q < W; q += 64) {
         uint64_t m = row[(size_t)q * 64];
         pop += __popcll(m);
-        if (m && low == NEAR_NO_SLOT) low = q * 64 + __builtin_ctzll(m); // (ascending q: this lane's lowest)
+        if (m && low == INDEX_NONE) low = q * 64 + __builtin_ctzll(m); // (ascending q: this lane's lowest)
         for (; m; m &= m - 1) {
             const int e = q * 64 + __builtin_ctzll(m);
             if (e >= p.E) continue; // (a row holds entity slots only)
-            const int64_t meta = reinterpret_cast<const int64_t *>(near_stat(p, base + (uint32_t)e))[ST_META * 64];
+            const int64_t meta = reinterpret_cast<const int64_t *>(entity_stat(p, (uint32_t)f.r * p.EP + (uint32_t)e))[ST_META * 64];
             const int etype = (int)((meta >> 8) & 0xff);
             hit |= etype == 0 ? SG_ST_HIT_VEHICLE : etype == 1 ? SG_ST_HIT_PEDESTRIAN : SG_ST_HIT_OTHER;
         }
@@ -785,14 +746,13 @@ static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, con
     }
 
     // the clearance
-    uint64_t bk = NEAR_NONE;
-    int bs = NEAR_NO_SLOT;
+    uint64_t bk = KEY_NONE;
+    int bs = INDEX_NONE;
     for (int e0 = 0; e0 < p.E; e0 += 64) {
         const int e = e0 + lane;
-        const bool other = e < p.E && e != slot; // (a lane without a slot reads the observer's own rows, which are there)
-        const uint32_t idx = base + (uint32_t)(other ? e : slot);
-        const double *de = near_dyn(p, idx), *se = near_stat(p, idx);
-        const bool in = other && reinterpret_cast<const uint64_t *>(de)[SG_F_PRESENT * 64] != 0;
+        const ObservedSlot es = observed_slot(p, f, e);
+        const double *de = es.dyn, *se = es.stat;
+        const bool in = es.other && es.present();
         const bool bit = ((row[(size_t)(e0 >> 6) * 64] >> lane) & 1ull) != 0;
         double g = __builtin_inf();
         if (sg_any(in && !bit)) {
@@ -804,20 +764,20 @@ static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, con
             g = status_corners_to_edges(B, A, g);
         }
         g = bit ? 0.0 : g;
-        const uint64_t key = in && g < __builtin_inf() ? (uint64_t)__double_as_longlong(g) : NEAR_NONE;
+        const uint64_t key = in && g < __builtin_inf() ? (uint64_t)__double_as_longlong(g) : KEY_NONE;
         const bool take = key < bk; // (ascending slots per lane: the lower slot keeps a tie)
         bk = take ? key : bk;
         bs = take ? e : bs;
     }
-    near_wave_min(bk, bs);
+    wave_min(bk, bs);
 
     // the surfaces: the pose point (every layer) and the four corners (the driveable surface)
     uint32_t lay = 0u;
     if (lane < 5 && p.road) {
         const RoadIndex RI = *p.road;
-        const double px = lane == 0 ? x : lane == 1 ? A[0] : lane == 2 ? A[2] : lane == 3 ? A[4] : A[6];
-        const double py = lane == 0 ? y : lane == 1 ? A[1] : lane == 2 ? A[3] : lane == 3 ? A[5] : A[7];
-        lay = rn_layers_at(RI, RI.net_of_scen[r], lane == 0 ? 0xffu : SG_LAYER_DRIVEABLE, px, py);
+        const double px = lane == 0 ? f.x : lane == 1 ? A[0] : lane == 2 ? A[2] : lane == 3 ? A[4] : A[6];
+        const double py = lane == 0 ? f.y : lane == 1 ? A[1] : lane == 2 ? A[3] : lane == 3 ? A[5] : A[7];
+        lay = rn_layers_at(RI, RI.net_of_scen[f.r], lane == 0 ? 0xffu : SG_LAYER_DRIVEABLE, px, py);
     }
     const int corners_on = __popcll(__ballot(lane >= 1 && lane < 5 && (lay & SG_LAYER_DRIVEABLE) != 0));
     const uint32_t lay0 = (uint32_t)__shfl((int)lay, 0, 64);
@@ -826,11 +786,11 @@ static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, con
         flags[o] = SG_ST_PRESENT | (pop ? SG_ST_COLLISION : 0u) | ((lay0 & SG_LAYER_DRIVEABLE) ? 0u : SG_ST_OFF_ROAD) |
                    (corners_on < 4 ? SG_ST_CORNER_OFF : 0u) | hit | (lay0 << SG_ST_LAYER_SHIFT);
     if (info && lane < SG_ST_NINFO)
-        info[(size_t)o * SG_ST_NINFO + lane] = lane == 0 ? pop : lane == 1 ? (low == NEAR_NO_SLOT ? -1 : low) : lane == 2 ? corners_on
-                                                                                                              : (bk == NEAR_NONE ? -1 : bs);
+        info[(size_t)o * SG_ST_NINFO + lane] = lane == 0 ? pop : lane == 1 ? (low == INDEX_NONE ? -1 : low) : lane == 2 ? corners_on
+                                                                                                              : (bk == KEY_NONE ? -1 : bs);
     if (feat && lane < SG_ST_NFEAT) {
         const double speed = sg_norm3(d[(SG_F_VEL + 0) * 64], d[(SG_F_VEL + 1) * 64], d[(SG_F_VEL + 2) * 64]);
-        const double gap = bk == NEAR_NONE ? __builtin_inf() : __builtin_sqrt(__longlong_as_double((long long)bk));
+        const double gap = bk == KEY_NONE ? __builtin_inf() : __builtin_sqrt(__longlong_as_double((long long)bk));
         feat[(size_t)o * SG_ST_NFEAT + lane] = lane == 0 ? speed : lane == 1 ? d[SG_F_DIST * 64] : gap;
     }
 }
@@ -841,8 +801,9 @@ static __global__ __launch_bounds__(256) void entity_status_kernel(Params p, con
 // where its own recording has it at the scenario's time -- progress along the route, what is left of it, points ahead, and the
 // displacement from the log (no counterpart in the reference, whose entities replay or are driven, never compared).  The
 // definition is in include/sgym.h at sg_route_observation: plain unfused fp64 with IEEE division and square root.  The route
-// rows are LaneSeg rows built by sg_set_routes exactly as sg_set_lanes builds its own; the point-to-segment rule is lane_project
-// and the recorded pose own_position_clamped, called, not restated; presence and the entity frame are those of nearest_kernel.
+// rows are LaneSeg rows built by sg_set_routes exactly as sg_set_lanes builds its own, read through polyline_nearest,
+// segment_view and polyline_point_at (sgym_polyline.hpp); the recorded pose is own_position_clamped; presence and the entity
+// frame are Observer's.
 // ------------------------------------------------------------------------------------------------
 struct RouteIndex {      // device pointers, by value; route_of == nullptr: no routes set
     const int32_t *route_of; // [R * EP] padded entity index -> route, -1 where the entity has none
@@ -851,25 +812,22 @@ struct RouteIndex {      // device pointers, by value; route_of == nullptr: no r
     const LaneSeg *seg;      // the segments of every route, route by route
 };
 
-// Observer o < n as in nearest_kernel; feat [n][SG_RT_NFEAT + 2 * n_ahead], info [n][SG_RT_NINFO] (may be nullptr), every byte
-// written.  One wavefront per observer, four per workgroup, no LDS, no barrier, no atomics.  What belongs to the observer alone
-// -- its pose, its recorded pose, the best row -- is the same in every lane: each lane loads and computes it for itself, as in
-// entity_status_kernel.
-//   phase one, lane = route segment: the lanes stride over the route's rows (a load is 64 consecutive 80-byte rows) and keep the
-//     smallest (d2 bits, index within the route); near_wave_min makes it the wavefront's.  Every lane then projects onto the best
-//     row again: the same operations on the same operands, so the same bits.
-//   phase two, lane m - 1 = look-ahead point m: its own binary search over cum, its own point.
+// Observer o < n: observer_of; feat [n][SG_RT_NFEAT + 2 * n_ahead], info [n][SG_RT_NINFO] (may be nullptr), every byte
+// written.  One wavefront per observer, four per workgroup, no LDS, no barrier, no atomics.  Its recorded pose and the best row
+// belong to the observer alone, like its pose: every lane computes them for itself.
+//   phase one, lane = route segment: polyline_nearest.  Every lane then projects onto the best row again (segment_view): the
+//     same operations on the same operands, so the same bits.
+//   phase two, lane m - 1 = look-ahead point m: its own polyline_point_at.
 //   the store, lane = feature: the row is at most 11 + 2 * 16 = 43 doubles, one pass; the look-ahead pairs come from their lanes
 //     by a cross-lane read.
 #ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
 static __global__ __launch_bounds__(256) void route_observation_kernel(Params p, RouteIndex P, const int32_t *obs_scen, const int32_t *obs_slot,
                                                                        int64_t n, int n_ahead, double spacing, double *feat, int32_t *info)
 {
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t o = (int64_t)blockIdx.x * 4 + w;
-    if (o >= n) return; // (the whole wavefront, which meets no barrier)
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
     const int W = SG_RT_NFEAT + 2 * n_ahead;
-    const NearObserver f = near_observer(p, obs_scen, obs_slot, o);
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
     double *row = feat + (size_t)o * W;
     if (!f.present) { // not in State.poses
         if (lane < W) row[lane] = 0.0;
@@ -879,7 +837,7 @@ static __global__ __launch_bounds__(256) void route_observation_kernel(Params p,
     const uint32_t idx = (uint32_t)f.r * p.EP + (uint32_t)f.slot;
 
     // the recorded track
-    const int64_t *sti = reinterpret_cast<const int64_t *>(near_stat(p, idx));
+    const int64_t *sti = reinterpret_cast<const int64_t *>(entity_stat(p, idx));
     const int n_k = (int)(sti[ST_META * 64] >> 32);
     double tr0 = 0.0, tr1 = 0.0, tr2 = 0.0, tr3 = 0.0, tr4 = 0.0;
     int when = 2;
@@ -890,63 +848,28 @@ static __global__ __launch_bounds__(256) void route_observation_kernel(Params p,
         own_position_clamped(kn, n_k, t, rec);
         const double X = rec[0] - f.x, Y = rec[1] - f.y;
         sg_sincos(rec[3], sr, cr);
-        tr0 = X * f.c + Y * f.s;
-        tr1 = Y * f.c - X * f.s;
+        f.to_frame(X, Y, tr0, tr1);
         tr2 = __builtin_sqrt(X * X + Y * Y);
-        tr3 = cr * f.c + sr * f.s;
-        tr4 = sr * f.c - cr * f.s;
+        f.to_frame(cr, sr, tr3, tr4);
         when = t < kn[0] ? -1 : t > kn[(size_t)(n_k - 1) * 7] ? 1 : 0;
     }
 
     // the route: phase one
     const int route = P.route_of ? P.route_of[idx] : -1;
     const int s0i = route >= 0 ? P.seg_off[route] : 0, s1i = route >= 0 ? P.seg_off[route + 1] : 0;
-    uint64_t bk = NEAR_NONE;
-    int bs = NEAR_NO_SLOT;
-    for (int i0 = s0i; i0 < s1i; i0 += 64) {
-        const int i = i0 + lane;
-        const LaneSeg g = P.seg[min(i, s1i - 1)];
-        double dx, dy, t;
-        const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
-        const bool take = i < s1i && d2 < __builtin_inf() && (uint64_t)__double_as_longlong(d2) < bk; // (a NaN fails; ascending i per lane)
-        bk = take ? (uint64_t)__double_as_longlong(d2) : bk;
-        bs = take ? i - s0i : bs;
-    }
-    near_wave_min(bk, bs);
-    const bool on_route = bk != NEAR_NONE; // (the same in every lane)
-    double rt0 = 0.0, rt1 = 0.0, rt2 = 0.0, rt3 = 0.0, rt4 = 0.0, rt5 = 0.0, ah0 = 0.0, ah1 = 0.0;
-    if (on_route) {
-        const LaneSeg g = P.seg[s0i + bs];
-        double dx, dy, t;
-        const double d2 = lane_project(g, f.x, f.y, dx, dy, t);
-        const double ux = g.len == 0.0 ? 0.0 : g.ex / g.len, uy = g.len == 0.0 ? 0.0 : g.ey / g.len;
+    const int best = polyline_nearest(P.seg, s0i, s1i, lane, f.x, f.y); // (the same in every lane)
+    SegmentView sv = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double left = 0.0, dist = 0.0, ah0 = 0.0, ah1 = 0.0;
+    if (best >= 0) {
+        sv = segment_view(P.seg[s0i + best], f.x, f.y, f.s, f.c);
         const double total = P.total[route];
-        rt0 = ux * dy - uy * dx;
-        rt1 = f.c * ux + f.s * uy;
-        rt2 = f.s * ux - f.c * uy;
-        rt3 = g.cum + t * g.len;
-        rt4 = total - rt3;
-        rt5 = __builtin_sqrt(d2);
+        left = total - sv.arc;
+        dist = __builtin_sqrt(sv.d2);
         // phase two
         if (lane < n_ahead) {
-            const double target = rt3 + (double)(lane + 1) * spacing;
             double x, y;
-            if (target > total) { // beyond the end: the route's last point
-                x = P.seg[s1i - 1].bx; y = P.seg[s1i - 1].by;
-            } else {
-                int lo = s0i, hi = s1i; // the last segment with cum <= target (cum[s0i] = 0 <= s0 <= target)
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (P.seg[mid].cum <= target) lo = mid; else hi = mid;
-                }
-                const LaneSeg q = P.seg[lo];
-                const double u = q.len == 0.0 ? 0.0 : (target - q.cum) / q.len;
-                if (u >= 1.0) { x = q.bx; y = q.by; }
-                else { x = q.ax + u * q.ex; y = q.ay + u * q.ey; }
-            }
-            const double X = x - f.x, Y = y - f.y;
-            ah0 = X * f.c + Y * f.s;
-            ah1 = Y * f.c - X * f.s;
+            polyline_point_at(P.seg, s0i, s1i, total, sv.arc + (double)(lane + 1) * spacing, x, y);
+            f.to_frame(x - f.x, y - f.y, ah0, ah1);
         }
     }
 
@@ -955,11 +878,11 @@ static __global__ __launch_bounds__(256) void route_observation_kernel(Params p,
     const double a0 = __shfl(ah0, from, 64), a1 = __shfl(ah1, from, 64);
     if (lane < W) {
         const double v = lane == 0 ? tr0 : lane == 1 ? tr1 : lane == 2 ? tr2 : lane == 3 ? tr3 : lane == 4 ? tr4
-                       : lane == 5 ? rt0 : lane == 6 ? rt1 : lane == 7 ? rt2 : lane == 8 ? rt3 : lane == 9 ? rt4 : lane == 10 ? rt5
-                       : ((lane - SG_RT_NFEAT) & 1) ? a1 : a0;
+                       : lane == 5 ? sv.offset : lane == 6 ? sv.cos_err : lane == 7 ? sv.sin_err : lane == 8 ? sv.arc
+                       : lane == 9 ? left : lane == 10 ? dist : ((lane - SG_RT_NFEAT) & 1) ? a1 : a0;
         row[lane] = v;
     }
-    if (info && lane < SG_RT_NINFO) info[(size_t)o * SG_RT_NINFO + lane] = lane == 0 ? (on_route ? bs : -1) : when;
+    if (info && lane < SG_RT_NINFO) info[(size_t)o * SG_RT_NINFO + lane] = lane == 0 ? best : when;
 }
 #endif // SG_UNIT_OBS
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Is the device code of two builds the same?  Compares the gfx950 code objects embedded in the objects of two build
 directories (make OUT=...): unit by unit byte for byte, and -- for kernels that moved from one unit to another -- kernel by
-kernel (disassembly with addresses relative to the kernel's start, and the register / LDS / scratch figures of the metadata).
+kernel (disassembly with addresses relative to the kernel's start and pc-relative addresses of data objects by the object's name, and
+the register / LDS / scratch figures of the metadata).
 
     python tools/codeobj_diff.py OLD_OBJ_DIR NEW_OBJ_DIR [--moved old_unit:new_unit ...]
 
@@ -44,7 +45,29 @@ def kernels(co):
         res[re.search(r"\.name:\s+(\S+)", k).group(1)] = (g("vgpr_count"), int(re.match(r":\s+(\d+)", k).group(1)), g("sgpr_count"),
                                                            g("private_segment_fixed_size"), g("group_segment_fixed_size"))
     dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
-    out, name, base, body = {}, None, 0, []
+    syms = []  # (address, size, name) of the data objects a kernel can point at
+    for line in subprocess.run([f"{LLVM}/llvm-objdump", "-t", co], capture_output=True, text=True, check=True).stdout.split("\n"):
+        m = re.match(r"^([0-9a-f]+)\s.*\sO\s+\S+\s+([0-9a-f]+)\s+(\S+)$", line)
+        if m:
+            syms.append((int(m.group(1), 16), int(m.group(2), 16), m.group(3)))
+    for line in subprocess.run([f"{LLVM}/llvm-readelf", "-r", co], capture_output=True, text=True, check=True).stdout.split("\n"):
+        m = re.match(r"^([0-9a-f]+)\s+[0-9a-f]+\s+R_AMDGPU_ABS64\s+[0-9a-f]+\s+(\S+) \+ (\d+)$", line)
+        if m:  # a GOT entry: the address of a data object, filled in at load time
+            syms.append((int(m.group(1), 16), 8, "got:%s+%s" % (m.group(2), m.group(3))))
+
+    def pc_relative(line, prev):
+        """`s_getpc_b64 s[n:..]` then `s_add_u32 sn, sn, literal` is the address of a data object outside the kernel, relative to
+        the s_add_u32: it moves whenever a kernel between the two changes size.  The literal becomes the object's name + offset."""
+        g, a = re.match(r"s_getpc_b64 s\[(\d+):", prev), re.match(r"s_add_u32 s(\d+), s(\d+), (0x[0-9a-f]+)\s+//\s*([0-9A-Fa-f]{8,}):", line)
+        if not (g and a and g.group(1) == a.group(1) == a.group(2)):
+            return line
+        target = int(a.group(4), 16) + int(a.group(3), 16)
+        for addr, size, sym in syms:
+            if addr <= target < addr + max(size, 1):
+                return "s_add_u32 s%s, s%s, <%s+%d>  // %s:" % (a.group(1), a.group(1), sym, target - addr, a.group(4))
+        return line
+
+    out, name, base, body, prev = {}, None, 0, [], ""
     for line in dis.split("\n"):
         m = re.match(r"^([0-9a-f]+) <(.+)>:$", line)
         if m:
@@ -54,6 +77,7 @@ def kernels(co):
             continue
         if name is None:
             continue
+        line, prev = pc_relative(line.strip(), prev), line.strip()
         # addresses (the trailing "// 000000001234:" and branch targets "<sym+0x..>") relative to the kernel's start
         line = re.sub(r"//\s*([0-9A-Fa-f]{8,}):", lambda a: "// +%x:" % (int(a.group(1), 16) - base), line)
         body.append(line.strip())
