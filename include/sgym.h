@@ -385,8 +385,8 @@ int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, const int32
 int sg_step_drivers(sg_handle *h, int32_t n_steps, const double *actions, int32_t actions_device);
 
 /* The built-in driver policy: traffic that reacts.  A listed driver follows a path (a polyline) with a Stanley-style steering law
- * and takes its acceleration from the Intelligent Driver Model (IDM) against the nearest box in a straight corridor ahead of it
- * and against the end of its path.  The reference has no such agent (its agents are replay, PID, pedestrian or caller-run); the
+ * and takes its acceleration from the Intelligent Driver Model (IDM) against the nearest box in a corridor ahead of it -- straight
+ * in its heading frame, or, per driver (SG_DP_CORRIDOR), bent along its path -- and against the end of its path.  The reference has no such agent (its agents are replay, PID, pedestrian or caller-run); the
  * device evaluates the policy on the current state, so reactive traffic runs for any number of steps with no host in the loop.
  * Plain fp64, IEEE division and square root, nothing fused.
  * Policy driver j is driver driver[j] of the list of sg_set_drivers, slot so of scenario r, with the parameter row params[j]
@@ -411,7 +411,22 @@ int sg_step_drivers(sg_handle *h, int32_t n_steps, const double *actions, int32_
  *   e is a candidate iff  lat - hw <= (cyo + 0.5*Wo) + HALF  and  lat + hw >= (cyo - 0.5*Wo) - HALF  and  lon + hl > front  and
  *   gap <= REACH (inclusive); a NaN anywhere fails.  The lead is the smallest (gap, slot), the gaps compared as fp64 values (a gap
  *   may be negative; ties, -0.0 against +0.0 included, go to the lower slot);  dv = v - (vxe*c + vye*s).  With no lead: gap = +inf,
- *   dv = +0.0.  The corridor is straight, in the driver's heading frame.
+ *   dv = +0.0.  The corridor is straight, in the driver's heading frame: this is the rule of CORRIDOR == 0.
+ *   the lead with CORRIDOR == 1, the corridor along the path (a driver with no best segment g -- a path of fewer than two points, or
+ *   no finite distance -- uses the straight rule above): the path has n segments; front, left = (cyo + 0.5*Wo) + HALF and
+ *   right = (cyo - 0.5*Wo) - HALF as above.  The window is the segments i with g <= i < n and cum_i <= (s0 + front) + REACH (cum never
+ *   decreases: a contiguous range, which may be empty -- then there is no lead).  For every OTHER slot e of r that is in State.poses,
+ *   with (qx, qy) and (sn, cn) as above: over the window (d2, dx, dy, t) by the point-to-segment rule at (qx, qy), a d2 that is not
+ *   finite skipped, the best segment k the smallest (d2, i); with no k, or len_k == 0, e is no candidate.  Otherwise, with
+ *   (ux, uy) = (ex_k/len_k, ey_k/len_k) and (dx, dy, t) of k:
+ *     offe = ux*dy - uy*dx,  ce = cn*ux + sn*uy,  sne = sn*ux - cn*uy,  se = cum_k + t*len_k,  res = ux*dx + uy*dy
+ *     hl = 0.5*(fabs(Le*ce) + fabs(We*sne)),  hw = 0.5*(fabs(Le*sne) + fabs(We*ce))
+ *     lon = se - s0,  lat = offe - off;   gap = (lon - hl) - front
+ *   e is a candidate iff  lat - hw <= left  and  lat + hw >= right  and  lon + hl > front  and  gap <= REACH  and  fabs(res) <= hl; a
+ *   NaN anywhere fails.  (res: how far the box centre lies beyond the end of its segment, along it.  At an interior projection it is
+ *   rounding noise; the test keeps out a box beyond the end of the window or of the path, or far out in the wedge of a sharp
+ *   corner, whose arclength would be that of the corner.)  The lead is the smallest (gap, slot) as above;
+ *   dv = v - (vxe*ux + vye*uy) with the direction of the lead's segment k.  With no lead: gap = +inf, dv = +0.0.  info[1] stays g.
  *   the acceleration: vr = v / V0, free = 1.0 - (vr*vr)*(vr*vr), root = 2.0*sqrt(A*B), and
  *     idm(g, d):  q = v*T + (v*d)/root;  ss = S0 + (q > 0 ? q : 0.0);  gg = g > GAP_MIN ? g : GAP_MIN;  rr = ss/gg;
  *                 idm = A*(free - rr*rr)
@@ -421,11 +436,11 @@ int sg_step_drivers(sg_handle *h, int32_t n_steps, const double *actions, int32_
  * waits for the work queued on sg_stream(h) first, as sg_set_drivers does.  SG_ERR_STATE before sg_upload or with no driver list.
  * SG_ERR_INVALID: m < 0; a NULL array that is needed; a driver index outside [0, n_drivers) or not strictly ascending; pt_off not
  * starting at 0 or not monotone; a parameter that is NaN; V0, A, B, K_SOFT or GAP_MIN not > 0 or infinite; T, S0, HALF or REACH
- * < 0 (REACH alone may be +inf, T, S0 and HALF may not); K_PSI or K_E infinite; a NaN in pts.  A refused call leaves the previous
+ * < 0 (REACH alone may be +inf, T, S0 and HALF may not); K_PSI or K_E infinite; CORRIDOR neither 0.0 (straight) nor 1.0 (along the path); a NaN in pts.  A refused call leaves the previous
  * policy in place.  sg_set_drivers forgets the policy, whether it replaces or clears the list, and so does sg_upload; sg_reset /
  * sg_reset_scenarios / sg_step / sg_step_drivers keep it, and sg_step_drivers never reads it. */
 enum { SG_DP_V0, SG_DP_T, SG_DP_S0, SG_DP_A, SG_DP_B, SG_DP_HALF, SG_DP_REACH,
-       SG_DP_K_PSI, SG_DP_K_E, SG_DP_K_SOFT, SG_DP_GAP_MIN, SG_DP_NPARAM = 12 };
+       SG_DP_K_PSI, SG_DP_K_E, SG_DP_K_SOFT, SG_DP_GAP_MIN, SG_DP_CORRIDOR, SG_DP_NPARAM = 12 };
 #define SG_DP_NINFO 2
 #define SG_DP_NFEAT 6
 typedef struct sg_driver_policy {
@@ -443,7 +458,10 @@ int sg_set_driver_policy(sg_handle *h, const sg_driver_policy *pol);
  * synchronous, through a scratch of the handle) or DEVICE (queued on sg_stream(h), not waited for), as in sg_entity_status, and a
  * persistent rollout launch that gave up is reported as there.  With no policy set: SG_OK, nothing is written (actions may be NULL
  * then).  SG_ERR_INVALID: actions NULL.  SG_ERR_STATE before sg_upload.  One wavefront per policy driver: lane = path segment, then
- * lane = entity over the scenario's slots in blocks of 64; any scenario width.  Not part of the sg_tick graph. */
+ * lane = entity over the scenario's slots in blocks of 64; any scenario width; with CORRIDOR == 1 every lane walks the window of the
+ * driver's path for its entity, so the time of such a driver grows with the segments inside REACH, not with the path.  One launch;
+ * two when the policy holds drivers of both modes (the rows of either mode go to a kernel of their own, so the straight rows do not
+ * carry the registers of the others).  Not part of the sg_tick graph. */
 int sg_driver_policy_actions(sg_handle *h, double *actions, int32_t *info, double *feat, int32_t outputs_device);
 
 /* sg_step_drivers with the policy in the loop: the same actions [n_steps][n_drivers][2] (HOST, DEVICE or NULL), the same order on

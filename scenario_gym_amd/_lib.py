@@ -19,7 +19,7 @@ TERM_MAX_LENGTH, TERM_COLLISION, TERM_EGO_COLLISION, TERM_EGO_OFF_ROAD = 1, 2, 4
 ST_PRESENT, ST_COLLISION, ST_OFF_ROAD, ST_CORNER_OFF, ST_HIT_VEHICLE, ST_HIT_PEDESTRIAN, ST_HIT_OTHER = 1, 2, 4, 8, 16, 32, 64
 ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
 # SG_DP_* of sg_set_driver_policy: the columns of a parameter row, its width, the widths of the info and feature rows
-(DP_V0, DP_T, DP_S0, DP_A, DP_B, DP_HALF, DP_REACH, DP_K_PSI, DP_K_E, DP_K_SOFT, DP_GAP_MIN) = range(11)
+(DP_V0, DP_T, DP_S0, DP_A, DP_B, DP_HALF, DP_REACH, DP_K_PSI, DP_K_E, DP_K_SOFT, DP_GAP_MIN, DP_CORRIDOR) = range(12)
 DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
 # SG_ROUTE_MAX_AHEAD / SG_RT_* of sg_route_observation: the points ahead, the widths of the info row and of the feature row (+ 2 * n_ahead)
 ROUTE_MAX_AHEAD, RT_NINFO, RT_NFEAT = 16, 2, 11

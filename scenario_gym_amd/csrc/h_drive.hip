@@ -102,6 +102,8 @@ extern "C" int sg_set_driver_policy(sg_handle *h, const sg_driver_policy *pol)
             std::isinf(q[SG_DP_HALF]))
             return fail(h, SG_ERR_INVALID, "%s: T, S0, HALF (finite) and REACH of policy driver %lld must not be negative", who, (long long)j);
         if (std::isinf(q[SG_DP_K_PSI]) || std::isinf(q[SG_DP_K_E])) return fail(h, SG_ERR_INVALID, "%s: K_PSI or K_E of policy driver %lld is infinite", who, (long long)j);
+        if (q[SG_DP_CORRIDOR] != 0.0 && q[SG_DP_CORRIDOR] != 1.0)
+            return fail(h, SG_ERR_INVALID, "%s: CORRIDOR of policy driver %lld is neither 0 (straight) nor 1 (along the path)", who, (long long)j);
     }
     const int64_t n_pts = pol->pt_off[m];
     if (n_pts > 0 && !pol->pts) return fail(h, SG_ERR_INVALID, "%s: null pts", who);
@@ -119,6 +121,7 @@ extern "C" int sg_set_driver_policy(sg_handle *h, const sg_driver_policy *pol)
     if (const int rc = t.upload(h, h->policy, &q.params, &q.seg, &q.driver)) return rc;
     q.total = q.params + (size_t)m * SG_DP_NPARAM;
     q.seg_off = q.driver + m;
+    for (int64_t j = 0; j < m; ++j) q.n_along += pol->params[(size_t)j * SG_DP_NPARAM + SG_DP_CORRIDOR] != 0.0;
     h->pol = q;
     h->n_pol = m;
     return SG_OK;

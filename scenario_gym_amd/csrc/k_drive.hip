@@ -19,7 +19,15 @@ void driver_policy(hipStream_t s, const sg::Params &p, const sg::PolicyIndex &P,
                    const int32_t *row_of, double *actions, int32_t *info, double *feat)
 {
     if (m <= 0) return;
-    sg::driver_policy_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
+    const dim3 grid((unsigned)((m + 3) / 4));
+    if (P.n_along == 0) {
+        sg::driver_policy_kernel<false, false><<<grid, dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
+    } else if (P.n_along == m) {
+        sg::driver_policy_kernel<true, false><<<grid, dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
+    } else { // both modes: each instantiation takes the rows of its own
+        sg::driver_policy_kernel<false, true><<<grid, dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
+        sg::driver_policy_kernel<true, true><<<grid, dim3(256), 0, s>>>(p, P, scen, slot, m, row_of, actions, info, feat);
+    }
 }
 
 void episode(hipStream_t s, const sg::EpisodeArgs &a)

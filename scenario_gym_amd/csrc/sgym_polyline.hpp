@@ -81,8 +81,9 @@ __device__ __forceinline__ void polyline_point_at(const LaneSeg *seg, int s0, in
 
 // segment g seen from the pose (px, py) with heading (s, c): the squared distance to its closest point, the lateral offset (left
 // of the segment's direction positive), cos and sin of the heading against that direction (all three zero for a segment of
-// length zero, which has none), and the arclength of the closest point
-struct SegmentView { double d2, offset, cos_err, sin_err, arc; };
+// length zero, which has none), the arclength of the closest point, the offset along the segment's direction (rounding noise
+// unless the closest point is an end of the segment), and that direction
+struct SegmentView { double d2, offset, cos_err, sin_err, arc, along, ux, uy; };
 __device__ __forceinline__ SegmentView segment_view(const LaneSeg &g, double px, double py, double s, double c)
 {
     double dx, dy, t;
@@ -93,6 +94,9 @@ __device__ __forceinline__ SegmentView segment_view(const LaneSeg &g, double px,
     v.cos_err = c * ux + s * uy;
     v.sin_err = s * ux - c * uy;
     v.arc = g.cum + t * g.len;
+    v.along = ux * dx + uy * dy;
+    v.ux = ux;
+    v.uy = uy;
     return v;
 }
 

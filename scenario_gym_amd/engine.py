@@ -106,14 +106,20 @@ def _social_force(who, params):
     return L.SgSocialForce(**d)
 
 
-def idm_params(v0, T=1.5, s0=2.0, a=1.5, b=2.0, half=0.2, reach=80.0, k_psi=1.0, k_e=0.5, k_soft=1.0, gap_min=0.1):
+CORRIDORS = {"straight": 0.0, "path": 1.0}
+
+
+def idm_params(v0, T=1.5, s0=2.0, a=1.5, b=2.0, half=0.2, reach=80.0, k_psi=1.0, k_e=0.5, k_soft=1.0, gap_min=0.1, corridor="straight"):
     """One parameter row of set_driver_policy ([DP_NPARAM] doubles): desired speed v0, time headway T, standstill gap s0, maximum
     acceleration a and comfortable deceleration b of the Intelligent Driver Model; the corridor's extra half width `half` and its
     length `reach` (inf: no limit); the steering gains on the heading error (k_psi) and on the lateral offset (k_e, softened by
-    k_soft at low speed); the smallest gap the model divides by (gap_min)."""
+    k_soft at low speed); the smallest gap the model divides by (gap_min); where the lead is looked for (corridor): "straight", a
+    corridor in the driver's heading frame, or "path", a corridor bent along the driver's path (SG_DP_CORRIDOR of include/sgym.h)."""
+    if corridor not in CORRIDORS:
+        raise ValueError(f"idm_params: corridor={corridor!r} is none of {sorted(CORRIDORS)}")
     row = np.zeros(L.DP_NPARAM)
-    row[[L.DP_V0, L.DP_T, L.DP_S0, L.DP_A, L.DP_B, L.DP_HALF, L.DP_REACH, L.DP_K_PSI, L.DP_K_E, L.DP_K_SOFT, L.DP_GAP_MIN]] = (
-        v0, T, s0, a, b, half, reach, k_psi, k_e, k_soft, gap_min)
+    row[[L.DP_V0, L.DP_T, L.DP_S0, L.DP_A, L.DP_B, L.DP_HALF, L.DP_REACH, L.DP_K_PSI, L.DP_K_E, L.DP_K_SOFT, L.DP_GAP_MIN, L.DP_CORRIDOR]] = (
+        v0, T, s0, a, b, half, reach, k_psi, k_e, k_soft, gap_min, CORRIDORS[corridor])
     return row
 
 

@@ -52,7 +52,8 @@ class VectorScenarioEnv:
         (trajectory.data[:, 1:3] as given), each with the same VehicleController; needs `drivers`, and no entity may be in both.
         traffic_params: None, keyword arguments of idm_params for every traffic entity (a dict), or one parameter row per traffic
         entity ([n_traffic, DP_NPARAM], environment by environment); v0 defaults to the largest knot-to-knot speed of the
-        entity's recording, floored at 1 m/s.
+        entity's recording, floored at 1 m/s.  {"corridor": "path"} makes the traffic look for its lead in a corridor bent along
+        its recorded trajectory, so it follows a lead round a bend; the default is the straight corridor in its heading frame.
         driver_progress: None, or the weight w of a progress term in the per-driver reward (needs `drivers` and driver_status):
         every driver gets a route -- its own recorded trajectory unless set_routes gave another -- and every step reports in
         `info` driver_route (the rows of sg_route_observation_observers) and driver_progress (the arclength gained along the
