@@ -887,6 +887,60 @@ int sg_route_observation(sg_handle *h, int32_t n_ahead, double spacing, double *
  * (feat may be NULL then). */
 int sg_route_observation_observers(sg_handle *h, int32_t n_ahead, double spacing, double *feat, int32_t *info, int32_t outputs_device);
 
+/* The time to collision (TTC) of the ego of every scenario (n = n_scenarios observers): when its box will first touch another
+ * entity's box if everybody keeps going as they are, for how long the two then overlap, and which face meets first -- the
+ * surrogate-safety measure of scenario analysis and the dense shaping / early-termination signal of a learning driver.  The
+ * reference has no such sensor: its FutureCollisionDetector (sg_future_collision) replays recordings, which is not the future
+ * of a driven entity, and answers with one bit.
+ * Two oriented boxes translate with constant velocities over [0, horizon].  Headings are FROZEN: the yaw rate is ignored, so
+ * for a turning vehicle the answer is that of the tangent motion at this instant.  Two rectangles are disjoint iff one of their
+ * four face normals separates them, so the contact interval is the intersection of four slab intervals.  Plain fp64, IEEE
+ * division, nothing fused.
+ * The observer is slot so of scenario r with pose (xo, yo, ho), (s, c) = sin, cos of ho, velocity (vxo, vyo) -- the x and y
+ * components of State.velocities, as sg_nearest_entities reads them -- and box (Wo, Lo, cxo, cyo) = (width, length, center_x,
+ * center_y).  The candidates are every OTHER slot e of r that is in State.poses (the presence rule of sg_nearest_entities),
+ * with pose (xe, ye, he), (sn, cn) = sin, cos of he, velocity (vxe, vye) and box (We, Le, cxe, cye):
+ *   px = xo + (cxo*c - cyo*s),   py = yo + (cxo*s + cyo*c)          (the box centres, as the driver policy forms them)
+ *   qx = xe + (cxe*cn - cye*sn), qy = ye + (cxe*sn + cye*cn)
+ *   dx = qx - px, dy = qy - py;  wx = vxe - vxo, wy = vye - vyo;  cr = cn*c + sn*s, sr = sn*c - cn*s
+ *   axis 0 (observer, along):  o = dx*c  + dy*s,   l = wx*c  + wy*s,   H = 0.5*Lo + 0.5*(fabs(Le*cr) + fabs(We*sr))
+ *   axis 1 (observer, across): o = dy*c  - dx*s,   l = wy*c  - wx*s,   H = 0.5*Wo + 0.5*(fabs(Le*sr) + fabs(We*cr))
+ *   axis 2 (other, along):     o = dx*cn + dy*sn,  l = wx*cn + wy*sn,  H = 0.5*Le + 0.5*(fabs(Lo*cr) + fabs(Wo*sr))
+ *   axis 3 (other, across):    o = dy*cn - dx*sn,  l = wy*cn - wx*sn,  H = 0.5*We + 0.5*(fabs(Lo*sr) + fabs(Wo*cr))
+ *   slab (o, l, H): l == 0: (tn, tf) = (-inf, +inf) when fabs(o) <= H, else (+inf, -inf); otherwise t1 = (-H - o)/l,
+ *     t2 = (H - o)/l, tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1
+ *   the axes in the order 0 to 3, from tmin = +0.0, tmax = +inf, axis = -1:  if (tn > tmin) { tmin = tn; axis = i; } (the first
+ *     strictly larger value wins: a tie keeps the lower axis);  if (tf < tmax) tmax = tf;
+ *   a pair where any of the twelve o, l, H is NaN is no contact; otherwise e is a contact iff tmin <= tmax && tmin <= horizon
+ *     && tmin < +inf (inclusive; horizon may be +inf)
+ *   if bit e of the observer's SG_F_COLL row (State.collisions()) is set, e is a contact with tmin = +0.0 and axis = -1 whatever
+ *     the slabs say (tmax and the l stay what the rules above gave): the state's own predicate decides the present, as for the
+ *     clearance of sg_entity_status
+ * tmin is never negative and never -0.0.  The threat is the contact with the smallest (tmin, slot).
+ *   feat[o][0]  tmin of the threat; +inf without one
+ *   feat[o][1]  tmax > tmin ? tmax : tmin of the threat, when the overlap ends (possibly +inf); +0.0 without one
+ *   feat[o][2]  l of axis 0 and
+ *   feat[o][3]  l of axis 1 of the threat: its velocity relative to the observer's in the observer's frame; +0.0 without one
+ *   info[o][0]  the threat's slot; -1 without one
+ *   info[o][1]  the number of contacts within the horizon
+ *   info[o][2]  axis of the threat, the face that meets first: 0 the observer's front or rear, 1 its side, 2 and 3 the other
+ *               box's faces; -1 for an overlap that already exists, and without a threat
+ * An observer that is not in State.poses gets info -1, -1, -1 and feat +0.0.
+ * feat: [n][SG_TTC_NFEAT] doubles, required; info: [n][SG_TTC_NINFO], may be NULL.  Every byte of the arrays given is written.
+ * HOST (outputs_device == 0, synchronous, through the observation scratch) or DEVICE (queued on sg_stream(h), not waited for),
+ * as in sg_nearest_entities, and a persistent rollout launch that gave up is reported as in sg_entity_status.
+ * SG_ERR_INVALID: horizon NaN or negative, feat NULL.  SG_ERR_STATE before sg_upload.  A refused call writes nothing and leaves
+ * the handle working.  One wavefront per observer: the scenario's slots go by in blocks of 64, lane = entity; any scenario
+ * width.  Not part of the sg_tick graph, and not read by sg_tick_drivers. */
+#define SG_TTC_NINFO 3
+#define SG_TTC_NFEAT 4
+int sg_time_to_collision(sg_handle *h, double horizon, double *feat, int32_t *info, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_time_to_collision for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_time_to_collision_observers(sg_handle *h, double horizon, double *feat, int32_t *info, int32_t outputs_device);
+
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).
  * actions: [n_scenarios][2] HOST (actions_device = 0) or DEVICE, or NULL for (0, 0).  Asynchronous: the work is queued on

@@ -30,13 +30,14 @@ from .agent import (  # noqa: F401
 from .engine import PackedScenarios, RolloutEngine, idm_params  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
-    RangeScanObservation, RouteObservation, SingleEntityObservation,
+    RangeScanObservation, RouteObservation, SingleEntityObservation, TimeToCollision,
     combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401
 from .gym import BatchedScenarioGym, ScenarioGym  # noqa: F401
 from .metrics import (  # noqa: F401
-    RSS, CollisionMetric, CollisionPointMetric, EgoAvgSpeed, EgoDistanceTravelled, EgoMaxSpeed, Metric, RSSDistances, StateCallback,
+    RSS, CollisionMetric, CollisionPointMetric, EgoAvgSpeed, EgoDistanceTravelled, EgoMaxSpeed, Metric, MinTimeToCollision, RSSDistances,
+    StateCallback,
 )
 from .actions import FixedTAction, ScenarioAction, UpdateStateVariableAction, UserDefinedAction  # noqa: F401
 from .scenario import Scenario  # noqa: F401

@@ -23,6 +23,8 @@ ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
 DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
 # SG_ROUTE_MAX_AHEAD / SG_RT_* of sg_route_observation: the points ahead, the widths of the info row and of the feature row (+ 2 * n_ahead)
 ROUTE_MAX_AHEAD, RT_NINFO, RT_NFEAT = 16, 2, 11
+# SG_TTC_* of sg_time_to_collision: the widths of the info and feature rows
+TTC_NINFO, TTC_NFEAT = 3, 4
 NCTRL = 16
 NOISE_OFF, NOISE_STREAM, NOISE_DEVICE = 0, 1, 2  # sg_set_ped_noise
 PED_SOCIAL_FORCE, PED_RANDOM_WALK = 0, 1         # sg_set_ped_behaviour
@@ -50,6 +52,7 @@ SYMBOLS = (
     "sg_set_driver_policy", "sg_driver_policy_actions", "sg_step_drivers_policy",
     "sg_set_routes", "sg_route_observation", "sg_route_observation_observers",
     "sg_reset_scenarios_device", "sg_tick_drivers",
+    "sg_time_to_collision", "sg_time_to_collision_observers",
 )
 
 
@@ -256,6 +259,8 @@ def load():
     lib.sg_set_routes.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sg_route_observation.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_route_observation_observers.argtypes = lib.sg_route_observation.argtypes
+    lib.sg_time_to_collision.argtypes = [H, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_time_to_collision_observers.argtypes = lib.sg_time_to_collision.argtypes
     lib.sg_reset_scenarios_device.argtypes = [H, C.c_void_p]
     lib.sg_tick_drivers.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(SgEpisodeRules), C.POINTER(SgEpisodeView)]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,5 +1,5 @@
 // h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, and -- each one observe() (sgym_host.hpp) behind its
-// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan and route observations and the episode status of the ego
+// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan, route and time-to-collision observations and the episode status of the ego
 // and of a list of observers; the lists of (scenario, slot) pairs (check_pairs, EntityList::upload); the path tables (PathTable) and
 // the routes.
 #include "sgym_host.hpp"
@@ -376,6 +376,29 @@ extern "C" int sg_entity_status_observers(sg_handle *h, uint32_t *flags, int32_t
 {
     if (!h) return SG_ERR_INVALID;
     return status_call(h, "sg_entity_status_observers", true, flags, info, feat, outputs_device);
+}
+
+// ---- the time to collision (time_to_collision_kernel, sgym_observers.hpp): [SG_TTC_NFEAT] doubles, [SG_TTC_NINFO] ints ------------------
+static int ttc_call(sg_handle *h, const char *who, bool observers, double horizon, double *feat, int32_t *info, int32_t outputs_device)
+{
+    if (!(horizon >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: horizon is negative or NaN", who);
+    return observe(h, who, observers, outputs_device, 0, "feat", {{feat, SG_TTC_NFEAT * sizeof(double)}, {info, SG_TTC_NINFO * sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
+                       sgl::time_to_collision(h->stream, h->p, d_scen, d_slot, n, horizon, static_cast<double *>(d[0]), static_cast<int32_t *>(d[1]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_time_to_collision(sg_handle *h, double horizon, double *feat, int32_t *info, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return ttc_call(h, "sg_time_to_collision", false, horizon, feat, info, outputs_device);
+}
+
+extern "C" int sg_time_to_collision_observers(sg_handle *h, double horizon, double *feat, int32_t *info, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return ttc_call(h, "sg_time_to_collision_observers", true, horizon, feat, info, outputs_device);
 }
 
 // ---- path tables: the polylines of sg_set_routes below and of sg_set_driver_policy (h_drive.hip) -------------------------------------

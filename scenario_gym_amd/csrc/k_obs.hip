@@ -1,6 +1,6 @@
 // k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel /
-// entity_status_kernel / route_observation_kernel: the map, look-ahead, nearest-entity, lane-frame, range-scan and route
-// observations and the episode status of the ego of every scenario or of a list of observers (scenario, slot), any entity of its
+// entity_status_kernel / route_observation_kernel / time_to_collision_kernel: the map, look-ahead, nearest-entity, lane-frame,
+// range-scan, route and time-to-collision observations and the episode status of the ego of every scenario or of a list of observers (scenario, slot), any entity of its
 // scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
@@ -67,5 +67,12 @@ void route_observation(hipStream_t s, const sg::Params &p, const sg::RouteIndex 
 {
     if (n <= 0) return;
     sg::route_observation_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, P, scen, slot, n, n_ahead, spacing, feat, info);
+}
+
+void time_to_collision(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, double *feat,
+                       int32_t *info)
+{
+    if (n <= 0) return;
+    sg::time_to_collision_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, horizon, feat, info);
 }
 } // namespace sgl

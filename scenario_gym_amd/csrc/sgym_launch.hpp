@@ -80,6 +80,11 @@ void entity_status(hipStream_t s, const sg::Params &p, const int32_t *scen, cons
 // feat [n][SG_RT_NFEAT + 2 * n_ahead], info [n][SG_RT_NINFO] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
 void route_observation(hipStream_t s, const sg::Params &p, const sg::RouteIndex &P, const int32_t *scen, const int32_t *slot, int64_t n,
                        int n_ahead, double spacing, double *feat, int32_t *info);
+// time_to_collision_kernel: when the box of observer o < n (the same two lists) first touches another present entity's within `horizon`
+// (which may be +inf) if both keep their velocity and heading.  feat [n][SG_TTC_NFEAT], info [n][SG_TTC_NINFO] (or nullptr), all
+// DEVICE.  One wavefront per observer, any scenario width.
+void time_to_collision(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, double *feat,
+                       int32_t *info);
 // k_drive.hip (sgym_drive.hpp): drive_kernel, one lane per driver d < n: the VehicleController step of entity (scen[d], slot[d]) with
 // actions[d] = (accel, steer) (nullptr: (0, 0)) from its current pose, into row (scen[d] * EP + slot[d]) of ext, the handle's
 // external-pose buffer [NE][6] -- NaN for a driver that is not in the scene; the controller speed in the slot's SG_F_CTRL + 0 cell.

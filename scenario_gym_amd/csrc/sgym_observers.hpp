@@ -1,5 +1,5 @@
-// sgym_observers.hpp -- The map, look-ahead, nearest-entity, lane-frame and range-scan observations and the entity status: one kernel
-// each for the ego of every scenario and for a caller-given list of observers (any entity).
+// sgym_observers.hpp -- The map, look-ahead, nearest-entity, lane-frame, range-scan, route and time-to-collision observations and the
+// entity status: one kernel each for the ego of every scenario and for a caller-given list of observers (any entity).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
 #pragma once
@@ -883,6 +883,108 @@ static __global__ __launch_bounds__(256) void route_observation_kernel(Params p,
         row[lane] = v;
     }
     if (info && lane < SG_RT_NINFO) info[(size_t)o * SG_RT_NINFO + lane] = lane == 0 ? best : when;
+}
+#endif // SG_UNIT_OBS
+
+// ------------------------------------------------------------------------------------------------
+// The time to collision: when an observer's box will touch another one if both keep their velocity and heading, for how long,
+// and which face meets first (no counterpart in the reference, whose FutureCollisionDetector replays recordings and answers
+// with one bit).  The definition is in include/sgym.h at sg_time_to_collision: two rectangles are disjoint iff one of their four
+// face normals separates them, so the contact interval is the intersection of four slab intervals; plain unfused fp64 with
+// IEEE division.
+// ------------------------------------------------------------------------------------------------
+
+// one slab of the definition: the times at which the offset o + t * l enters and leaves [-H, H] (an offset that does not change
+// is inside for every t or for none)
+__device__ __forceinline__ void ttc_slab(double o, double l, double H, double &tn, double &tf)
+{
+    const double t1 = (-H - o) / l, t2 = (H - o) / l;
+    const bool still = l == 0.0, inside = __builtin_fabs(o) <= H, up = t1 < t2;
+    tn = still ? (inside ? -__builtin_inf() : __builtin_inf()) : (up ? t1 : t2);
+    tf = still ? (inside ? __builtin_inf() : -__builtin_inf()) : (up ? t2 : t1);
+}
+
+// Observer o < n: observer_of; feat [n][SG_TTC_NFEAT], info [n][SG_TTC_NINFO] (may be nullptr), every byte written.  One
+// wavefront per observer, four observers per workgroup, no LDS, no barrier, no atomics.  Its box, like its pose, belongs to the
+// observer alone: every lane has it for itself.  The scenario's slots go by in blocks of 64, ascending, lane = entity: presence,
+// the bit of the observer's collision row, sin / cos of the entity's heading, the four slabs; a block in which no lane has a
+// candidate skips them.  Per lane a running (tmin bits, slot) with a strict < and beside it what the outputs need of that pair;
+// wave_min makes the key the wavefront's, and the rest comes from the lane that owns the winning slot by a cross-lane read (it is
+// that lane's own best: the lowest of its slots with the smallest key).  The count is a ballot per block.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void time_to_collision_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n,
+                                                                       double horizon, double *feat, int32_t *info)
+{
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
+    if (!f.present) { // not in State.poses
+        if (lane < SG_TTC_NFEAT) feat[(size_t)o * SG_TTC_NFEAT + lane] = 0.0;
+        if (info && lane < SG_TTC_NINFO) info[(size_t)o * SG_TTC_NINFO + lane] = -1;
+        return;
+    }
+    const ObservedSlot own = observed_slot(p, f, f.slot);
+    const double Wo = own.stat[ST_BW * 64], Lo = own.stat[ST_BL * 64], cxo = own.stat[ST_BCX * 64], cyo = own.stat[ST_BCY * 64];
+    const double px = f.x + (cxo * f.c - cyo * f.s), py = f.y + (cxo * f.s + cyo * f.c);
+    const uint64_t *row = reinterpret_cast<const uint64_t *>(own.dyn) + SG_F_COLL * 64; // word q: row[q * 64] (64 * words >= E)
+
+    uint64_t bk = KEY_NONE;
+    int bs = INDEX_NONE, b_axis = -1, total = 0;
+    double b_until = 0.0, b_l0 = 0.0, b_l1 = 0.0;
+    for (int e0 = 0; e0 < p.E; e0 += 64) {
+        const int e = e0 + lane;
+        const ObservedSlot es = observed_slot(p, f, e);
+        const double *d = es.dyn, *st = es.stat;
+        const bool in = es.other && es.present();
+        if (!sg_any(in)) continue; // (the same in every lane)
+        const bool bit = ((row[(size_t)(e0 >> 6) * 64] >> lane) & 1ull) != 0;
+        double sn, cn;
+        sg_sincos(d[(SG_F_POSE + 3) * 64], sn, cn);
+        const double We = st[ST_BW * 64], Le = st[ST_BL * 64], cxe = st[ST_BCX * 64], cye = st[ST_BCY * 64];
+        const double qx = d[(SG_F_POSE + 0) * 64] + (cxe * cn - cye * sn), qy = d[(SG_F_POSE + 1) * 64] + (cxe * sn + cye * cn);
+        const double dx = qx - px, dy = qy - py, wx = d[(SG_F_VEL + 0) * 64] - f.vx, wy = d[(SG_F_VEL + 1) * 64] - f.vy;
+        const double cr = cn * f.c + sn * f.s, sr = sn * f.c - cn * f.s;
+        const double ao[4] = {dx * f.c + dy * f.s, dy * f.c - dx * f.s, dx * cn + dy * sn, dy * cn - dx * sn};
+        const double al[4] = {wx * f.c + wy * f.s, wy * f.c - wx * f.s, wx * cn + wy * sn, wy * cn - wx * sn};
+        const double aH[4] = {0.5 * Lo + 0.5 * (__builtin_fabs(Le * cr) + __builtin_fabs(We * sr)),
+                              0.5 * Wo + 0.5 * (__builtin_fabs(Le * sr) + __builtin_fabs(We * cr)),
+                              0.5 * Le + 0.5 * (__builtin_fabs(Lo * cr) + __builtin_fabs(Wo * sr)),
+                              0.5 * We + 0.5 * (__builtin_fabs(Lo * sr) + __builtin_fabs(Wo * cr))};
+        double tmin = 0.0, tmax = __builtin_inf();
+        int axis = -1;
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { // (registers: only ever indexed by this unrolled loop)
+            double tn, tf;
+            ttc_slab(ao[i], al[i], aH[i], tn, tf);
+            nan = nan || ao[i] != ao[i] || al[i] != al[i] || aH[i] != aH[i];
+            if (tn > tmin) { tmin = tn; axis = i; }
+            if (tf < tmax) tmax = tf;
+        }
+        const bool meets = !nan && tmin <= tmax && tmin <= horizon && tmin < __builtin_inf();
+        tmin = bit ? 0.0 : tmin;  // the state's own predicate decides the present
+        axis = bit ? -1 : axis;
+        const bool contact = in && (bit || meets);
+        total += __popcll(__ballot(contact));
+        const uint64_t key = contact ? (uint64_t)__double_as_longlong(tmin) : KEY_NONE;
+        const bool take = key < bk; // (ascending slots per lane: the lower slot keeps a tie)
+        bk = take ? key : bk;
+        bs = take ? e : bs;
+        b_until = take ? (tmax > tmin ? tmax : tmin) : b_until;
+        b_l0 = take ? al[0] : b_l0;
+        b_l1 = take ? al[1] : b_l1;
+        b_axis = take ? axis : b_axis;
+    }
+    wave_min(bk, bs);
+    const bool threat = bk != KEY_NONE;
+    const int from = threat ? (bs & 63) : 0; // (the cross-lane reads are the whole wavefront's)
+    const double until = __shfl(b_until, from, 64), l0 = __shfl(b_l0, from, 64), l1 = __shfl(b_l1, from, 64);
+    const int axis = __shfl(b_axis, from, 64);
+    if (lane < SG_TTC_NFEAT) {
+        const double v = lane == 0 ? __longlong_as_double((long long)bk) : lane == 1 ? until : lane == 2 ? l0 : l1;
+        feat[(size_t)o * SG_TTC_NFEAT + lane] = threat ? v : lane == 0 ? __builtin_inf() : 0.0;
+    }
+    if (info && lane < SG_TTC_NINFO) info[(size_t)o * SG_TTC_NINFO + lane] = lane == 1 ? total : !threat ? -1 : lane == 0 ? bs : axis;
 }
 #endif // SG_UNIT_OBS
 

@@ -552,7 +552,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) / time_to_collision_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -723,6 +723,40 @@ class RolloutEngine:
         n = self._n_obs if observers else self.R
         call = self.lib.sg_route_observation_observers if observers else self.lib.sg_route_observation
         return self._observe(call, (n_ahead, float(spacing)), device, ((n, L.RT_NFEAT + 2 * max(n_ahead, 0)), "float64"), ((n, L.RT_NINFO), "int32"))
+
+    def _time_to_collision(self, call, n, horizon, torch_out):
+        return self._observe(call, (float(horizon),), torch_out, ((n, L.TTC_NFEAT), "float64"), ((n, L.TTC_NINFO), "int32"))
+
+    def time_to_collision(self, horizon=float("inf"), torch_out=False):
+        """The time to collision of the ego of every scenario (sg_time_to_collision): when its bounding box first touches the box
+        of another entity that is in the scene, within `horizon` seconds (inclusive; inf: ever), if both keep their velocity and
+        heading (the yaw rate is ignored).  Returns (feat [R, 4] float64, info [R, 3] int32).  feat: the time to the first
+        contact -- 0 for an entity it already collides with, inf when there is none --, the time at which that overlap ends (it
+        may be inf; 0 without a contact), and the threat's velocity relative to the ego's along and across the ego's heading (0
+        without).  info: the threat's slot (-1: none), the number of entities met within the horizon, and the face that meets
+        first -- 0 the ego's front or rear, 1 its side, 2 / 3 the other box's front or rear / side, -1 for an overlap that exists
+        already and without a threat.  An ego that is not in the scene: info -1, feat 0.  torch_out: torch tensors in HBM the
+        kernel writes directly (waited for, as in entity_status)."""
+        return self._time_to_collision(self.lib.sg_time_to_collision, self.R, horizon, torch_out)
+
+    def time_to_collision_observers(self, horizon=float("inf"), torch_out=False):
+        """time_to_collision for every observer of set_observers (sg_time_to_collision_observers): (feat [n, 4], info [n, 3]);
+        empty arrays when no observers are set."""
+        return self._time_to_collision(self.lib.sg_time_to_collision_observers, self._n_obs, horizon, torch_out)
+
+    def time_to_collision_observers_queued(self, feat, info, horizon=float("inf"), ordered=True):
+        """time_to_collision_observers into `feat` [n, 4] float64 and `info` [n, 3] int32, contiguous torch tensors on this GPU,
+        without any host wait: the kernel is queued on the engine's stream behind the work of torch's current stream, and
+        torch's current stream is ordered behind it (ordered=False: the caller orders the two streams itself,
+        ordered_with_torch).  Returns (feat, info)."""
+        import torch
+
+        assert feat.is_cuda and feat.dtype == torch.float64 and feat.is_contiguous() and tuple(feat.shape) == (self._n_obs, L.TTC_NFEAT)
+        assert info.is_cuda and info.dtype == torch.int32 and info.is_contiguous() and tuple(info.shape) == (self._n_obs, L.TTC_NINFO)
+        with self.ordered_with_torch(ordered):
+            self._check(self.lib.sg_time_to_collision_observers(self.h, float(horizon), feat.data_ptr() if feat.numel() else None,
+                                                                info.data_ptr() if info.numel() else None, 1), "sg_time_to_collision_observers")
+        return feat, info
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

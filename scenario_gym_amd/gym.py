@@ -400,20 +400,39 @@ class BatchedScenarioGym:
         RolloutEngine.entity_status gives them for the egos -- one device call with every slot an observer; a padding slot
         reads as an entity that is not in the scene.  The gym's own observer list is put back afterwards."""
         R, E = self.engine.R, self.engine.E
-        kinds = np.asarray(self._packed.kind).reshape(R, E)
-        r, e = np.nonzero(kinds != L.KIND_NONE)
         flags, info, feat = np.full((R, E), L.ST_OFF_ROAD, np.uint32), np.full((R, E, L.ST_NINFO), -1, np.int32), np.zeros((R, E, L.ST_NFEAT))
         self._set_road_networks()
+        r, e, (flags[r, e], info[r, e], feat[r, e]) = self._every_slot(self.engine.entity_status_observers)
+        return flags, info, feat
+
+    def _every_slot(self, call):
+        """(r, e, call()) with every entity slot of the batch -- (r[k], e[k]), padding slots left out -- as the engine's observers
+        for this one call; the gym's own observer list is put back afterwards."""
+        kinds = np.asarray(self._packed.kind).reshape(self.engine.R, self.engine.E)
+        r, e = np.nonzero(kinds != L.KIND_NONE)
         self.engine.set_observers(r, e)
         try:
-            flags[r, e], info[r, e], feat[r, e] = self.engine.entity_status_observers()
+            return r, e, call()
         finally:
             self._observers_sent = 0
             if self._observers:
                 self._send_observers()
             else:
                 self.engine.set_observers([], [])
-        return flags, info, feat
+
+    def _time_to_collision(self, observers: bool, horizon: float):
+        """(feat [n, 4], info [n, 3]) of State.time_to_collision."""
+        call = self.engine.time_to_collision_observers if observers else self.engine.time_to_collision
+        return self._cached(("ttc", observers, horizon), lambda: call(horizon), observers=observers)
+
+    def time_to_collision(self, horizon: float = float("inf")):
+        """State.time_to_collision for every entity slot of the batch: (feat [R, E, 4], info [R, E, 3]) as
+        RolloutEngine.time_to_collision gives them for the egos -- one device call with every slot an observer; a padding slot
+        reads as an entity that is not in the scene.  The gym's own observer list is put back afterwards."""
+        R, E = self.engine.R, self.engine.E
+        feat, info = np.zeros((R, E, L.TTC_NFEAT)), np.full((R, E, L.TTC_NINFO), -1, np.int32)
+        r, e, (feat[r, e], info[r, e]) = self._every_slot(lambda: self.engine.time_to_collision_observers(horizon))
+        return feat, info
 
     def _set_lanes(self):
         """The lane centre lines of every scenario's road network -> the device (behind the networks themselves, whose

@@ -134,6 +134,33 @@ class CollisionPointMetric(_DeviceMetric):
         return list(self.collisions)
 
 
+class MinTimeToCollision(Metric):
+    """The ego's smallest time to collision over the rollout (State.time_to_collision with `horizon`: constant velocities,
+    frozen headings), the surrogate-safety figure of a scenario; no counterpart in the reference, whose RSS metric plays this
+    role.  get_state(): (ttc, t) -- the smallest value over the reset state and the state after every step, and State.t of the
+    first state that had it; (inf, None) when nothing was ever met within the horizon.  Stepped on the host after every device
+    step, like any Metric that is not built in; the value itself is computed on the device."""
+
+    name = "min_time_to_collision"
+
+    def __init__(self, horizon: float = float("inf"), name: Optional[str] = None):
+        super().__init__(name=name)
+        self.horizon = float(horizon)
+        self._min, self._t = float("inf"), None
+
+    def _reset(self, state) -> None:
+        self._min, self._t = float("inf"), None
+        self._step(state)
+
+    def _step(self, state) -> None:
+        obs = state.time_to_collision(horizon=self.horizon)
+        if obs.n_contacts > 0 and obs.ttc < self._min:  # (n_contacts -1: the ego is not in the scene, and its ttc reads 0)
+            self._min, self._t = obs.ttc, float(state.t)
+
+    def get_state(self):
+        return self._min, self._t
+
+
 class StateCallback(ABC):
     """callback.py:9-41: a callback that derives additional information from the state.  `reset(state)` resolves
     `required_callbacks` through `state.get_callback` (ValueError when one is missing) and calls `_reset`; the gym calls the

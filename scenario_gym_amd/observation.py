@@ -138,6 +138,26 @@ class EntityStatus:
     distance: float
 
 
+@dataclass
+class TimeToCollision:
+    """The time to collision of one entity (State.time_to_collision, sg_time_to_collision; no counterpart in the reference, whose
+    FutureCollisionDetector replays recordings): `ttc` -- the time until its box first touches the box of another entity in
+    State.poses if both keep their velocity and heading (the yaw rate is ignored), 0 for an entity it collides with already,
+    inf when nothing is met within the horizon; `until` -- the time at which that overlap ends (it may be inf; 0 without a
+    threat); `rel_velocity` -- the threat's velocity relative to the entity's, along and across the entity's heading (zeros
+    without); `entity` -- the threat, None without; `n_contacts` -- how many entities are met within the horizon (-1 for an
+    entity that is not in State.poses, whose other fields are those of "no threat" with ttc 0); `face` -- which face meets
+    first: 0 the entity's front or rear, 1 its side, 2 / 3 the threat's front or rear / side, -1 for an overlap that exists
+    already and without a threat."""
+
+    ttc: float
+    until: float
+    rel_velocity: np.ndarray
+    entity: Any
+    n_contacts: int
+    face: int
+
+
 def combine_observations(*classes, prefixes: Optional[Sequence[Optional[str]]] = None):
     """observation.py:31-84: a dataclass holding the fields of all `classes` in order.  A field name that an earlier class
     already contributed is skipped -- or, with `prefixes` (one per class), taken as "<prefix>_<name>"; a name that is still

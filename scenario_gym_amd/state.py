@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib as L
 from .entity import Entity
-from .observation import EntityStatus, RouteObservation
+from .observation import EntityStatus, RouteObservation, TimeToCollision
 from .road_network import LAYER_CROSSING, LAYER_IMPENETRABLE, LAYER_INTERSECTION, LAYER_LANE, LAYER_PAVEMENT, LAYER_ROAD
 from .scenario import Scenario
 
@@ -272,6 +272,18 @@ class State:
         entity = self._scenario.ego if entity is None else entity
         present = bool(self._s()["present"][self._i, self._scenario.entities.index(entity)])
         return RouteObservation(entity, present, feat[row].copy(), int(info[row, 0]), int(info[row, 1]))
+
+    def time_to_collision(self, entity: Optional[Entity] = None, horizon: float = float("inf")):
+        """The time to collision of `entity` (any entity of the scenario, default the ego) at the current state, computed on the
+        device (sg_time_to_collision / sg_time_to_collision_observers): a TimeToCollision -- when its box first touches the box
+        of another entity within `horizon` seconds if both keep their velocity and heading, until when, that entity, its
+        relative velocity in the entity's frame, how many entities are met, and the face that meets first."""
+        observers, row = self._sensor_row(entity)
+        feat, info = self._gym._time_to_collision(observers, float(horizon))
+        ents = self._scenario.entities
+        threat = int(info[row, 0])
+        return TimeToCollision(float(feat[row, 0]), float(feat[row, 1]), feat[row, 2:4].copy(), ents[threat] if threat >= 0 else None,
+                               int(info[row, 1]), int(info[row, 2]))
 
     def get_road_info_at_entity(self, e: Entity):
         """state.py:330-338: (class names, objects) of the road geometries whose boundary strictly contains the entity's

@@ -43,7 +43,7 @@ class VectorScenarioEnv:
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
                  drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True,
                  traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None,
-                 driver_progress: Optional[float] = None, device_tick: bool = False):
+                 driver_progress: Optional[float] = None, device_tick: bool = False, driver_ttc: Optional[float] = None):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
         VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
         driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
@@ -66,7 +66,13 @@ class VectorScenarioEnv:
         those of the default path, bit for bit; `info` also carries episode_return [n_drivers] and episode_length [R] (of the
         episode up to and including this tick).  The tensors are views of buffers the engine owns: the next step overwrites
         them.  No `done` bookkeeping is kept on the host: auto_reset=False never resets and never raises -- a finished environment
-        simply goes on stepping, and the caller decides (reset(), engine.reset_scenarios_device)."""
+        simply goes on stepping, and the caller decides (reset(), engine.reset_scenarios_device).
+        driver_ttc: None, or the horizon H in seconds (inf: unbounded) of a time-to-collision row per driver (needs `drivers`):
+        every step reports in `info` driver_ttc [n_drivers, 4] and driver_ttc_info [n_drivers, 3], the rows of
+        sg_time_to_collision_observers for the drivers on the state the returned `obs` describes -- after an auto-reset, unlike
+        driver_flags -- and reset() leaves the same two in `reset_info`.  numpy arrays, or with torch_obs tensors in HBM; with
+        device_tick the call is queued behind the tick and nothing crosses PCIe (an observer list of the caller's own that differs
+        from the driver list is swapped around the call, and each swap waits for the stream).  Not part of driver_reward."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -79,6 +85,10 @@ class VectorScenarioEnv:
         if self.driver_progress is not None and (drivers is None or not self.driver_status):
             raise ValueError("driver_progress: needs a driver list (drivers=...) with driver_status")
 
+        self.driver_ttc = None if driver_ttc is None else float(driver_ttc)
+        if self.driver_ttc is not None and drivers is None:
+            raise ValueError("driver_ttc: needs a driver list (drivers=...)")
+        self.reset_info = {}
         self.device_tick = bool(device_tick)
         if self.device_tick and (drivers is None or not torch_obs):
             raise ValueError("device_tick: needs a driver list (drivers=...) and torch_obs=True")
@@ -181,6 +191,7 @@ class VectorScenarioEnv:
         self.engine.reset()
         self.done[:] = False
         self._route_s0 = None
+        self.reset_info = self._driver_ttc_info()
         return self._observe()
 
     def step(self, actions):
@@ -261,6 +272,7 @@ class VectorScenarioEnv:
             self.done = np.zeros(self.n_envs, bool)
             if self._route_s0 is not None:  # a new episode: its first tick has no previous arclength
                 self._route_s0[1][done[self._drv_env]] = False
+        info.update(self._driver_ttc_info())  # (the state the observation describes: behind the auto-reset)
         return self._observe(), reward, done, info
 
     def _step_device(self, actions):
@@ -281,13 +293,33 @@ class VectorScenarioEnv:
             v = self.engine.tick_drivers(actions.contiguous(), terminal_mask=self._mask, auto_reset=self.auto_reset,
                                          w_progress=self.driver_progress or 0.0, ordered=False)
             obs = self.engine.raster_map_observers_queued(self._dev_obs, self._codes, self.width, self.height, self.n, self.n, ordered=False)
-        info = {"terminal_flags": v["term_flags"], "episode_return": v["ep_return"][:nd], "episode_length": v["ep_length"]}
+            ttc = self._driver_ttc_info(queued=True)
+        info = {"terminal_flags": v["term_flags"], "episode_return": v["ep_return"][:nd], "episode_length": v["ep_length"], **ttc}
         if self.driver_status and nd:
             info.update(driver_flags=v["drv_flags"][:nd], driver_info=v["drv_info"][:nd], driver_feat=v["drv_feat"][:nd],
                         driver_reward=v["drv_reward"][:nd], driver_done=v["drv_done"][:nd].view(torch.bool))
             if self.driver_progress is not None:
                 info.update(driver_route=v["drv_route"][:nd], driver_progress=v["drv_progress"][:nd])
         return obs, v["env_reward"], v["env_done"].view(torch.bool), info
+
+    def _driver_ttc_info(self, queued=False):
+        """driver_ttc=H: {driver_ttc [n_drivers, 4], driver_ttc_info [n_drivers, 3]} of the drivers at the current state
+        (sg_time_to_collision_observers), else {}.  queued (device_tick, inside its ordered_with_torch block): into tensors the
+        environment keeps, on the engine's stream with no host wait."""
+        if self.driver_ttc is None or not self.n_drivers:
+            return {}
+        if queued:
+            if getattr(self, "_dev_ttc", None) is None:
+                import torch
+
+                dev = self._dev_obs.device
+                self._dev_ttc = (torch.empty((self.n_drivers, L.TTC_NFEAT), dtype=torch.float64, device=dev),
+                                 torch.empty((self.n_drivers, L.TTC_NINFO), dtype=torch.int32, device=dev))
+            call = lambda: self.engine.time_to_collision_observers_queued(*self._dev_ttc, self.driver_ttc, ordered=False)  # noqa: E731
+        else:
+            call = lambda: self.engine.time_to_collision_observers(self.driver_ttc, torch_out=self.torch_obs)  # noqa: E731
+        feat, info = self._driver_call(call)
+        return {"driver_ttc": feat, "driver_ttc_info": info}
 
     def _driver_status(self):
         """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays."""
@@ -314,6 +346,17 @@ class VectorScenarioEnv:
         """The episode status of every observer of set_observers at the current state (sg_entity_status_observers): (flags [n],
         info [n, 4], feat [n, 3], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy arrays."""
         out = self.engine.entity_status_observers(torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
+
+    def time_to_collision(self, horizon: float = float("inf")):
+        """The time to collision of the ego of every environment at the current state (sg_time_to_collision): (feat [R, 4], info
+        [R, 3]: RolloutEngine.time_to_collision).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        return self.engine.time_to_collision(horizon, torch_out=self.torch_obs)
+
+    def time_to_collision_observers(self, horizon: float = float("inf")):
+        """The time to collision of every observer of set_observers at the current state (sg_time_to_collision_observers): (feat
+        [n, 4], info [n, 3], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        out = self.engine.time_to_collision_observers(horizon, torch_out=self.torch_obs)
         return tuple(out) + self._observer_index(out[0])
 
     def road_info(self, cap: int = 32):
