@@ -941,6 +941,55 @@ int sg_time_to_collision(sg_handle *h, double horizon, double *feat, int32_t *in
  * (feat may be NULL then). */
 int sg_time_to_collision_observers(sg_handle *h, double horizon, double *feat, int32_t *info, int32_t outputs_device);
 
+/* The surface scan: the static-geometry half of the lidar.  A fan of n_rays beams from the pose point of the ego of every
+ * scenario (n = n_scenarios observers), each reporting, for every requested road layer, the range at which the beam first
+ * changes side of that layer's surface: an observer standing on the layer gets the distance to leaving it, an observer off it
+ * the distance to reaching it.  sg_range_scan sees boxes only (a beam across a kerb comes back with max_range) and
+ * sg_entity_status answers yes / no at five points; the reference has no such sensor.  Plain fp64, nothing fused.
+ * The observer is slot so of scenario r with pose (xo, yo, ho) and (s, c) = sin, cos of ho.  The beams are those of
+ * sg_range_scan: beam b in [0, n_rays) has the angle a_b = angle0 + (double)b * dangle, (sb, cb) = sin, cos of a_b, and the
+ * world direction ux = cb*c - sb*s, uy = sb*c + cb*s.  The point of a beam at parameter t is
+ *   P(t) = (xo + t*ux, yo + t*uy)                                    (one product and one sum per coordinate)
+ * in_l(x, y) is 1 when the point is strictly inside the union of the polygons of scenario r's network that carry the layer
+ * bit l -- what sg_road_info_points(...).layers and the SG_ST_LAYER_SHIFT bits of sg_entity_status answer: a point on a ring
+ * is outside, a NaN or infinite coordinate is in nothing, and on a handle without networks, or in a scenario without one, it
+ * is 0 everywhere.  For layer l = layers[j] and beam b:
+ *   1. s0 = in_l(xo, yo): the pose point itself, not P(0); it always agrees with the status bits
+ *   2. the coarse march: t_k = (double)k * step for k = 1 .. n_steps; k* is the smallest k with in_l(P(t_k)) != s0
+ *   3. without a k* the range is (double)n_steps * step and the beam has no hit
+ *   4. otherwise lo = (double)(k* - 1) * step, hi = (double)k* * step, and n_refine times: mid = (lo + hi) * 0.5; when
+ *      in_l(P(mid)) != s0, hi = mid, else lo = mid
+ *   5. the range is hi, the nearest point KNOWN to lie on the other side; the bracket [lo, hi] around the crossing the march
+ *      found has the width step * 2^-n_refine (until lo and hi are adjacent doubles, where it stays)
+ * The march samples, it does not intersect: a strip of the other side narrower than `step` that lies between two coarse
+ * samples is stepped over, so the caller chooses `step` to suit the narrowest thing it must see.  The scan is defined over the
+ * point predicate and not over polygon edges because the boundary of a union is not the union of the polygons' boundaries:
+ * abutting lanes and roads share or nearly share edges, which are no crossing at all.
+ *   feat[o][j][b]   the range
+ *   flags[o][j][b]  bit 0: the beam hit; bit 1: s0.  May be NULL
+ *   hits[o][j]      the number of beams that hit.  May be NULL
+ * An observer that is not in State.poses gets feat +0.0, flags 0 and hits -1.  Every byte of the arrays given is written.
+ * feat: [n][n_layers][n_rays] doubles, flags: [n][n_layers][n_rays] bytes, hits: [n][n_layers]; HOST (outputs_device == 0,
+ * synchronous, through the observation scratch) or DEVICE (queued on sg_stream(h), not waited for), as in sg_range_scan, and a
+ * persistent rollout launch that gave up is reported as there.  SG_ERR_INVALID: n_layers outside 1..8, a layer that is not
+ * exactly one SG_LAYER_* bit (0, the entity layer, is refused here; duplicates are allowed), n_rays outside
+ * 1..SG_SURF_MAX_RAYS, angle0 or dangle NaN or infinite, step NaN, infinite or not > 0, n_steps outside 1..SG_SURF_MAX_STEPS,
+ * n_refine outside 0..64, feat or layers NULL.  SG_ERR_STATE before sg_upload.  A refused call writes nothing and leaves the
+ * handle working.  One wavefront per observer, lane = beam for the march (one cell lookup per sample answers every layer),
+ * lane = (beam, layer) for the bisections; it reads nothing of the other entities, so any scenario width.  Not part of the
+ * sg_tick graph. */
+#define SG_SURF_MAX_RAYS 1024
+#define SG_SURF_MAX_STEPS 4096
+int sg_surface_scan(sg_handle *h, int32_t n_layers, const int32_t *layers, int32_t n_rays, double angle0, double dangle, double step,
+                    int32_t n_steps, int32_t n_refine, double *feat, uint8_t *flags, int32_t *hits, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_surface_scan for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_surface_scan_observers(sg_handle *h, int32_t n_layers, const int32_t *layers, int32_t n_rays, double angle0, double dangle,
+                              double step, int32_t n_steps, int32_t n_refine, double *feat, uint8_t *flags, int32_t *hits,
+                              int32_t outputs_device);
+
 /* One tick of the external-action loop (integrations/openaigym.py:171-226) for every scenario, as one captured hipGraph:
  * sg_step(h, 1, actions) + sg_terminal_flags + sg_raster_map_device with the given observation geometry (1..8 layers).
  * actions: [n_scenarios][2] HOST (actions_device = 0) or DEVICE, or NULL for (0, 0).  Asynchronous: the work is queued on

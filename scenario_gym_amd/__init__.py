@@ -15,6 +15,7 @@ from .agent import (  # noqa: F401
     RasterizedMapSensor,
     ReplayTrajectoryController,
     Sensor,
+    SurfaceScanSensor,
     VehicleController,
     PedestrianAgent,
     PedestrianBehaviour,
@@ -30,7 +31,7 @@ from .agent import (  # noqa: F401
 from .engine import PackedScenarios, RolloutEngine, idm_params  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
-    RangeScanObservation, RouteObservation, SingleEntityObservation, TimeToCollision,
+    RangeScanObservation, RouteObservation, SingleEntityObservation, SurfaceScanObservation, TimeToCollision,
     combine_observations,
 )
 from .entity import BoundingBox, CatalogEntry, Entity, MiscObject, Pedestrian, Vehicle  # noqa: F401

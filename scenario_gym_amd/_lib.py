@@ -25,6 +25,8 @@ DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
 ROUTE_MAX_AHEAD, RT_NINFO, RT_NFEAT = 16, 2, 11
 # SG_TTC_* of sg_time_to_collision: the widths of the info and feature rows
 TTC_NINFO, TTC_NFEAT = 3, 4
+# SG_SURF_* of sg_surface_scan: the most beams and coarse steps; the bits of its flag bytes (the beam hit, the pose point is on the layer)
+SURF_MAX_RAYS, SURF_MAX_STEPS, SURF_HIT, SURF_INSIDE = 1024, 4096, 1, 2
 NCTRL = 16
 NOISE_OFF, NOISE_STREAM, NOISE_DEVICE = 0, 1, 2  # sg_set_ped_noise
 PED_SOCIAL_FORCE, PED_RANDOM_WALK = 0, 1         # sg_set_ped_behaviour
@@ -53,6 +55,7 @@ SYMBOLS = (
     "sg_set_routes", "sg_route_observation", "sg_route_observation_observers",
     "sg_reset_scenarios_device", "sg_tick_drivers",
     "sg_time_to_collision", "sg_time_to_collision_observers",
+    "sg_surface_scan", "sg_surface_scan_observers",
 )
 
 
@@ -261,6 +264,9 @@ def load():
     lib.sg_route_observation_observers.argtypes = lib.sg_route_observation.argtypes
     lib.sg_time_to_collision.argtypes = [H, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_time_to_collision_observers.argtypes = lib.sg_time_to_collision.argtypes
+    lib.sg_surface_scan.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_surface_scan_observers.argtypes = lib.sg_surface_scan.argtypes
     lib.sg_reset_scenarios_device.argtypes = [H, C.c_void_p]
     lib.sg_tick_drivers.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(SgEpisodeRules), C.POINTER(SgEpisodeView)]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib as L
 from .entity import Entity
 from .observation import (CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, RangeScanObservation,
-                          NearestEntitiesObservation, SingleEntityObservation, combine_observations)
+                          NearestEntitiesObservation, SingleEntityObservation, SurfaceScanObservation, combine_observations)
 from .scenario import Scenario
 
 
@@ -194,6 +194,34 @@ class RangeScanSensor(Sensor):
     def _step(self, state):
         ranges, rates, hit = state.range_scan(self.n_rays, self.angle0, self.dangle, self.max_range, entity=self.entity)
         return RangeScanObservation(self.entity, *state.get_entity_data(self.entity), ranges, rates, hit)
+
+
+class SurfaceScanSensor(Sensor):
+    """A scan of the road surfaces around the sensor's entity (no counterpart in the reference): the beams of RangeScanSensor,
+    each reporting for every layer of `layers` (RasterizedMapSensor's surface layers, "impenetrable", or LAYER_* bits) the
+    distance at which it first changes side of the layer's surface -- how far the road goes in that direction --, found by
+    n_steps samples `step` apart and n_refine bisections, computed on the device for the whole batch: sg_surface_scan for the
+    egos, one sg_surface_scan_observers call for the sensors of all other entities."""
+
+    def __init__(self, entity: Entity, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
+                 step: float = 0.5, n_steps: int = 64, n_refine: int = 16):
+        from .road_network import surface_layer_bits
+
+        super().__init__(entity)
+        self.layers = [layers] if isinstance(layers, (str, int, np.integer)) else list(layers)
+        self.bits = tuple(surface_layer_bits(self.layers))
+        self.n_rays, self.angle0, self.n_steps, self.n_refine = int(n_rays), float(angle0), int(n_steps), int(n_refine)
+        self.step_size = float(step)  # (`step` is the sensor's method)
+        self.dangle = None if dangle is None else float(dangle)
+
+    @property
+    def output_shape(self):
+        return (len(self.bits), self.n_rays)
+
+    def _step(self, state):
+        ranges, hit, inside = state.surface_scan(self.bits, self.n_rays, self.angle0, self.dangle, self.step_size, self.n_steps, self.n_refine,
+                                                 entity=self.entity)
+        return SurfaceScanObservation(self.entity, *state.get_entity_data(self.entity), ranges, hit, inside)
 
 
 class GlobalCollisionDetector(Sensor):

@@ -1,5 +1,5 @@
 // h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, and -- each one observe() (sgym_host.hpp) behind its
-// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan, route and time-to-collision observations and the episode status of the ego
+// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan, route, time-to-collision and surface-scan observations and the episode status of the ego
 // and of a list of observers; the lists of (scenario, slot) pairs (check_pairs, EntityList::upload); the path tables (PathTable) and
 // the routes.
 #include "sgym_host.hpp"
@@ -399,6 +399,48 @@ extern "C" int sg_time_to_collision_observers(sg_handle *h, double horizon, doub
 {
     if (!h) return SG_ERR_INVALID;
     return ttc_call(h, "sg_time_to_collision_observers", true, horizon, feat, info, outputs_device);
+}
+
+// ---- the surface scan (surface_scan_kernel, sgym_observers.hpp): the doubles first -- [n_layers][n_rays] doubles, [n_layers] hit
+// counts, [n_layers][n_rays] flag bytes ------------------------------------------------------------------------------------------
+static int surface_call(sg_handle *h, const char *who, bool observers, int32_t n_layers, const int32_t *layers, int32_t n_rays, double angle0,
+                        double dangle, double step, int32_t n_steps, int32_t n_refine, double *feat, uint8_t *flags, int32_t *hits,
+                        int32_t outputs_device)
+{
+    if (n_layers < 1 || n_layers > 8) return fail(h, SG_ERR_INVALID, "%s: n_layers=%d outside 1..8", who, n_layers);
+    if (!layers) return fail(h, SG_ERR_INVALID, "%s: null layers", who);
+    for (int k = 0; k < n_layers; ++k) {
+        const uint32_t L = (uint32_t)layers[k];
+        if (layers[k] < 1 || L > 255u || (L & (L - 1))) return fail(h, SG_ERR_INVALID, "%s: layers[%d]=%d is not one SG_LAYER_* bit", who, k, layers[k]);
+    }
+    if (n_rays < 1 || n_rays > SG_SURF_MAX_RAYS) return fail(h, SG_ERR_INVALID, "%s: n_rays=%d outside 1..%d", who, n_rays, SG_SURF_MAX_RAYS);
+    if (!std::isfinite(angle0) || !std::isfinite(dangle)) return fail(h, SG_ERR_INVALID, "%s: angle0 or dangle is infinite or NaN", who);
+    if (!std::isfinite(step) || !(step > 0.0)) return fail(h, SG_ERR_INVALID, "%s: step is not positive, infinite or NaN", who);
+    if (n_steps < 1 || n_steps > SG_SURF_MAX_STEPS) return fail(h, SG_ERR_INVALID, "%s: n_steps=%d outside 1..%d", who, n_steps, SG_SURF_MAX_STEPS);
+    if (n_refine < 0 || n_refine > 64) return fail(h, SG_ERR_INVALID, "%s: n_refine=%d outside 0..64", who, n_refine);
+    const size_t cells = (size_t)n_layers * n_rays;
+    return observe(h, who, observers, outputs_device, 0, "feat", {{feat, cells * sizeof(double)}, {hits, (size_t)n_layers * sizeof(int32_t)}, {flags, cells}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
+                       sgl::surface_scan(h->stream, h->p, d_scen, d_slot, n, n_layers, layers, n_rays, angle0, dangle, step, n_steps, n_refine,
+                                         static_cast<double *>(d[0]), static_cast<unsigned char *>(d[2]), static_cast<int32_t *>(d[1]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_surface_scan(sg_handle *h, int32_t n_layers, const int32_t *layers, int32_t n_rays, double angle0, double dangle, double step,
+                               int32_t n_steps, int32_t n_refine, double *feat, uint8_t *flags, int32_t *hits, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return surface_call(h, "sg_surface_scan", false, n_layers, layers, n_rays, angle0, dangle, step, n_steps, n_refine, feat, flags, hits, outputs_device);
+}
+
+extern "C" int sg_surface_scan_observers(sg_handle *h, int32_t n_layers, const int32_t *layers, int32_t n_rays, double angle0, double dangle,
+                                         double step, int32_t n_steps, int32_t n_refine, double *feat, uint8_t *flags, int32_t *hits,
+                                         int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return surface_call(h, "sg_surface_scan_observers", true, n_layers, layers, n_rays, angle0, dangle, step, n_steps, n_refine, feat, flags, hits,
+                        outputs_device);
 }
 
 // ---- path tables: the polylines of sg_set_routes below and of sg_set_driver_policy (h_drive.hip) -------------------------------------

@@ -1,7 +1,7 @@
 // k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel /
-// entity_status_kernel / route_observation_kernel / time_to_collision_kernel: the map, look-ahead, nearest-entity, lane-frame,
-// range-scan, route and time-to-collision observations and the episode status of the ego of every scenario or of a list of observers (scenario, slot), any entity of its
-// scenario (sgym_observers.hpp).
+// entity_status_kernel / route_observation_kernel / time_to_collision_kernel / surface_scan_kernel: the map, look-ahead,
+// nearest-entity, lane-frame, range-scan, route, time-to-collision and surface-scan observations and the episode status of the ego
+// of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
 
@@ -74,5 +74,16 @@ void time_to_collision(hipStream_t s, const sg::Params &p, const int32_t *scen, 
 {
     if (n <= 0) return;
     sg::time_to_collision_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, horizon, feat, info);
+}
+
+void surface_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_layers, const int32_t *layers,
+                  int n_rays, double angle0, double dangle, double step, int n_steps, int n_refine, double *feat, unsigned char *flags,
+                  int32_t *hits)
+{
+    if (n <= 0) return;
+    sg::SurfLayers lay{};
+    for (int k = 0; k < n_layers && k < 8; ++k) lay.bit[k] = (uint32_t)layers[k];
+    sg::surface_scan_kernel<<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(p, scen, slot, n, lay, n_layers, n_rays, angle0, dangle, step, n_steps,
+                                                                                n_refine, feat, flags, hits);
 }
 } // namespace sgl

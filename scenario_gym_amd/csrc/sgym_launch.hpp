@@ -85,6 +85,13 @@ void route_observation(hipStream_t s, const sg::Params &p, const sg::RouteIndex 
 // DEVICE.  One wavefront per observer, any scenario width.
 void time_to_collision(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, double horizon, double *feat,
                        int32_t *info);
+// surface_scan_kernel: n_rays <= SG_SURF_MAX_RAYS beams from observer o < n (the same two lists), the beams of range_scan, each against
+// the surfaces of the n_layers <= 8 road layers `layers` (HOST, one SG_LAYER_* bit each; they travel by value): n_steps samples `step`
+// apart, then n_refine bisections of the step that changed side.  feat [n][n_layers][n_rays], flags [n][n_layers][n_rays] (or
+// nullptr), hits [n][n_layers] (or nullptr), all DEVICE.  One wavefront per observer, any scenario width.
+void surface_scan(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_layers, const int32_t *layers,
+                  int n_rays, double angle0, double dangle, double step, int n_steps, int n_refine, double *feat, unsigned char *flags,
+                  int32_t *hits);
 // k_drive.hip (sgym_drive.hpp): drive_kernel, one lane per driver d < n: the VehicleController step of entity (scen[d], slot[d]) with
 // actions[d] = (accel, steer) (nullptr: (0, 0)) from its current pose, into row (scen[d] * EP + slot[d]) of ext, the handle's
 // external-pose buffer [NE][6] -- NaN for a driver that is not in the scene; the controller speed in the slot's SG_F_CTRL + 0 cell.

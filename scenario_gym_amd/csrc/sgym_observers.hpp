@@ -988,4 +988,121 @@ static __global__ __launch_bounds__(256) void time_to_collision_kernel(Params p,
 }
 #endif // SG_UNIT_OBS
 
+// ------------------------------------------------------------------------------------------------
+// The surface scan: a fan of beams from an observer's pose point, each reporting per requested road layer the range at which
+// it first changes side of that layer's surface (no counterpart in the reference; range_scan_kernel is the half that sees
+// boxes).  The definition is in include/sgym.h at sg_surface_scan: a coarse march of n_steps samples `step` apart over the
+// exact point predicate rn_layers_at (sgym_road.hpp), then n_refine bisections of the step that flipped; plain unfused fp64.
+// ------------------------------------------------------------------------------------------------
+struct SurfLayers {
+    uint32_t bit[8]; // one SG_LAYER_* bit per requested layer, 0 behind the last (by value: no device copy)
+};
+
+// Observer o < n: observer_of; feat [n][n_layers][n_rays], flags [n][n_layers][n_rays] (may be nullptr), hits [n][n_layers]
+// (may be nullptr), every byte written.  One wavefront per observer, four observers per workgroup, no LDS, no barrier, no
+// atomics; nothing of the other entities is read, so the scenario's width does not matter.  The beams go by in blocks of 64:
+//   the march, lane = beam: one rn_layers_at per sample with want = the layers of the list that have not flipped yet on this
+//     beam -- one cell lookup answers all of them, and a layer's answer does not depend on what else is asked for --, the step
+//     of the first flip per list entry in registers (indexed by unrolled loops only); the wavefront leaves the march once no
+//     live lane has a layer left.  The hit counts are ballots, the same in every lane.
+//   the bisections, lane = (beam, list entry): pair q of the block is beam q % nb, entry q / nb (nb: the block's beams), in
+//     rounds of 64 pairs.  A bisection is n_refine dependent lookups, so with few beams and several layers (16 x 3) one round
+//     does what a lane = beam loop over the layers would do in three, and with 64 beams and one layer the two are the same.  A
+//     pair's lane fetches the beam's direction and first-flip step from the beam's lane (cross-lane reads by the whole
+//     wavefront) and writes the pair's outputs itself: consecutive lanes, consecutive beams of one layer.
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+static __global__ __launch_bounds__(256) void surface_scan_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n,
+                                                                  SurfLayers lay, int n_layers, int n_rays, double angle0, double dangle,
+                                                                  double step, int n_steps, int n_refine, double *feat,
+                                                                  unsigned char *flags, int32_t *hits)
+{
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o)) return; // (the whole wavefront, which meets no barrier)
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
+    const size_t row0 = (size_t)o * n_layers;
+    if (!f.present) { // not in State.poses
+        for (size_t i = lane; i < (size_t)n_layers * n_rays; i += 64) {
+            feat[row0 * n_rays + i] = 0.0;
+            if (flags) flags[row0 * n_rays + i] = 0;
+        }
+        if (hits && lane < n_layers) hits[row0 + lane] = -1;
+        return;
+    }
+    uint32_t want = 0u;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) want |= lay.bit[l];
+    RoadIndex RI{};
+    int net = -1;
+    if (p.road) {
+        RI = *p.road;
+        net = RI.net_of_scen[f.r];
+    }
+    const uint32_t s0 = rn_layers_at(RI, net, want, f.x, f.y); // (the pose point itself: the same in every lane)
+    const double reach = (double)n_steps * step;
+    int count[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // (the same in every lane)
+
+    for (int b0 = 0; b0 < n_rays; b0 += 64) {
+        const int b = b0 + lane;
+        double sb, cb;
+        sg_sincos(angle0 + (double)b * dangle, sb, cb);
+        const double ux = cb * f.c - sb * f.s, uy = sb * f.c + cb * f.s;
+
+        // the march
+        int first[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        uint32_t pending = (b < n_rays && net >= 0) ? want : 0u;
+        for (int k = 1; k <= n_steps && sg_any(pending != 0u); ++k) {
+            const double t = (double)k * step;
+            uint32_t flip = 0u;
+            if (pending) flip = (rn_layers_at(RI, net, pending, f.x + t * ux, f.y + t * uy) ^ s0) & pending;
+#pragma unroll
+            for (int l = 0; l < 8; ++l) first[l] = (flip & lay.bit[l]) ? k : first[l];
+            pending &= ~flip;
+        }
+#pragma unroll
+        for (int l = 0; l < 8; ++l) count[l] += __popcll(__ballot(first[l] > 0));
+
+        // the bisections
+        const int nb = min(64, n_rays - b0), pairs = nb * n_layers;
+        for (int q0 = 0; q0 < pairs; q0 += 64) {
+            const int q = q0 + lane;
+            const bool valid = q < pairs;
+            const int l = valid ? q / nb : 0, from = valid ? q - l * nb : 0;
+            const double bux = __shfl(ux, from, 64), buy = __shfl(uy, from, 64);
+            int k = 0;
+            uint32_t bit = 0u;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int km = __shfl(first[m], from, 64);
+                k = m == l ? km : k;
+                bit = m == l ? lay.bit[m] : bit;
+            }
+            const uint32_t side0 = s0 & bit;
+            const bool hit = valid && k > 0;
+            double hi = reach;
+            if (hit) {
+                double lo = (double)(k - 1) * step;
+                hi = (double)k * step;
+                for (int i = 0; i < n_refine; ++i) {
+                    const double mid = (lo + hi) * 0.5;
+                    const bool across = rn_layers_at(RI, net, bit, f.x + mid * bux, f.y + mid * buy) != side0;
+                    hi = across ? mid : hi;
+                    lo = across ? lo : mid;
+                }
+            }
+            if (valid) {
+                const size_t at = (row0 + l) * n_rays + b0 + from; // (consecutive lanes, consecutive beams of one layer)
+                feat[at] = hi;
+                if (flags) flags[at] = (unsigned char)((hit ? 1u : 0u) | (side0 ? 2u : 0u));
+            }
+        }
+    }
+    if (hits && lane < n_layers) {
+        int c = 0;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) c = lane == l ? count[l] : c;
+        hits[row0 + lane] = c;
+    }
+}
+#endif // SG_UNIT_OBS
+
 } // namespace sg

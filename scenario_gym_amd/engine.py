@@ -675,6 +675,36 @@ class RolloutEngine:
         hits [n]); empty arrays when no observers are set."""
         return self._range_scan(self.lib.sg_range_scan_observers, self._n_obs, n_rays, angle0, dangle, max_range, torch_out)
 
+    def _surface_scan(self, call, n, layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out):
+        from .road_network import surface_layer_bits
+
+        lay = np.ascontiguousarray(surface_layer_bits(layers), np.int32)
+        n_rays, nl = int(n_rays), len(lay)
+        dangle = 2.0 * np.pi / max(n_rays, 1) if dangle is None else float(dangle)  # (n_rays < 1 is the library's to refuse)
+        cells = (n, nl, max(n_rays, 0))
+        return self._observe(call, (nl, lay.ctypes.data if nl else None, n_rays, float(angle0), dangle, float(step), int(n_steps), int(n_refine)),
+                             torch_out, (cells, "float64"), (cells, "uint8"), ((n, nl), "int32"))
+
+    def surface_scan(self, layers, n_rays=64, angle0=-np.pi, dangle=None, step=0.5, n_steps=64, n_refine=16, torch_out=False):
+        """The surface scan of the ego of every scenario (sg_surface_scan; set_road_networks comes first): n_rays <= 1024 beams
+        from the ego's pose point, the beams of range_scan, each against the surface of every layer of `layers` (1..8 names of
+        road_network.LAYER_CODES other than "entity", "impenetrable", or LAYER_* bits; duplicates are fine).  Returns (ranges
+        [R, n_layers, n_rays] float64, flags [R, n_layers, n_rays] uint8, hits [R, n_layers] int32): per layer and beam the
+        range at which the beam first changes side of the layer's surface -- from on it, the distance to leaving it; from off
+        it, the distance to reaching it -- found by n_steps <= 4096 samples `step` apart and n_refine <= 64 bisections of the
+        step that changed side (the point reported lies on the other side, the crossing at most step * 2^-n_refine before
+        it; a strip narrower than `step` between two samples is stepped over), n_steps * step without a change; flags:
+        SURF_HIT the beam changed side, SURF_INSIDE the pose point is on the layer; hits: the beams that changed side, -1 for
+        an ego that is not in the scene (ranges and flags 0).  Without a road network every range is n_steps * step.
+        torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
+        return self._surface_scan(self.lib.sg_surface_scan, self.R, layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out)
+
+    def surface_scan_observers(self, layers, n_rays=64, angle0=-np.pi, dangle=None, step=0.5, n_steps=64, n_refine=16, torch_out=False):
+        """surface_scan for every observer of set_observers (sg_surface_scan_observers): (ranges [n, n_layers, n_rays], flags
+        [n, n_layers, n_rays], hits [n, n_layers]); empty arrays when no observers are set."""
+        return self._surface_scan(self.lib.sg_surface_scan_observers, self._n_obs, layers, n_rays, angle0, dangle, step, n_steps, n_refine,
+                                  torch_out)
+
     def _entity_status(self, call, n, torch_out):
         return self._observe(call, (), torch_out, ((n,), "int32" if torch_out else "uint32"), ((n, L.ST_NINFO), "int32"), ((n, L.ST_NFEAT), "float64"))
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RangeScanSensor, RasterizedMapSensor,
-                    _create_agent)
+                    SurfaceScanSensor, _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
 from .packing import pack_policy_drivers, pack_scenarios
@@ -300,7 +300,7 @@ class BatchedScenarioGym:
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
-        # the observers of the batch: every map / look-ahead / nearest-entity / lane sensor of a non-ego entity (inside a CombinedSensor too), so that
+        # the observers of the batch: every map / look-ahead / nearest-entity / lane / range-scan / surface-scan sensor of a non-ego entity (inside a CombinedSensor too), so that
         # one device call per step and sensor configuration serves all of them; a sensor met later joins when it is first stepped
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
 
@@ -314,7 +314,7 @@ class BatchedScenarioGym:
         for i, sc in enumerate(self.scenarios):
             for a in agents[i].values():
                 for s in leaves(getattr(a, "sensor", None)):
-                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor, RangeScanSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor, RangeScanSensor, SurfaceScanSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
                         self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
@@ -389,6 +389,12 @@ class BatchedScenarioGym:
         call = self.engine.range_scan_observers if observers else self.engine.range_scan
         return self._cached(("scan", observers, n_rays, angle0, dangle, max_range), lambda: call(n_rays, angle0, dangle, max_range),
                             observers=observers)
+
+    def _surface_scan(self, observers: bool, bits, n_rays: int, angle0: float, dangle: Optional[float], step: float, n_steps: int, n_refine: int):
+        """(ranges [n, n_layers, n_rays], flags [n, n_layers, n_rays], hits [n, n_layers]) of SurfaceScanSensor; bits: LAYER_* bits."""
+        call = self.engine.surface_scan_observers if observers else self.engine.surface_scan
+        return self._cached(("surf", observers, bits, n_rays, angle0, dangle, step, n_steps, n_refine),
+                            lambda: call(bits, n_rays, angle0, dangle, step, n_steps, n_refine), observers=observers, roads=True)
 
     def _entity_status(self, observers: bool):
         """(flags [n], info [n, 4], feat [n, 3]) of State.entity_status."""

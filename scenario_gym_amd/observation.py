@@ -115,6 +115,18 @@ class RangeScanObservation(SingleEntityObservation):
 
 
 @dataclass
+class SurfaceScanObservation(SingleEntityObservation):
+    """The surface scan (no counterpart in the reference): per layer of the sensor's list and beam of its fan `ranges`
+    [n_layers, n_rays], the distance from the entity's pose point at which the beam first changes side of the layer's surface
+    -- from on it, to leaving it; from off it, to reaching it -- and the sensor's n_steps * step without a change; `hit`
+    [n_layers, n_rays] bool, whether it changed side; `inside` [n_layers] bool, whether the pose point is on the layer."""
+
+    ranges: np.ndarray
+    hit: np.ndarray
+    inside: np.ndarray
+
+
+@dataclass
 class EntityStatus:
     """The episode status of one entity (State.entity_status, sg_entity_status; the reference asks ego_collision and
     ego_off_road of entities[0] alone): `present` -- it is in State.poses; `in_collision` -- its State.collisions() row is not

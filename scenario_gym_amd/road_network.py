@@ -37,6 +37,23 @@ LAYER_CODES = {"entity": 0, "driveable_surface": LAYER_DRIVEABLE, "road": LAYER_
                "lane": LAYER_LANE, "walkable_surface": LAYER_WALKABLE, "pavement": LAYER_PAVEMENT, "crossing": LAYER_CROSSING}
 
 
+def surface_layer_bits(layers):
+    """The layer list of a surface scan (sg_surface_scan) as LAYER_* bits: each entry a name of LAYER_CODES other than "entity",
+    "impenetrable" (the buildings), or a LAYER_* bit as it is.  One name or bit stands for a list of one."""
+    if isinstance(layers, (str, int, np.integer)):
+        layers = [layers]
+    names = dict(LAYER_CODES, impenetrable=LAYER_IMPENETRABLE)
+    del names["entity"]
+    out = []
+    for layer in layers:
+        if isinstance(layer, str):
+            if layer not in names:
+                raise ValueError(f"surface scan: no road layer {layer!r} (one of {sorted(names)})")
+            layer = names[layer]
+        out.append(int(layer))
+    return out
+
+
 def shared_polygon_arrays(scenarios):
     """The arguments of RolloutEngine.set_road_networks for `scenarios`: (polygon_arrays() of every distinct road network -- one
     that several scenarios share, by object identity, once --, per scenario its index into that list, -1 for none)."""

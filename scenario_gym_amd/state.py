@@ -233,6 +233,21 @@ class State:
         ents = self._scenario.entities
         return feat[row, :, 0].copy(), feat[row, :, 1].copy(), [ents[j] if j >= 0 else None for j in slots[row]]
 
+    def surface_scan(self, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
+                     step: float = 0.5, n_steps: int = 64, n_refine: int = 16, entity: Optional[Entity] = None):
+        """SurfaceScanSensor(entity, layers, n_rays, angle0, dangle, step, n_steps, n_refine) at the current state, computed on the
+        device against the scenario's road network: (ranges [n_layers, n_rays], hit [n_layers, n_rays] bool, inside [n_layers]
+        bool) -- per layer (names of RasterizedMapSensor's surface layers, "impenetrable", or LAYER_* bits) and beam from the pose
+        point of `entity` (any entity of the scenario, default the ego), the beams of range_scan, the range at which the beam
+        first changes side of the layer's surface (n_steps * step without a change), whether it did, and whether the pose point
+        is on the layer.  (zeros, False, False) for an entity that is not in `poses`."""
+        from .road_network import surface_layer_bits
+
+        observers, row = self._sensor_row(entity)
+        feat, flags, _ = self._gym._surface_scan(observers, tuple(surface_layer_bits(layers)), int(n_rays), float(angle0),
+                                                 None if dangle is None else float(dangle), float(step), int(n_steps), int(n_refine))
+        return feat[row].copy(), (flags[row] & L.SURF_HIT) != 0, (flags[row, :, 0] & L.SURF_INSIDE) != 0
+
     def entity_status(self, entity: Optional[Entity] = None):
         """The episode status of `entity` (any entity of the scenario, default the ego) at the current state, computed on the
         device (sg_entity_status / sg_entity_status_observers): an EntityStatus -- in the scene, in a collision and with whom,

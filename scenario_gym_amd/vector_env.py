@@ -423,6 +423,21 @@ class VectorScenarioEnv:
         out = self.engine.range_scan_observers(n_rays, angle0, dangle, max_range, torch_out=self.torch_obs)
         return tuple(out) + self._observer_index(out[0])
 
+    def surface_scan(self, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
+                     step: float = 0.5, n_steps: int = 64, n_refine: int = 16):
+        """The surface scan of the ego of every environment at the current state (sg_surface_scan): (ranges
+        [R, n_layers, n_rays], flags [R, n_layers, n_rays] SURF_HIT / SURF_INSIDE, hits [R, n_layers]:
+        RolloutEngine.surface_scan).  torch_obs: torch tensors in HBM; else numpy arrays."""
+        return self.engine.surface_scan(layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out=self.torch_obs)
+
+    def surface_scan_observers(self, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
+                               step: float = 0.5, n_steps: int = 64, n_refine: int = 16):
+        """The surface scan of every observer of set_observers at the current state (sg_surface_scan_observers): (ranges
+        [n, n_layers, n_rays], flags [n, n_layers, n_rays], hits [n, n_layers], env_of_observer [n], slot [n]).  torch_obs:
+        torch tensors in HBM; else numpy arrays."""
+        out = self.engine.surface_scan_observers(layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0])
+
     def _set_lanes(self):
         if not self._lanes_set:
             self.engine.set_lanes(shared_lane_arrays(self.scenarios)[0])
