@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers; sg_entity_status, sg_entity_status_observers; sg_set_driver_policy, sg_driver_policy_actions, sg_step_drivers_policy) */
+#define SG_ABI_VERSION 7 /* 2: sg_scenario_state.last_row_hi (scenarios of up to 512 entities); 3: sg_schedule_info replaces sg_pipeline_info; 4: sg_crowd_walk_stats removed; 5: sg_last_kernel; 6: sg_road_info, sg_road_info_points; 7: sg_set_observers, sg_raster_map_observers, sg_future_collision_observers (added within 7, purely additive: sg_nearest_entities, sg_nearest_entities_observers; sg_set_lanes, sg_lane_observation, sg_lane_observation_observers; sg_range_scan, sg_range_scan_observers; sg_set_drivers, sg_step_drivers; sg_entity_status, sg_entity_status_observers; sg_set_driver_policy, sg_driver_policy_actions, sg_step_drivers_policy; sg_snapshot_create, sg_snapshot_save, sg_snapshot_restore, sg_snapshot_bytes, sg_snapshot_destroy) */
 
 typedef enum {
     SG_OK = 0,
@@ -545,6 +545,48 @@ typedef struct sg_episode_view {
  * SG_ERR_STATE before sg_upload or without a driver list; SG_ERR_INVALID: rules or out NULL, r_step, r_bad or w_progress NaN or
  * infinite.  A refused call queues nothing and leaves state, accounting and *out as they were. */
 int sg_tick_drivers(sg_handle *h, const double *actions, int32_t actions_device, const sg_episode_rules *rules, sg_episode_view *out);
+
+/* Device snapshots: go back to a saved state, every scenario or the masked ones.  The reference has no counterpart (a State is
+ * deep-copied by hand there); planners over the simulator (save, roll candidates, go back), resets to saved situations and
+ * counterfactuals need it, and with sg_tick / sg_tick_drivers the state never leaves the device.
+ * STATE is everything a later call reads of what an earlier call wrote: the entity blocks and sg_scenario_state (noise_pos, the
+ * position in a scenario's noise stream, included), the collision events with the poses kept beside them, the pose record, the poses
+ * of sg_set_external_poses (a driver's pose included), the RSSDistances records when they exist, CollisionMetric.last_timestep and
+ * the twin table of scenarios of more than 512 entities, and the episode accounting of sg_tick_drivers (previous arclength, return,
+ * length).  SETTINGS are not state and are not saved: the timestep, the pedestrian models and noise settings, road networks, lanes,
+ * observers, drivers, policy, routes, tuning.
+ * What "restored" means: after sg_snapshot_restore(h, s, mask, ..), for every scenario r with mask[r] != 0, every later call -- a
+ * step by any entry point and kernel family, every read and observation -- returns for r byte for byte what it would have returned
+ * had it been made right after the sg_snapshot_save (or the create) that last wrote r's rows of s, whatever happened on the handle in
+ * between; scenarios with mask[r] == 0 are untouched, on the handle and in the snapshot.
+ *
+ * sg_snapshot_create: device room for one copy of every state array, then a save of every scenario -- a snapshot never holds an
+ * unsaved row, so a masked restore is always defined.  It allocates and may therefore wait for the device.  Arrays the handle makes
+ * on first use come into being here as that use would make them: the RSSDistances records when sg_set_rss is on (as sg_reset makes
+ * them: the callback runs once on the current state), the episode buffer when a driver list is set, the scratch of scenarios of more
+ * than 512 entities.  Any number of snapshots per handle, independent of each other; the handle owns them, sg_snapshot_destroy (which
+ * waits for sg_stream(h)) or sg_destroy frees them.  sg_snapshot_bytes: the device bytes of one.
+ *
+ * sg_snapshot_save copies the rows of the masked scenarios from the handle into the snapshot, sg_snapshot_restore copies them back.
+ * mask: [n_scenarios] bytes, NULL = every scenario; mask_device == 0: a HOST array, copied before the call returns (the caller's
+ * array is free then); else a DEVICE pointer read in stream order, which must stay as it is until the copy has run (as
+ * sg_reset_scenarios_device reads its mask).  The drivers of a scenario go with their scenario, as in sg_reset_scenarios.
+ * Order: both are queued on sg_stream(h) behind everything earlier calls queued on either stream of the handle, and never wait for
+ * the device: they may stand back to back with sg_step*, sg_tick_drivers, sg_rollout_async and the observation calls.  One kernel
+ * launch per call (plus the copy of a HOST mask).  Not to be called while sg_stream(h) is capturing.  The copy is in place, no
+ * address moves: a captured sg_tick graph and the pointers of sg_state_view / sg_episode_view stay valid across a restore.
+ * Episode accounting that is due to start anew (after sg_reset, sg_set_routes: the next tick would zero it) is zeroed first, by save
+ * and by restore, which a caller cannot tell from the tick doing it.
+ * SG_ERR_INVALID: h, s or out NULL, or a snapshot that is not one of this handle's.  SG_ERR_STATE: before sg_upload; the batch
+ * (sg_upload), the driver list (sg_set_drivers) or sg_set_rss changed since the snapshot was created (the message names which; the
+ * snapshot can then only be destroyed).  A persistent rollout launch that gave up is sticky and reported with its own code and
+ * message, as sg_tick_drivers reports it.  A refused call queues nothing and changes nothing. */
+typedef struct sg_snapshot sg_snapshot; /* opaque, owned by the handle it was created on */
+int sg_snapshot_create(sg_handle *h, sg_snapshot **out);
+int sg_snapshot_save(sg_handle *h, sg_snapshot *s, const uint8_t *mask, int32_t mask_device);
+int sg_snapshot_restore(sg_handle *h, sg_snapshot *s, const uint8_t *mask, int32_t mask_device);
+int sg_snapshot_bytes(sg_handle *h, const sg_snapshot *s, uint64_t *bytes);
+int sg_snapshot_destroy(sg_handle *h, sg_snapshot *s);
 
 /* ScenarioGym.rollout(): reset, then step each scenario while it is not done, at most max_steps
  * (scenario_gym.py:256-267).  The time loop runs inside the kernels: one launch for short runs; long runs of batches with

@@ -56,6 +56,7 @@ SYMBOLS = (
     "sg_reset_scenarios_device", "sg_tick_drivers",
     "sg_time_to_collision", "sg_time_to_collision_observers",
     "sg_surface_scan", "sg_surface_scan_observers",
+    "sg_snapshot_create", "sg_snapshot_save", "sg_snapshot_restore", "sg_snapshot_bytes", "sg_snapshot_destroy",
 )
 
 
@@ -269,6 +270,11 @@ def load():
     lib.sg_surface_scan_observers.argtypes = lib.sg_surface_scan.argtypes
     lib.sg_reset_scenarios_device.argtypes = [H, C.c_void_p]
     lib.sg_tick_drivers.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(SgEpisodeRules), C.POINTER(SgEpisodeView)]
+    lib.sg_snapshot_create.argtypes = [H, C.POINTER(C.c_void_p)]
+    lib.sg_snapshot_save.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_snapshot_restore.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_snapshot_bytes.argtypes = [H, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.sg_snapshot_destroy.argtypes = [H, C.c_void_p]
     lib.sg_debug_trig32.argtypes =[H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ("sg_last_error", "sg_last_kernel", "sg_stream", "sg_version", "sg_group_handle", "sg_group_last_error"):  # (pointers / strings)

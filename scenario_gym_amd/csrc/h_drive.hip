@@ -16,6 +16,7 @@ extern "C" int sg_set_drivers(sg_handle *h, int64_t n, const int32_t *scenario, 
     if (const int rc = check_pairs(h, who, n, scenario, slot, PAIR_EXTERNAL | PAIR_ONCE)) return rc;
     forget_episodes(h); // (the accounting of sg_tick_drivers is per position in the list)
     forget_driver_policy(h); // (its indices are positions in the old list)
+    ++h->drivers_gen;        // (... and so are the accounting rows of a snapshot)
     if (n == 0) {
         h->drivers.n = 0;
         return SG_OK;

@@ -7,13 +7,14 @@ using namespace sgh;
 
 // Lays the buffer out for the current driver list: the accounting at the front (doubles, ints, bytes: one memset zeroes it), then the
 // arrays of the view, the widest element type first so that every array is aligned.  Only a change of the number of drivers moves
-// anything (sg_set_drivers has waited for the stream by then).
-static int episode_layout(sg_handle *h)
+// anything (sg_set_drivers has waited for the stream by then).  The lengths and the prev_ok bytes each end on a multiple of 8, so
+// that no 8-byte word holds cells of two arrays (snapshot_copy_kernel moves such cells as whole words).
+int sgh::episode_layout(sg_handle *h)
 {
     const size_t n = (size_t)h->drivers.n, R = (size_t)h->R;
     if (h->ep_n == h->drivers.n && h->episode.ptr) return SG_OK;
     const auto pad8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
-    const size_t state = pad8(2 * n * sizeof(double) + R * sizeof(int32_t) + n);
+    const size_t state = 2 * n * sizeof(double) + pad8(R * sizeof(int32_t)) + pad8(n);
     const size_t doubles = R + n * (SG_ST_NFEAT + SG_RT_NFEAT + 3), ints = 2 * R + n * (1 + SG_ST_NINFO + SG_RT_NINFO), bytes = 2 * R + n;
     const size_t total = state + doubles * sizeof(double) + ints * sizeof(int32_t) + bytes;
     h->ep_n = -1;
@@ -30,7 +31,9 @@ static int episode_layout(sg_handle *h)
     double *env_reward, *drv_feat, *drv_route;
     uint32_t *term_flags, *drv_flags;
     int32_t *drv_info, *drv_route_info;
-    take(a.prev_s, n); take(a.acc_return, n); take(a.acc_length, R); take(a.prev_ok, n);
+    take(a.prev_s, n); take(a.acc_return, n); take(a.acc_length, R);
+    at = h->episode.as<unsigned char>() + 2 * n * sizeof(double) + pad8(R * sizeof(int32_t));
+    take(a.prev_ok, n);
     at = h->episode.as<unsigned char>() + state;
     take(env_reward, R); take(drv_feat, n * SG_ST_NFEAT); take(drv_route, n * SG_RT_NFEAT);
     take(a.drv_progress, n); take(a.drv_reward, n); take(a.ep_return, n);

@@ -93,6 +93,7 @@ extern "C" int sg_create(const sg_config *cfg, sg_handle **out)
     h->slice_mode = env_int("SG_SLICE", 1);
     h->queue_mode = env_int("SG_QUEUE", 1);
     h->quiet = env_int("SG_QUIET", 1) != 0;
+    h->snap_d2d = env_int("SG_SNAP_D2D", 0); // (tools/snapshot_time.py compares the two)
     // the controller stream carries the serial chain of the table path (control_kernel_fast: 64 wavefronts that every rollout
     // launch waits for): highest stream priority, so that its launches are dispatched ahead of the rollout kernels'
     // (measured: no difference at 4096 x 64, where the launches never queue; SG_CTL_PRIO=0 creates it at the lowest)
@@ -143,6 +144,7 @@ extern "C" int sg_destroy(sg_handle *h)
         }
     }
 #endif
+    free_snapshots(h);
     free_pool(h->static_allocs);
     free_pool(h->state_allocs);
     free_pool(h->road_allocs);

@@ -153,6 +153,7 @@ static void forget_batch(sg_handle *h)
     h->uploaded = false; // (the controller table buffers stay: launch_rollout regrows them when the new batch needs more)
     h->ego_first = true;
     ++h->generation;
+    ++h->upload_gen; // (the snapshots of the previous batch can only be destroyed)
     free_pool(h->slice_allocs);
     h->slice_T = -1;
 }

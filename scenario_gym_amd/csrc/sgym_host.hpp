@@ -1,7 +1,7 @@
 // sgym_host.hpp -- what the host units of libsgym_hip.so share (private: the public side is include/sgym.h).
 // The handle, the error and allocation helpers, and the declarations of the few internal functions that cross unit
 // boundaries (namespace sgh).  The units: sgym_hip.hip (the dispatcher and the stepping entry points), h_handle.hip, h_upload.hip,
-// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_drive.hip, h_episode.hip, h_read.hip, h_group.hip.  None of them holds a
+// h_queue.hip, h_slice.hip, h_wide.hip, h_rss.hip, h_road.hip, h_observe.hip, h_drive.hip, h_episode.hip, h_snapshot.hip, h_read.hip, h_group.hip.  None of them holds a
 // kernel: they launch through sgym_launch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +239,11 @@ struct sg_handle {
     // page-locked staging of sg_read_metrics (the per-scenario state and the event table travel every time metrics are read:
     // 0.5 + up to 6 MB for 4096 scenarios; pageable copies ran at a third of the PCIe rate)
     sgh::GrowBuf pin_sd{sgh::GrowBuf::HOST}, pin_ev{sgh::GrowBuf::HOST};
+
+    // ---- h_snapshot.hip: the snapshots (sg_snapshot_create) ----
+    std::vector<sg_snapshot *> snapshots;              // the ones alive (sg_destroy frees them)
+    uint64_t upload_gen = 0, drivers_gen = 0;          // bumped by sg_upload / sg_set_drivers: a snapshot made before is of no use after
+    int snap_d2d = 0;                                  // env SG_SNAP_D2D=1: a NULL-mask save / restore as one device-to-device copy per array
 };
 
 namespace sgh {
@@ -502,6 +507,9 @@ int check_pairs(sg_handle *h, const char *who, int64_t n, const int32_t *scenari
 // in place without the policy, never written) or null ((0, 0) for every driver)
 int drivers_step(sg_handle *h, int n_steps, const double *actions, int32_t actions_device, bool policy, bool wait_host_copy);
 // ---- h_episode.hip ----
+// the episode buffer laid out for the current driver list (h->ep, h->ep_view, h->ep_state_bytes); a change of the number of drivers
+// moves it and forgets the episodes
+int episode_layout(sg_handle *h);
 int episode_clear_masked(sg_handle *h, const uint8_t *d_mask); // (enqueued; nothing when no episode is in progress)
 // ---- h_queue.hip ----
 int check_queue(sg_handle *h);
@@ -516,6 +524,8 @@ int launch_sliced(sg_handle *h, int n_steps);
 // ---- h_wide.hip ----
 int ensure_wide(sg_handle *h);
 int launch_wide(sg_handle *h, int n_steps, int do_reset, int force, const double *d_actions, bool rss);
+// ---- h_snapshot.hip ----
+void free_snapshots(sg_handle *h); // (sg_destroy; the stream has been waited for)
 // ---- h_rss.hip ----
 int ensure_rss(sg_handle *h, bool *fresh);
 int ensure_rssq(sg_handle *h);

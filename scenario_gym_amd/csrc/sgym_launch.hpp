@@ -12,6 +12,7 @@
 #include "sgym_queue.hpp"
 #include "sgym_policy.hpp"
 #include "sgym_episode.hpp"
+#include "sgym_snapshot.hpp"
 
 namespace sgl {
 
@@ -108,6 +109,9 @@ void driver_policy(hipStream_t s, const sg::Params &p, const sg::PolicyIndex &P,
 // All pointers DEVICE.
 void episode(hipStream_t s, const sg::EpisodeArgs &a);
 void episode_clear(hipStream_t s, const uint8_t *mask, const sg::EpisodeArgs &a);
+// k_snap.hip (sgym_snapshot.hpp): snapshot_copy_kernel, one launch -- the rows of the scenarios with mask[r] != 0 (DEVICE [R]; nullptr:
+// every scenario) of every segment of the table, handle -> snapshot (restore == 0) or back; a capped grid that strides over the chunks
+void snapshot_copy(hipStream_t s, const sg::SnapTable &t, const uint8_t *mask, int restore);
 // k_tab.hip: rollout_kernel_tab<G> / rollout_kernel_tab_planar<G>
 void rollout_tab(int G, bool planar, dim3 grid, hipStream_t s, const sg::Params &p, double timestep, int force, const sg::TabGroups &tg);
 // k_tabq.hip (sgym_queue.hpp): rollout_kernel_tabq<G> / rollout_kernel_tabq_planar<G> -- the table path as one persistent launch

@@ -123,6 +123,58 @@ def idm_params(v0, T=1.5, s0=2.0, a=1.5, b=2.0, half=0.2, reach=80.0, k_psi=1.0,
     return row
 
 
+class Snapshot:
+    """One copy of an engine's state on the device (include/sgym.h, sg_snapshot_*): save() the rows of the masked scenarios into
+    it, restore() them back; every later call then returns for those scenarios what it would have returned right after the save.
+    mask: None (every scenario), a numpy bool / uint8 [R] array (copied before the call returns), or a torch uint8 / bool [R]
+    tensor on the engine's GPU, read in stream order behind torch's current stream (ordered_with_torch) and to be left as it is
+    until the copy has run.  Both calls are queued on the engine's stream and not waited for.  Settings (timestep, networks,
+    observers, drivers, routes, policy) are not state.  After upload, set_drivers or a set_rss toggle a snapshot can only be
+    closed."""
+
+    def __init__(self, engine, handle):
+        self.engine, self._s = engine, handle
+
+    def _call(self, fn, mask):
+        eng = self.engine
+        if self._s is None:
+            raise RuntimeError(f"{fn.__name__}: the snapshot is closed")
+        if mask is None:
+            eng._check(fn(eng.h, self._s, None, 0), fn.__name__)
+        elif hasattr(mask, "data_ptr") and getattr(mask, "is_cuda", False):
+            import torch
+
+            assert mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and mask.numel() == eng.R
+            with eng.ordered_with_torch():
+                eng._check(fn(eng.h, self._s, mask.data_ptr(), 1), fn.__name__)
+        else:
+            m = np.ascontiguousarray(mask).astype(np.uint8, copy=False)
+            assert m.shape == (eng.R,)
+            eng._check(fn(eng.h, self._s, m.ctypes.data, 0), fn.__name__)
+
+    def save(self, mask=None):
+        self._call(self.engine.lib.sg_snapshot_save, mask)
+
+    def restore(self, mask=None):
+        self._call(self.engine.lib.sg_snapshot_restore, mask)
+
+    @property
+    def nbytes(self):
+        n = C.c_uint64()
+        self.engine._check(self.engine.lib.sg_snapshot_bytes(self.engine.h, self._s, C.byref(n)), "sg_snapshot_bytes")
+        return int(n.value)
+
+    def close(self):
+        """Frees the snapshot (waits for the engine's stream); a second call does nothing."""
+        s, self._s = self._s, None
+        eng = self.engine
+        if s is not None and getattr(eng, "h", None):
+            snaps = eng.__dict__.get("_snapshots", [])
+            if self in snaps:
+                snaps.remove(self)
+            eng._check(eng.lib.sg_snapshot_destroy(eng.h, s), "sg_snapshot_destroy")
+
+
 class RolloutEngine:
     """ScenarioGym's step loop for a whole batch, resident on one MI355X."""
 
@@ -288,6 +340,8 @@ class RolloutEngine:
 
     def close(self):
         if getattr(self, "h", None):
+            for snap in list(self.__dict__.get("_snapshots", ())):
+                snap.close()
             self.lib.sg_destroy(self.h)
             self.h = None
 
@@ -415,6 +469,15 @@ class RolloutEngine:
         assert mask.is_cuda and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and mask.numel() == self.R
         with self.ordered_with_torch():
             self._check(self.lib.sg_reset_scenarios_device(self.h, mask.data_ptr()), "sg_reset_scenarios_device")
+
+    def snapshot(self):
+        """A Snapshot of the engine's state as it is now (sg_snapshot_create): every scenario saved.  Allocates, so it may wait
+        for the device; save / restore never do."""
+        s = C.c_void_p()
+        self._check(self.lib.sg_snapshot_create(self.h, C.byref(s)), "sg_snapshot_create")
+        snap = Snapshot(self, s)
+        self.__dict__.setdefault("_snapshots", []).append(snap)
+        return snap
 
     def _stream(self):
         """The engine's stream (sg_stream) as a torch stream: what orders it against torch's streams without a host wait."""

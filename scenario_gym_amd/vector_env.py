@@ -36,6 +36,16 @@ from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
 
 
+class EnvState:
+    """What VectorScenarioEnv.save_state returns: the engine's Snapshot and the environment's host state beside it."""
+
+    def __init__(self, snapshot, done, route_s0):
+        self.snapshot, self.done, self.route_s0 = snapshot, done, route_s0
+
+    def close(self):
+        self.snapshot.close()
+
+
 class VectorScenarioEnv:
     def __init__(self, scenarios: Sequence[Scenario], timestep: float = 0.1,
                  terminal_conditions: Optional[Sequence[str]] = None, layers: Optional[Sequence[str]] = None,
@@ -191,6 +201,34 @@ class VectorScenarioEnv:
         self.engine.reset()
         self.done[:] = False
         self._route_s0 = None
+        self.reset_info = self._driver_ttc_info()
+        return self._observe()
+
+    def save_state(self):
+        """A token of the state of every environment as it is now: an engine Snapshot (sg_snapshot_create: allocates, may wait
+        for the device) and the environment's own per-episode host state, `done` and the previous arclengths of the progress
+        reward.  With device_tick there is no host state.  restore_state(token) goes back to it any number of times;
+        token.close() frees it (close() of the environment does too)."""
+        route = None if self._route_s0 is None else (self._route_s0[0].copy(), self._route_s0[1].copy())
+        return EnvState(self.engine.snapshot(), None if self.device_tick else self.done.copy(), route)
+
+    def restore_state(self, token, mask=None):
+        """Back to the state of save_state for every environment, or for those with mask[i] != 0 (numpy bool / uint8 [R], or with
+        device_tick a torch uint8 / bool tensor on the device, read in stream order): the engine's state (sg_snapshot_restore,
+        queued, not waited for), and on the default path `done` and the previous arclengths of the masked environments and their
+        drivers, nobody else's.  Every later step returns for them what it would have returned right after save_state.  Returns
+        the observation of the restored state as reset() returns it, and leaves reset_info as reset() does."""
+        token.snapshot.restore(mask)
+        if not self.device_tick:
+            m = np.ones(self.n_envs, bool) if mask is None else np.asarray(mask).astype(bool)
+            self.done[m] = token.done[m]
+            if self._drv_env is not None and (token.route_s0 is not None or self._route_s0 is not None):
+                md = m[self._drv_env]
+                if self._route_s0 is None:
+                    self._route_s0 = (np.zeros(self.n_drivers), np.zeros(self.n_drivers, bool))
+                saved = token.route_s0 if token.route_s0 is not None else (np.zeros(self.n_drivers), np.zeros(self.n_drivers, bool))
+                self._route_s0[0][md] = saved[0][md]
+                self._route_s0[1][md] = saved[1][md]
         self.reset_info = self._driver_ttc_info()
         return self._observe()
 

@@ -5,7 +5,8 @@
     from tools.kernel_resources import table                 -> {demangled name: dict(vgpr, agpr, sgpr, lds, scratch)}
 
 (the table kernels of the rollout have to stay within 168 VGPRs -- three wavefronts per SIMD -- and control_kernel within 128:
-tests/test_host_api.py checks it on every build.)
+tests/test_host_api.py checks it on every build.  snapshot_copy_kernel, the copy of sg_snapshot_save / _restore, is listed as
+"sg::snapshot_copy_kernel(sg::SnapTable, ...": 38 VGPRs, no scratch, no LDS; tests/test_snapshot_inventory.py holds it to that.)
 """
 import os
 import re
