@@ -720,6 +720,51 @@ int sg_nearest_entities(sg_handle *h, int32_t k, double radius, double *feat, in
 int sg_nearest_entities_observers(sg_handle *h, int32_t k, double radius, double *feat, int32_t *slots, int32_t *count,
                                   int32_t outputs_device);
 
+/* The pose history: where the ego of every scenario (n = n_scenarios observers) and the k entities nearest to it were at the
+ * last n_samples rows of the pose record, `stride` rows apart, in the ego's CURRENT frame -- the input of vectorised driving
+ * policies and trajectory predictors.  The reference has no such sensor (its State.recorded_poses hands the whole record to
+ * the host).  It reads the record a handle created with record_capacity > 0 keeps on the device: one row of poses and one time
+ * per scenario at reset and behind every step, NaN in all six coordinates of an entity that is not in State.poses, L = rec_rows
+ * rows of scenario r so far; every kind of reset takes L back to 1.  Nothing is stepped and nothing of the record is changed.
+ * For observer o = slot so of scenario r with current pose (xo, yo, ho), (s, c) = sin, cos of ho, and t = State.t of r:
+ *   subjects   subject 0 is the observer itself.  Subjects 1..k are the neighbours sg_nearest_entities_observers(k, radius)
+ *              selects at the current state, by exactly its rule and in its order: the other slots of r that are in
+ *              State.poses with a finite d2 <= radius * radius, ascending (d2, slot).  slots[o][i - 1] and count[o] carry the
+ *              bytes that call would write.  k == 0: the observer's own history alone (slots may be NULL; count is still the
+ *              number of candidates within the radius).
+ *   samples    sample j in [0, n_samples) reads record row rho = L - 1 - j * stride; sample 0 is the current state.
+ *   validity   sample j of subject e is valid iff rho >= 0 and the recorded x of e in row rho is not NaN.
+ * With (X, Y, Hd) the recorded coordinates 0, 1 and 3 of e in row rho, (se, ce) = sin, cos of Hd, dx = X - xo, dy = Y - yo, a
+ * valid sample gives
+ *   feat[o][i][j][0..5]  dx*c + dy*s (along the observer's heading now), dy*c - dx*s (left positive), ce*c + se*s and
+ *                        se*c - ce*s (cos, sin of the heading then relative to the observer's now), t - rec_t[rho] (the age of
+ *                        the sample in seconds; +0.0 for j = 0), 1.0
+ * in plain fp64, unfused, as sg_nearest_entities computes its rows.  An invalid sample is six +0.0, and so is every sample of
+ * a subject row behind the last neighbour.
+ * A STALE record -- rec_rows != n_steps + 1 of r: the record filled up and the scenario went on stepping, so its last row is
+ * not the current state -- gives count -2, slots -1 and all features +0.0 for every observer of r: old rows are never presented
+ * as recent ones.  Otherwise an observer that is not in State.poses gets count -1, slots -1 and all features +0.0, as in
+ * sg_nearest_entities.
+ * Every byte of the outputs given is written.  feat: [n][1 + k][n_samples][6] doubles, slots: [n][k], count: [n], may be NULL;
+ * HOST (outputs_device == 0, synchronous, through the observation scratch) or DEVICE (queued on sg_stream(h), not waited for),
+ * as in sg_nearest_entities, and a persistent rollout launch that gave up is reported as there.  SG_ERR_INVALID: n_samples
+ * outside 1..SG_HIST_MAX_SAMPLES, stride outside 1..SG_HIST_MAX_STRIDE, k outside 0..32, radius NaN or negative, feat NULL.
+ * SG_ERR_STATE: the call needs a pose record -- a handle created with record_capacity == 0 has none --, and before sg_upload.
+ * The record costs record_capacity * 6 * n_scenarios * entity_stride * 8 bytes of device memory, which snapshots copy too.
+ * One wavefront per observer selects as sg_nearest_entities does and walks the (subject, sample) pairs 64 at a time, subject
+ * fastest; scenarios of more than 512 entities take one workgroup per observer.  Not part of the sg_tick graph: queue it
+ * behind sg_tick / sg_tick_drivers with device outputs. */
+#define SG_HIST_MAX_SAMPLES 64
+#define SG_HIST_MAX_STRIDE (1 << 20)
+int sg_pose_history(sg_handle *h, int32_t n_samples, int32_t stride, int32_t k, double radius, double *feat, int32_t *slots,
+                    int32_t *count, int32_t outputs_device);
+
+/* The same for every observer of sg_set_observers (n = their number; duplicates each get their rows).  For the observer
+ * (r, ego of r) the bytes are those of sg_pose_history for scenario r.  With no observers set: SG_OK, nothing is written
+ * (feat may be NULL then). */
+int sg_pose_history_observers(sg_handle *h, int32_t n_samples, int32_t stride, int32_t k, double radius, double *feat,
+                              int32_t *slots, int32_t *count, int32_t outputs_device);
+
 /* The lane centre lines of the networks of sg_set_road_networks, which comes first: its net_of_scenario tells which
  * network a scenario uses.  SG_ERR_STATE before sg_upload or before sg_set_road_networks.  SG_ERR_INVALID: n_networks other
  * than that call's, offsets that do not start at 0 or are not monotone, a successor index outside its network, a NULL array

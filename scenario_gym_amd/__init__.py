@@ -11,6 +11,7 @@ from .agent import (  # noqa: F401
     LaneSensor,
     NearestEntitiesSensor,
     PIDController,
+    PoseHistorySensor,
     RangeScanSensor,
     RasterizedMapSensor,
     ReplayTrajectoryController,
@@ -31,6 +32,7 @@ from .agent import (  # noqa: F401
 from .engine import PackedScenarios, RolloutEngine, idm_params  # noqa: F401
 from .observation import (  # noqa: F401
     CollisionObservation, EntityStatus, FutureCollisionObservation, LaneObservation, MapObservation, NearestEntitiesObservation, Observation,
+    PoseHistoryObservation,
     RangeScanObservation, RouteObservation, SingleEntityObservation, SurfaceScanObservation, TimeToCollision,
     combine_observations,
 )

@@ -23,6 +23,8 @@ ST_LAYER_SHIFT, ST_NINFO, ST_NFEAT = 8, 4, 3
 DP_NPARAM, DP_NINFO, DP_NFEAT = 12, 2, 6
 # SG_ROUTE_MAX_AHEAD / SG_RT_* of sg_route_observation: the points ahead, the widths of the info row and of the feature row (+ 2 * n_ahead)
 ROUTE_MAX_AHEAD, RT_NINFO, RT_NFEAT = 16, 2, 11
+# SG_HIST_* of sg_pose_history: the most samples, the largest stride, the width of a sample's feature row
+HIST_MAX_SAMPLES, HIST_MAX_STRIDE, HIST_NFEAT = 64, 1 << 20, 6
 # SG_TTC_* of sg_time_to_collision: the widths of the info and feature rows
 TTC_NINFO, TTC_NFEAT = 3, 4
 # SG_SURF_* of sg_surface_scan: the most beams and coarse steps; the bits of its flag bytes (the beam hit, the pose point is on the layer)
@@ -47,6 +49,7 @@ SYMBOLS = (
     "sg_group_read_metrics", "sg_group_last_error", "sg_host_alloc", "sg_host_free", "sg_road_info", "sg_road_info_points",
     "sg_set_observers", "sg_raster_map_observers", "sg_future_collision_observers",
     "sg_nearest_entities", "sg_nearest_entities_observers",
+    "sg_pose_history", "sg_pose_history_observers",
     "sg_set_lanes", "sg_lane_observation", "sg_lane_observation_observers",
     "sg_range_scan", "sg_range_scan_observers",
     "sg_set_drivers", "sg_step_drivers",
@@ -248,6 +251,8 @@ def load():
     lib.sg_future_collision_observers.argtypes = [H, C.c_double, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_nearest_entities.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_nearest_entities_observers.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_pose_history.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.sg_pose_history_observers.argtypes = lib.sg_pose_history.argtypes
     lib.sg_set_lanes.argtypes = [H, C.POINTER(SgLanes)]
     lib.sg_lane_observation.argtypes = [H, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib as L
 from .entity import Entity
 from .observation import (CollisionObservation, FutureCollisionObservation, LaneObservation, MapObservation, RangeScanObservation,
-                          NearestEntitiesObservation, SingleEntityObservation, SurfaceScanObservation, combine_observations)
+                          NearestEntitiesObservation, PoseHistoryObservation, SingleEntityObservation, SurfaceScanObservation, combine_observations)
 from .scenario import Scenario
 
 
@@ -155,6 +155,26 @@ class NearestEntitiesSensor(Sensor):
     def _step(self, state):
         neighbours, features = state.nearest_entities(self.k, self.radius, entity=self.entity)
         return NearestEntitiesObservation(self.entity, *state.get_entity_data(self.entity), neighbours, features)
+
+
+class PoseHistorySensor(Sensor):
+    """The input of vectorised driving policies and trajectory predictors (no counterpart in the reference): the last
+    n_samples poses, `stride` steps apart, of the sensor's entity and of the k nearest entities within `radius` of it, in the
+    entity's current frame, computed on the device for the whole batch from the pose record: sg_pose_history for the egos, one
+    sg_pose_history_observers call for the sensors of all other entities.  Needs BatchedScenarioGym(record=True): the record
+    takes (max_steps + 1) * 6 * n_scenarios * entity_stride * 8 bytes of device memory."""
+
+    def __init__(self, entity: Entity, n_samples: int = 8, stride: int = 1, k: int = 0, radius: float = float("inf")):
+        super().__init__(entity)
+        self.n_samples, self.stride, self.k, self.radius = int(n_samples), int(stride), int(k), float(radius)
+
+    @property
+    def output_shape(self):
+        return (1 + self.k, self.n_samples, 6)
+
+    def _step(self, state):
+        history, neighbours, theirs = state.pose_history(self.n_samples, self.stride, self.k, self.radius, entity=self.entity)
+        return PoseHistoryObservation(self.entity, *state.get_entity_data(self.entity), history, neighbours, theirs)
 
 
 class LaneSensor(Sensor):

@@ -1,5 +1,5 @@
 // h_observe.hip -- observations: the RL tick as one graph launch, terminal flags, and -- each one observe() (sgym_host.hpp) behind its
-// argument checks -- map, look-ahead, nearest-entity, lane-frame, range-scan, route, time-to-collision and surface-scan observations and the episode status of the ego
+// argument checks -- map, look-ahead, nearest-entity, pose-history, lane-frame, range-scan, route, time-to-collision and surface-scan observations and the episode status of the ego
 // and of a list of observers; the lists of (scenario, slot) pairs (check_pairs, EntityList::upload); the path tables (PathTable) and
 // the routes.
 #include "sgym_host.hpp"
@@ -291,6 +291,38 @@ extern "C" int sg_nearest_entities_observers(sg_handle *h, int32_t k, double rad
 {
     if (!h) return SG_ERR_INVALID;
     return nearest_call(h, "sg_nearest_entities_observers", true, k, radius, feat, slots, count, outputs_device);
+}
+
+// ---- the pose history (pose_history_kernel, sgym_observers.hpp): [1 + k][n_samples][6] doubles, [k] slots, a count ------------------
+static int history_call(sg_handle *h, const char *who, bool observers, int32_t n_samples, int32_t stride, int32_t k, double radius, double *feat,
+                        int32_t *slots, int32_t *count, int32_t outputs_device)
+{
+    if (n_samples < 1 || n_samples > SG_HIST_MAX_SAMPLES) return fail(h, SG_ERR_INVALID, "%s: n_samples=%d outside 1..%d", who, n_samples, SG_HIST_MAX_SAMPLES);
+    if (stride < 1 || stride > SG_HIST_MAX_STRIDE) return fail(h, SG_ERR_INVALID, "%s: stride=%d outside 1..%d", who, stride, SG_HIST_MAX_STRIDE);
+    if (k < 0 || k > SG_NEAR_MAX_K) return fail(h, SG_ERR_INVALID, "%s: k=%d outside 0..%d", who, k, SG_NEAR_MAX_K);
+    if (!(radius >= 0.0)) return fail(h, SG_ERR_INVALID, "%s: radius is negative or NaN", who);
+    if (h->cfg.record_capacity <= 0) return fail(h, SG_ERR_STATE, "%s: needs a pose record: the handle was created with record_capacity == 0", who);
+    return observe(h, who, observers, outputs_device, 0, "feat",
+                   {{feat, (size_t)(1 + k) * n_samples * 6 * sizeof(double)}, {slots, (size_t)k * sizeof(int32_t)}, {count, sizeof(int32_t)}},
+                   [&](void *const *d, const int32_t *d_scen, const int32_t *d_slot, int64_t n) {
+                       sgl::pose_history(h->stream, h->p, d_scen, d_slot, n, n_samples, stride, k, radius, static_cast<double *>(d[0]),
+                                         static_cast<int32_t *>(d[1]), static_cast<int32_t *>(d[2]));
+                       return hipGetLastError();
+                   });
+}
+
+extern "C" int sg_pose_history(sg_handle *h, int32_t n_samples, int32_t stride, int32_t k, double radius, double *feat, int32_t *slots,
+                               int32_t *count, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return history_call(h, "sg_pose_history", false, n_samples, stride, k, radius, feat, slots, count, outputs_device);
+}
+
+extern "C" int sg_pose_history_observers(sg_handle *h, int32_t n_samples, int32_t stride, int32_t k, double radius, double *feat,
+                                         int32_t *slots, int32_t *count, int32_t outputs_device)
+{
+    if (!h) return SG_ERR_INVALID;
+    return history_call(h, "sg_pose_history_observers", true, n_samples, stride, k, radius, feat, slots, count, outputs_device);
 }
 
 // ---- the lane-frame vector observation (lane_observation_kernel, sgym_observers.hpp): [k][6 + 2 * n_ahead] doubles, [k] lane

@@ -1,6 +1,6 @@
 // k_obs.hip -- map_raster_kernel / look_ahead_kernel / nearest_kernel / lane_observation_kernel / range_scan_kernel /
-// entity_status_kernel / route_observation_kernel / time_to_collision_kernel / surface_scan_kernel: the map, look-ahead,
-// nearest-entity, lane-frame, range-scan, route, time-to-collision and surface-scan observations and the episode status of the ego
+// entity_status_kernel / route_observation_kernel / time_to_collision_kernel / surface_scan_kernel / pose_history_kernel: the map,
+// look-ahead, nearest-entity, lane-frame, range-scan, route, time-to-collision, surface-scan and pose-history observations and the episode status of the ego
 // of every scenario or of a list of observers (scenario, slot), any entity of its scenario (sgym_observers.hpp).
 #define SG_UNIT_OBS
 #include "sgym_launch.hpp"
@@ -38,6 +38,19 @@ void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int3
     else if (p.E > 128) sg::nearest_kernel<4><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
     else if (p.E > 64) sg::nearest_kernel<2><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
     else sg::nearest_kernel<1><<<per_wave, block, 0, s>>>(p, scen, slot, n, k, r2, feat, slots, count);
+}
+
+void pose_history(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_samples, int stride, int k,
+                  double radius, double *feat, int32_t *slots, int32_t *count)
+{
+    if (n <= 0) return;
+    const double r2 = radius * radius; // (+inf for an infinite radius: every finite distance passes)
+    const dim3 per_wave((unsigned)((n + 3) / 4)), block(256);
+    if (p.E > 512) sg::pose_history_kernel<0><<<dim3((unsigned)n), block, 0, s>>>(p, scen, slot, n, n_samples, stride, k, r2, feat, slots, count);
+    else if (p.E > 256) sg::pose_history_kernel<8><<<per_wave, block, 0, s>>>(p, scen, slot, n, n_samples, stride, k, r2, feat, slots, count);
+    else if (p.E > 128) sg::pose_history_kernel<4><<<per_wave, block, 0, s>>>(p, scen, slot, n, n_samples, stride, k, r2, feat, slots, count);
+    else if (p.E > 64) sg::pose_history_kernel<2><<<per_wave, block, 0, s>>>(p, scen, slot, n, n_samples, stride, k, r2, feat, slots, count);
+    else sg::pose_history_kernel<1><<<per_wave, block, 0, s>>>(p, scen, slot, n, n_samples, stride, k, r2, feat, slots, count);
 }
 
 void lane_observation(hipStream_t s, const sg::Params &p, const sg::LaneIndex &L, const int32_t *scen, const int32_t *slot, int64_t n, int k,

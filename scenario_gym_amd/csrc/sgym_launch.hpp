@@ -62,6 +62,11 @@ void look_ahead(hipStream_t s, const sg::Params &p, const int32_t *scen, const i
 // observer for scenarios of at most 512 entities (NB = 1, 2, 4, 8 blocks of 64 slots), one workgroup beyond (NB = 0).
 void nearest(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int k, double radius, double *feat,
              int32_t *slots, int32_t *count);
+// pose_history_kernel<NB>: the last n_samples <= SG_HIST_MAX_SAMPLES rows of the pose record (p.rec_cap > 0), `stride` rows apart, of
+// observer o < n (the same two lists) and of its k <= 32 neighbours of nearest_kernel, in the observer's current frame.  feat
+// [n][1 + k][n_samples][6], slots [n][k] (or nullptr), count [n] (or nullptr), all DEVICE.  The widths of nearest_kernel.
+void pose_history(hipStream_t s, const sg::Params &p, const int32_t *scen, const int32_t *slot, int64_t n, int n_samples, int stride, int k,
+                  double radius, double *feat, int32_t *slots, int32_t *count);
 // lane_observation_kernel: the k <= 8 nearest lane centre lines within `radius` of observer o < n (the same two lists) and
 // n_ahead <= 16 points ahead on each.  feat [n][k][6 + 2 * n_ahead], lanes [n][k] (or nullptr), count [n] (or nullptr), all DEVICE;
 // L: the rows of sg_set_lanes (L.seg == nullptr: none set).  One wavefront per observer.

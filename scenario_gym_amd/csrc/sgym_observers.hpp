@@ -1,4 +1,4 @@
-// sgym_observers.hpp -- The map, look-ahead, nearest-entity, lane-frame, range-scan, route and time-to-collision observations and the
+// sgym_observers.hpp -- The map, look-ahead, nearest-entity, lane-frame, range-scan, route, time-to-collision, surface-scan and pose-history observations and the
 // entity status: one kernel each for the ego of every scenario and for a caller-given list of observers (any entity).
 // Part of the gfx950 device code of the batched rollout engine; included by sgym_device.hpp (in order: every part builds on
 // the ones before it), never on its own.
@@ -363,36 +363,31 @@ __device__ __forceinline__ void near_store(const Params &p, const Observer &f, i
 // slots per lane do not fit registers; the rows come from the caches).  The <= 4 * k finalists go through LDS to wavefront 0,
 // which selects among them as the narrow path does.
 #ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+// The selection of nearest_kernel<NB> below, which pose_history_kernel<NB> shares: lane j returns the slot of neighbour j of the
+// present observer f (-1 behind the last), `total` the candidates within the radius.  NB == 0: every wavefront of the workgroup
+// calls it (it holds a barrier); the answers are wavefront 0's alone, the others return -1.
 template <int NB>
-static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n, int k,
-                                                             double r2, double *feat, int32_t *slots, int32_t *count)
+__device__ __forceinline__ int near_neighbours(const Params &p, const Observer &f, int k, double r2, int lane, int w, int &total)
 {
-    int lane; int64_t o;
-    if (!wave_item(n, lane, o, NB == 0)) return; // (NB > 0: the whole wavefront, which meets no barrier)
-    const int w = wave_index();
-    const Observer f = observer_of(p, obs_scen, obs_slot, o);
-    if (!f.present) { // (the whole workgroup on the wide path)
-        if (NB || w == 0) near_store(p, f, o, k, lane, -1, -1, feat, slots, count);
-        return;
-    }
     if constexpr (NB > 0) {
         uint64_t key[NB];
-        int slot[NB], total = 0;
+        int slot[NB];
+        total = 0;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             slot[j] = lane + 64 * j;
             key[j] = near_key(p, f, slot[j], r2);
             total += __popcll(__ballot(key[j] != KEY_NONE));
         }
-        const int nb = near_select<NB>(key, slot, k, lane);
-        near_store(p, f, o, k, lane, nb, total, feat, slots, count);
+        return near_select<NB>(key, slot, k, lane);
     } else {
         __shared__ uint64_t fin_key[4 * SG_NEAR_MAX_K];
         __shared__ int fin_slot[4 * SG_NEAR_MAX_K];
         __shared__ int fin_total[4];
         const int n_blocks = (p.E + 63) >> 6;
         uint64_t last_key = 0, my_key = KEY_NONE;
-        int last_slot = -1, my_slot = INDEX_NONE, total = 0;
+        int last_slot = -1, my_slot = INDEX_NONE;
+        total = 0;
         for (int j = 0; j < k; ++j) {
             uint64_t bk = KEY_NONE;
             int bs = INDEX_NONE;
@@ -413,12 +408,30 @@ static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int
         if (lane < SG_NEAR_MAX_K) { fin_key[w * SG_NEAR_MAX_K + lane] = my_key; fin_slot[w * SG_NEAR_MAX_K + lane] = my_slot; }
         if (lane == 0) fin_total[w] = total;
         __syncthreads();
-        if (w != 0) return;
+        if (w != 0) return -1;
         uint64_t key[2] = {fin_key[lane], fin_key[lane + 64]};
         const int slot[2] = {fin_slot[lane], fin_slot[lane + 64]};
-        const int nb = near_select<2>(key, slot, k, lane);
-        near_store(p, f, o, k, lane, nb, fin_total[0] + fin_total[1] + fin_total[2] + fin_total[3], feat, slots, count);
+        total = fin_total[0] + fin_total[1] + fin_total[2] + fin_total[3];
+        return near_select<2>(key, slot, k, lane);
     }
+}
+
+template <int NB>
+static __global__ __launch_bounds__(256) void nearest_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n, int k,
+                                                             double r2, double *feat, int32_t *slots, int32_t *count)
+{
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o, NB == 0)) return; // (NB > 0: the whole wavefront, which meets no barrier)
+    const int w = wave_index();
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
+    if (!f.present) { // (the whole workgroup on the wide path)
+        if (NB || w == 0) near_store(p, f, o, k, lane, -1, -1, feat, slots, count);
+        return;
+    }
+    int total;
+    const int nb = near_neighbours<NB>(p, f, k, r2, lane, w, total);
+    if (NB == 0 && w != 0) return;
+    near_store(p, f, o, k, lane, nb, total, feat, slots, count);
 }
 #endif // SG_UNIT_OBS
 
@@ -1101,6 +1114,89 @@ static __global__ __launch_bounds__(256) void surface_scan_kernel(Params p, cons
 #pragma unroll
         for (int l = 0; l < 8; ++l) c = lane == l ? count[l] : c;
         hits[row0 + lane] = c;
+    }
+}
+#endif // SG_UNIT_OBS
+
+// ------------------------------------------------------------------------------------------------
+// The pose history: where an observer and the k entities nearest to it were at the last n_samples record rows, `stride` rows
+// apart, in the observer's CURRENT frame (no counterpart in the reference, whose State.recorded_poses hands the whole record to
+// the host).  The definition is in include/sgym.h at sg_pose_history: the neighbours are those of nearest_kernel at the current
+// state (near_neighbours), the rows come from the pose record the stepping kernels append to (p.rec_pose, p.rec_t; row
+// rec_rows - 1 is the current state), plain unfused fp64 as near_store computes its rows.  (SG_HIST_MAX_SAMPLES,
+// SG_HIST_MAX_STRIDE: include/sgym.h.)
+// ------------------------------------------------------------------------------------------------
+#ifdef SG_UNIT_OBS // (emitted by the one object that launches it: csrc/Makefile, sgym_launch.hpp)
+// the subject slots of the wide path: neighbour i of the workgroup's observer at [i - 1]
+__device__ __forceinline__ int *hist_subjects()
+{
+    __shared__ int subject[SG_NEAR_MAX_K];
+    return subject;
+}
+
+// Observer o < n: observer_of.  feat [n][1 + k][n_samples][6] fp64, slots [n][k] (may be nullptr), count [n] (may be nullptr),
+// every byte written.  0 <= k <= 32, 1 <= n_samples <= 64, stride >= 1.  Subject 0 is the observer, subject i >= 1 neighbour
+// i - 1 of near_neighbours.  count: the candidates within the radius; -2 for a stale record (rec_rows != n_steps + 1: the record
+// filled up and the scenario went on stepping), else -1 for an observer that is not present; both with slots -1 and zero rows.
+// NB > 0 (scenarios of at most NB * 64 <= 512 entities): one wavefront per observer, four observers per workgroup, no LDS, no
+// barrier.  After the selection lane i - 1 holds neighbour i; the (subject, sample) pairs go by 64 at a time, pair q = sample
+// q / (1 + k) of subject q % (1 + k) -- subject fastest: for one row and coordinate the slots of a scenario lie within EP * 8
+// bytes, so the 64 loads of a plane touch the few cache lines of 64 / (1 + k) rows -- and a lane fetches its subject's slot from
+// the lane that holds it (a cross-lane read by the whole wavefront).  Per pair three 8-byte loads (the x, y and heading planes
+// of the row), the row's time, one sg_sincos, six stores.  Row offsets are 64-bit: rec_cap * 6 * R * EP exceeds 2^31.
+// NB == 0 (the wide path): one workgroup per observer; wavefront 0's neighbours go through LDS and all 256 threads walk the pairs.
+template <int NB>
+static __global__ __launch_bounds__(256) void pose_history_kernel(Params p, const int32_t *obs_scen, const int32_t *obs_slot, int64_t n,
+                                                                  int n_samples, int stride, int k, double r2, double *feat, int32_t *slots,
+                                                                  int32_t *count)
+{
+    int lane; int64_t o;
+    if (!wave_item(n, lane, o, NB == 0)) return; // (NB > 0: the whole wavefront, which meets no barrier)
+    const int w = wave_index();
+    const Observer f = observer_of(p, obs_scen, obs_slot, o);
+    const sg_scenario_state &sd = p.sdyn[f.r];
+    const double t = sd.t;
+    const int L = sd.rec_rows;
+    const int status = L != sd.n_steps + 1 ? -2 : f.present ? 0 : -1; // (the same in every lane; on the wide path in the whole workgroup)
+    int nb = -1, total = status;
+    if (status == 0) nb = near_neighbours<NB>(p, f, max(k, 1), r2, lane, w, total); // (k == 0: the count alone)
+    if (NB || w == 0) {
+        if (lane == 0 && count) count[o] = total;
+        if (lane < k && slots) slots[(size_t)o * k + lane] = nb;
+    }
+    if constexpr (NB == 0) {
+        if (w == 0 && lane < SG_NEAR_MAX_K) hist_subjects()[lane] = nb;
+        __syncthreads();
+    }
+    const int S = 1 + k, pairs = S * n_samples;
+    const int step = NB ? 64 : 256, me = NB ? lane : (int)threadIdx.x;
+    const size_t plane = (size_t)p.R * p.EP;
+    const double *rec = p.rec_pose + (size_t)f.r * p.EP;
+    double *out = feat + (size_t)o * pairs * 6;
+    for (int q0 = 0; q0 < pairs; q0 += step) { // (uniform trip count: the cross-lane read is the whole wavefront's)
+        const int q = q0 + me, j = q / S, i = q - j * S;
+        int e;
+        if constexpr (NB > 0) e = __shfl(nb, max(i - 1, 0), 64);
+        else e = hist_subjects()[max(i - 1, 0)];
+        e = i == 0 ? f.slot : e;
+        if (q >= pairs) continue;
+        const int rho = L - 1 - j * stride; // (j * stride < 2^26)
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (status == 0 && e >= 0 && rho >= 0 && rho < p.rec_cap) {
+            const double *row = rec + (size_t)rho * 6 * plane + e;
+            const double X = row[0], Y = row[plane], Hd = row[3 * plane], tr = p.rec_t[(size_t)rho * p.R + f.r];
+            if (X == X) { // (an absent entity's row is NaN in all six coordinates)
+                double se, ce;
+                sg_sincos(Hd, se, ce);
+                f.to_frame(X - f.x, Y - f.y, v[0], v[1]);
+                f.to_frame(ce, se, v[2], v[3]);
+                v[4] = j == 0 ? 0.0 : t - tr;
+                v[5] = 1.0;
+            }
+        }
+        double *dst = out + ((size_t)i * n_samples + j) * 6; // (48 bytes per lane)
+#pragma unroll
+        for (int m = 0; m < 6; ++m) dst[m] = v[m];
     }
 }
 #endif // SG_UNIT_OBS

@@ -615,7 +615,7 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) / time_to_collision_observers -- observer k is entity slot
+        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / pose_history_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) / time_to_collision_observers -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -671,6 +671,48 @@ class RolloutEngine:
         """nearest_entities for every observer of set_observers (sg_nearest_entities_observers): (feat [n, k, 8], slots [n, k],
         count [n]); empty arrays when no observers are set."""
         return self._nearest(self.lib.sg_nearest_entities_observers, self._n_obs, k, radius, torch_out)
+
+    def _pose_history(self, call, n, n_samples, stride, k, radius, torch_out):
+        H, k = int(n_samples), int(k)
+        return self._observe(call, (H, int(stride), k, float(radius)), torch_out, ((n, 1 + max(k, 0), max(H, 0), L.HIST_NFEAT), "float64"),
+                             ((n, max(k, 0)), "int32"), ((n,), "int32"))
+
+    def pose_history(self, n_samples, stride=1, k=0, radius=float("inf"), torch_out=False):
+        """The pose history of the ego of every scenario (sg_pose_history): where the ego and its k <= 32 nearest entities --
+        those nearest_entities(k, radius) selects at the current state, in its order -- were at the last n_samples <= 64 rows of
+        the pose record, `stride` rows apart, in the ego's current frame.  Returns (feat [R, 1 + k, n_samples, 6] float64, slots
+        [R, k] int32, count [R] int32): feat[:, 0] is the ego's own history, feat[:, i] neighbour i's; sample 0 is the current
+        state, sample j the record row j * stride steps back; per sample the longitudinal and lateral offset in the ego's
+        frame now, cos and sin of the heading then relative to the ego's now, the age of the sample in seconds, and 1.0 -- or
+        six zeros for a sample from before the episode began, for an entity that was not in the scene then, and behind the last
+        neighbour.  count = the candidates within the radius, -1 (and zeros) for an ego that is not in the scene, -2 (and
+        zeros) when the scenario's record filled up and it went on stepping.  Needs an engine created with record_capacity > 0
+        that covers the episode: the record takes record_capacity * 6 * R * EP * 8 bytes of device memory (EP: E rounded up to
+        64), and snapshots copy it.  Every kind of reset starts the history anew.  torch_out: torch tensors in HBM the kernel
+        writes directly (waited for, as in raster_map_observers)."""
+        return self._pose_history(self.lib.sg_pose_history, self.R, n_samples, stride, k, radius, torch_out)
+
+    def pose_history_observers(self, n_samples, stride=1, k=0, radius=float("inf"), torch_out=False):
+        """pose_history for every observer of set_observers (sg_pose_history_observers): (feat [n, 1 + k, n_samples, 6], slots
+        [n, k], count [n]); empty arrays when no observers are set."""
+        return self._pose_history(self.lib.sg_pose_history_observers, self._n_obs, n_samples, stride, k, radius, torch_out)
+
+    def pose_history_observers_queued(self, feat, slots, count, stride=1, radius=float("inf"), ordered=True):
+        """pose_history_observers into `feat` [n, 1 + k, n_samples, 6] float64, `slots` [n, k] int32 and `count` [n] int32,
+        contiguous torch tensors on this GPU (k and n_samples are read off feat), without any host wait: the kernel is queued on
+        the engine's stream behind the work of torch's current stream, and torch's current stream is ordered behind it
+        (ordered=False: the caller orders the two streams itself, ordered_with_torch).  Returns (feat, slots, count)."""
+        import torch
+
+        n, S, H = self._n_obs, int(feat.shape[1]), int(feat.shape[2])
+        assert feat.is_cuda and feat.dtype == torch.float64 and feat.is_contiguous() and tuple(feat.shape) == (n, S, H, L.HIST_NFEAT)
+        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and tuple(slots.shape) == (n, S - 1)
+        assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (n,)
+        with self.ordered_with_torch(ordered):
+            self._check(self.lib.sg_pose_history_observers(self.h, H, int(stride), S - 1, float(radius), feat.data_ptr() if feat.numel() else None,
+                                                           slots.data_ptr() if slots.numel() else None,
+                                                           count.data_ptr() if count.numel() else None, 1), "sg_pose_history_observers")
+        return feat, slots, count
 
     def set_lanes(self, networks):
         """sg_set_lanes: the lane centre lines of the networks of set_road_networks, which comes first (its net_of_scenario
@@ -983,6 +1025,7 @@ class RolloutEngine:
             present=present, dists=rows(L.F_DIST)[..., 0], coll=coll[..., 0] if v.row_words == 1 else coll,
             ctrl_state=rows(L.F_CTRL, 4), force=rows(L.F_FORCE, 2), t=scen["t"].copy(), prev_t=scen["prev_t"].copy(),
             done=scen["done"].astype(bool), n_steps=scen["n_steps"].copy(), noise_pos=scen["noise_pos"].copy(),
+            rec_rows=scen["rec_rows"].copy(),
         )
 
     METRIC_DTYPE = np.dtype([("ego_avg_speed", "f8"), ("ego_max_speed", "f8"), ("ego_distance_travelled", "f8"),

@@ -13,7 +13,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib as L
-from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, RangeScanSensor, RasterizedMapSensor,
+from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, NearestEntitiesSensor, PoseHistorySensor, RangeScanSensor, RasterizedMapSensor,
                     SurfaceScanSensor, _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
@@ -300,7 +300,7 @@ class BatchedScenarioGym:
         self.metrics = [list(self.metric_factory()) for _ in self.scenarios]
         self._invalidate()
         self._prev_state = None
-        # the observers of the batch: every map / look-ahead / nearest-entity / lane / range-scan / surface-scan sensor of a non-ego entity (inside a CombinedSensor too), so that
+        # the observers of the batch: every map / look-ahead / nearest-entity / pose-history / lane / range-scan / surface-scan sensor of a non-ego entity (inside a CombinedSensor too), so that
         # one device call per step and sensor configuration serves all of them; a sensor met later joins when it is first stepped
         self._observers, self._observer_of, self._observers_sent = [], {}, 0
 
@@ -314,7 +314,7 @@ class BatchedScenarioGym:
         for i, sc in enumerate(self.scenarios):
             for a in agents[i].values():
                 for s in leaves(getattr(a, "sensor", None)):
-                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, LaneSensor, RangeScanSensor, SurfaceScanSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
+                    if isinstance(s, (RasterizedMapSensor, FutureCollisionDetector, NearestEntitiesSensor, PoseHistorySensor, LaneSensor, RangeScanSensor, SurfaceScanSensor)) and s.entity is not sc.ego and s.entity in sc.entities:
                         self._observer(i, sc.entities.index(s.entity))
         self._reset_host_side()
 
@@ -383,6 +383,13 @@ class BatchedScenarioGym:
         """(feat [n, k, 8], slots [n, k], count [n]) of NearestEntitiesSensor."""
         call = self.engine.nearest_entities_observers if observers else self.engine.nearest_entities
         return self._cached(("near", observers, k, radius), lambda: call(k, radius), observers=observers)
+
+    def _pose_history(self, observers: bool, n_samples: int, stride: int, k: int, radius: float):
+        """(feat [n, 1 + k, n_samples, 6], slots [n, k], count [n]) of PoseHistorySensor; the device reads the pose record."""
+        if not self.record:
+            raise RuntimeError("pose_history needs BatchedScenarioGym(record=True)")
+        call = self.engine.pose_history_observers if observers else self.engine.pose_history
+        return self._cached(("hist", observers, n_samples, stride, k, radius), lambda: call(n_samples, stride, k, radius), observers=observers)
 
     def _range_scan(self, observers: bool, n_rays: int, angle0: float, dangle: Optional[float], max_range: float):
         """(feat [n, n_rays, 2], slots [n, n_rays], hits [n]) of RangeScanSensor."""

@@ -60,6 +60,21 @@ class NearestEntitiesObservation(SingleEntityObservation):
 
 
 @dataclass
+class PoseHistoryObservation(SingleEntityObservation):
+    """The pose-history observation (no counterpart in the reference): `history` [n_samples, 6] -- where the entity itself was
+    at the last n_samples rows of the pose record, `stride` rows apart, in its current frame: per sample the longitudinal and
+    lateral offset, cos and sin of the heading then relative to the heading now, the age of the sample in seconds and 1.0, or
+    six zeros for a sample that does not exist (before the episode began, or the entity was not in the scene then); sample 0 is
+    the current state.  `history_neighbours`, the nearest entities as NearestEntitiesObservation lists them (under a name of
+    its own, so that both keep their lists in a CombinedSensor), and `neighbour_histories` [k, n_samples, 6], their rows in the
+    same frame; rows behind the last neighbour are zero."""
+
+    history: np.ndarray
+    history_neighbours: list
+    neighbour_histories: np.ndarray
+
+
+@dataclass
 class LaneObservation(SingleEntityObservation):
     """The lane-frame vector observation (no counterpart in the reference): `lanes`, the lanes of the scenario's road network
     whose centre lines are nearest to the entity, within the sensor's radius, by ascending (squared distance, position in

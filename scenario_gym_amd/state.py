@@ -220,6 +220,20 @@ class State:
         ents = self._scenario.entities
         return [ents[j] for j in slots[row] if j >= 0], feat[row].copy()
 
+    def pose_history(self, n_samples: int = 8, stride: int = 1, k: int = 0, radius: float = float("inf"),
+                     entity: Optional[Entity] = None):
+        """PoseHistorySensor(entity, n_samples, stride, k, radius) at the current state, computed on the device from the pose
+        record (sg_pose_history; needs the gym's record=True): (history [n_samples, 6], neighbours, neighbour_histories
+        [k, n_samples, 6]) -- where `entity` (any entity of the scenario, default the ego) and the at most k entities
+        nearest_entities(k, radius) lists were at the last n_samples record rows, `stride` rows apart, in the entity's current
+        frame: per sample the longitudinal and lateral offset, cos and sin of the relative heading, the age in seconds and 1.0;
+        six zeros for a sample from before the episode began, for an entity that was not in `poses` then, and behind the last
+        neighbour.  (zeros, [], zeros) for an entity that is not in `poses`."""
+        observers, row = self._sensor_row(entity)
+        feat, slots, _ = self._gym._pose_history(observers, int(n_samples), int(stride), int(k), float(radius))
+        ents = self._scenario.entities
+        return feat[row, 0].copy(), [ents[j] for j in slots[row] if j >= 0], feat[row, 1:].copy()
+
     def range_scan(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0,
                    entity: Optional[Entity] = None):
         """RangeScanSensor(entity, n_rays, angle0, dangle, max_range) at the current state, computed on the device: (ranges

@@ -53,7 +53,8 @@ class VectorScenarioEnv:
                  auto_reset: bool = True, torch_obs: bool = False, device: int = 0,
                  drivers: Optional[Sequence[Sequence[int]]] = None, driver_status: bool = True,
                  traffic: Optional[Sequence[Sequence[int]]] = None, traffic_params=None,
-                 driver_progress: Optional[float] = None, device_tick: bool = False, driver_ttc: Optional[float] = None):
+                 driver_progress: Optional[float] = None, device_tick: bool = False, driver_ttc: Optional[float] = None,
+                 driver_history: Optional[dict] = None):
         """drivers: per environment the entity indices (positions in scenarios[i].entities) the policy drives, each with a
         VehicleController(max_steer, max_accel); None: the ego of every environment, one action per environment.
         driver_status: with a driver list, every step also reports the episode status of every driver (sg_entity_status_observers)
@@ -82,7 +83,19 @@ class VectorScenarioEnv:
         sg_time_to_collision_observers for the drivers on the state the returned `obs` describes -- after an auto-reset, unlike
         driver_flags -- and reset() leaves the same two in `reset_info`.  numpy arrays, or with torch_obs tensors in HBM; with
         device_tick the call is queued behind the tick and nothing crosses PCIe (an observer list of the caller's own that differs
-        from the driver list is swapped around the call, and each swap waits for the stream).  Not part of driver_reward."""
+        from the driver list is swapped around the call, and each swap waits for the stream).  Not part of driver_reward.
+        driver_history: None, or dict(samples=H, stride=s, k=k, radius=r) (stride 1, k 0 and radius inf unless given) for a pose
+        history per driver (needs `drivers`, and "max_length" among the terminal conditions, which bounds an episode): every
+        reset() and step() reports driver_history [n_drivers, 1 + k, H, 6], driver_history_slots [n_drivers, k] and
+        driver_history_count [n_drivers], the rows of sg_pose_history_observers for the drivers -- where each driver and its k
+        nearest entities were at the last H ticks, s ticks apart, in the driver's current frame -- on the state the returned
+        `obs` describes, behind an auto-reset as driver_ttc is: a new episode starts with one valid sample.  Delivered and
+        queued as driver_ttc is.  The engine then keeps a pose record of the longest episode of the batch, rows = the steps at
+        which max_length ends it + the reset row (+ one step of slack for the rounding of the clock), which costs rows * 6 * R *
+        EP * 8 bytes of device memory (EP: the entities per environment rounded up to 64) and is copied by save_state.  (A
+        ring-shaped record would cut that to H * s rows, but it would change every stepping kernel.)  An environment that goes
+        on stepping past its end (device_tick with auto_reset=False) overruns the record: its rows are zero and its count -2
+        until it is reset.  Not part of driver_reward."""
         self.scenarios = list(scenarios)
         self.terminal_conditions = list(terminal_conditions) if terminal_conditions is not None else \
             ["max_length", "ego_collision", "ego_off_road"]
@@ -98,6 +111,17 @@ class VectorScenarioEnv:
         self.driver_ttc = None if driver_ttc is None else float(driver_ttc)
         if self.driver_ttc is not None and drivers is None:
             raise ValueError("driver_ttc: needs a driver list (drivers=...)")
+        self.driver_history = None
+        if driver_history is not None:
+            if drivers is None:
+                raise ValueError("driver_history: needs a driver list (drivers=...)")
+            if "max_length" not in self.terminal_conditions:
+                raise ValueError('driver_history: needs "max_length" among the terminal conditions (it bounds the pose record)')
+            unknown = set(driver_history) - {"samples", "stride", "k", "radius"}
+            if unknown or "samples" not in driver_history:
+                raise ValueError("driver_history: dict(samples=H, stride=1, k=0, radius=inf)")
+            self.driver_history = (int(driver_history["samples"]), int(driver_history.get("stride", 1)), int(driver_history.get("k", 0)),
+                                   float(driver_history.get("radius", float("inf"))))
         self.reset_info = {}
         self.device_tick = bool(device_tick)
         if self.device_tick and (drivers is None or not torch_obs):
@@ -139,8 +163,14 @@ class VectorScenarioEnv:
                 packed.ctrl[int(i) * packed.n_entities + int(k)] = agent.controller.ctrl_row()
         self.n_envs = packed.n_scenarios
         self._ego = np.array([sc.entities.index(sc.ego) for sc in self.scenarios], np.int64)
+        record_rows = 0
+        if self.driver_history is not None:
+            # max_length ends an episode behind the first step n >= 1 with t0 + n * dt + dt > length (check_terminal on the
+            # device): n = max(1, floor((length - t0) / dt)); one more for the rounding of the summed clock, one for the reset row
+            longest = float(np.max(np.asarray(packed.length, np.float64) - np.asarray(packed.t0, np.float64)))
+            record_rows = max(1, int(np.floor(max(longest, 0.0) / float(timestep)))) + 2
         self.engine = RolloutEngine(packed.n_scenarios, packed.n_entities, timestep=timestep,
-                                    terminal_conditions=self.terminal_conditions, device=device)
+                                    terminal_conditions=self.terminal_conditions, device=device, record_capacity=record_rows)
         self.engine.upload(packed)
         self.engine.set_road_networks(*shared_polygon_arrays(self.scenarios))
         self._lanes_set = False  # the lane centre lines go down when a lane observation is first asked for
@@ -201,7 +231,7 @@ class VectorScenarioEnv:
         self.engine.reset()
         self.done[:] = False
         self._route_s0 = None
-        self.reset_info = self._driver_ttc_info()
+        self.reset_info = {**self._driver_ttc_info(), **self._driver_history_info()}
         return self._observe()
 
     def save_state(self):
@@ -229,7 +259,7 @@ class VectorScenarioEnv:
                 saved = token.route_s0 if token.route_s0 is not None else (np.zeros(self.n_drivers), np.zeros(self.n_drivers, bool))
                 self._route_s0[0][md] = saved[0][md]
                 self._route_s0[1][md] = saved[1][md]
-        self.reset_info = self._driver_ttc_info()
+        self.reset_info = {**self._driver_ttc_info(), **self._driver_history_info()}
         return self._observe()
 
     def step(self, actions):
@@ -311,6 +341,7 @@ class VectorScenarioEnv:
             if self._route_s0 is not None:  # a new episode: its first tick has no previous arclength
                 self._route_s0[1][done[self._drv_env]] = False
         info.update(self._driver_ttc_info())  # (the state the observation describes: behind the auto-reset)
+        info.update(self._driver_history_info())
         return self._observe(), reward, done, info
 
     def _step_device(self, actions):
@@ -331,7 +362,7 @@ class VectorScenarioEnv:
             v = self.engine.tick_drivers(actions.contiguous(), terminal_mask=self._mask, auto_reset=self.auto_reset,
                                          w_progress=self.driver_progress or 0.0, ordered=False)
             obs = self.engine.raster_map_observers_queued(self._dev_obs, self._codes, self.width, self.height, self.n, self.n, ordered=False)
-            ttc = self._driver_ttc_info(queued=True)
+            ttc = {**self._driver_ttc_info(queued=True), **self._driver_history_info(queued=True)}
         info = {"terminal_flags": v["term_flags"], "episode_return": v["ep_return"][:nd], "episode_length": v["ep_length"], **ttc}
         if self.driver_status and nd:
             info.update(driver_flags=v["drv_flags"][:nd], driver_info=v["drv_info"][:nd], driver_feat=v["drv_feat"][:nd],
@@ -358,6 +389,28 @@ class VectorScenarioEnv:
             call = lambda: self.engine.time_to_collision_observers(self.driver_ttc, torch_out=self.torch_obs)  # noqa: E731
         feat, info = self._driver_call(call)
         return {"driver_ttc": feat, "driver_ttc_info": info}
+
+    def _driver_history_info(self, queued=False):
+        """driver_history=dict(...): {driver_history [n_drivers, 1 + k, H, 6], driver_history_slots [n_drivers, k],
+        driver_history_count [n_drivers]} of the drivers at the current state (sg_pose_history_observers), else {}.  queued
+        (device_tick, inside its ordered_with_torch block): into tensors the environment keeps, on the engine's stream with no
+        host wait."""
+        if self.driver_history is None or not self.n_drivers:
+            return {}
+        H, stride, k, radius = self.driver_history
+        if queued:
+            if getattr(self, "_dev_hist", None) is None:
+                import torch
+
+                dev = self._dev_obs.device
+                self._dev_hist = (torch.empty((self.n_drivers, 1 + k, H, L.HIST_NFEAT), dtype=torch.float64, device=dev),
+                                  torch.empty((self.n_drivers, k), dtype=torch.int32, device=dev),
+                                  torch.empty((self.n_drivers,), dtype=torch.int32, device=dev))
+            call = lambda: self.engine.pose_history_observers_queued(*self._dev_hist, stride, radius, ordered=False)  # noqa: E731
+        else:
+            call = lambda: self.engine.pose_history_observers(H, stride, k, radius, torch_out=self.torch_obs)  # noqa: E731
+        feat, slots, count = self._driver_call(call)
+        return {"driver_history": feat, "driver_history_slots": slots, "driver_history_count": count}
 
     def _driver_status(self):
         """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays."""
@@ -440,6 +493,12 @@ class VectorScenarioEnv:
         """The vector observation of the ego of every environment at the current state (sg_nearest_entities): (feat [R, k, 8],
         slots [R, k] positions in scenarios[i].entities or -1, count [R]).  torch_obs: torch tensors in HBM; else numpy arrays."""
         return self.engine.nearest_entities(k, radius, torch_out=self.torch_obs)
+
+    def pose_history(self, n_samples: int = 8, stride: int = 1, k: int = 0, radius: float = float("inf")):
+        """The pose history of the ego of every environment at the current state (sg_pose_history): (feat [R, 1 + k, n_samples, 6],
+        slots [R, k] positions in scenarios[i].entities or -1, count [R]: RolloutEngine.pose_history).  Needs the pose record
+        that driver_history=... makes the engine keep.  torch_obs: torch tensors in HBM; else numpy arrays."""
+        return self.engine.pose_history(n_samples, stride, k, radius, torch_out=self.torch_obs)
 
     def observe_entities_nearest(self, k: int = 8, radius: float = float("inf")):
         """The vector observation of every observer of set_observers at the current state (sg_nearest_entities_observers):
