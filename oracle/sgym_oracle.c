@@ -507,6 +507,20 @@ int sgo_quads_intersect(const double *A, const double *B)
     return 1;
 }
 
+/* A box with a NaN corner (a pedestrian whose pose the social force's 0 / 0 left undefined) is in nobody's list and its own
+ * list is empty: tree.query(g, predicate="intersects") of detect_geom_collisions compares envelopes and then evaluates the
+ * predicate, and every ordered comparison with a NaN bound or coordinate is false, so nothing is found for such a box and no
+ * query finds it (with NaN in x the envelope is null outright; with NaN in y alone it is not, and the comparisons decide).
+ * Reasoned from the library's envelope and predicate code, not run against the reference.  Without this test the restatement
+ * below would do the opposite: its envelope test looks for a comparison that EXCLUDES and its separating-axis test for an axis
+ * that SEPARATES, so a NaN box would overlap every present entity. */
+static int corners_have_nan(const double *a)
+{
+    for (int i = 0; i < 8; ++i)
+        if (a[i] != a[i]) return 1;
+    return 0;
+}
+
 static int corners_equal(const double *a, const double *b)
 {
     for (int i = 0; i < 8; ++i)
@@ -802,9 +816,9 @@ static void detect_collisions(int E, int W, const uint8_t *present, const double
             if (present[j] && corners_equal(cor + (size_t)i * 8, cor + (size_t)j * 8)) last[i] = j;
     }
     for (int i = 0; i < E; ++i) {
-        if (!present[i]) continue;
+        if (!present[i] || corners_have_nan(cor + (size_t)i * 8)) continue;
         for (int j = 0; j < E; ++j) {
-            if (j == i || !present[j]) continue;
+            if (j == i || !present[j] || corners_have_nan(cor + (size_t)j * 8)) continue;
             const double *a = aabb + (size_t)i * 4, *b = aabb + (size_t)j * 4;
             if (a[2] < b[0] || b[2] < a[0] || a[3] < b[1] || b[3] < a[1]) continue; /* STRtree envelope */
             if (corners_equal(cor + (size_t)i * 8, cor + (size_t)j * 8)) continue;  /* g != g_prime */

@@ -136,7 +136,7 @@ __device__ __forceinline__ void tile_collisions_from(const TileCentre &C, bool p
             L.sx[sl] = sx;
             L.sy[sl] = sy;
             L.ss[sl] = stp * stp;
-            insane = present & !(crowd_sane(x, 0x1p400) & crowd_sane(y, 0x1p400) & crowd_sane(sx, 0x1p20) & crowd_sane(sy, 0x1p20) &
+            insane = present & !(crowd_sane_coord(x) & crowd_sane_coord(y) & crowd_sane(sx, 0x1p20) & crowd_sane(sy, 0x1p20) &
                                  (stp < 0x1p20));
         }
     }

@@ -230,10 +230,12 @@ __device__ __forceinline__ void ped_pairs_balanced(const Params &p, LDS &L, int 
 // are replaced by GUARDS that are established once per step for the whole tile (crowd_sane, voted in tile_collisions) and
 // once per launch for the parameters (crowd_params_ok), plus four exponent compares per pair.  Why that suffices, for a pair
 // that is ACTIVE (inside the radius rule, so |r| <= radius * (1 + 1e-9) < 2^21); inactive pairs are masked, garbage is fine:
-//   guards: every coordinate and every product stp * o of a present pedestrian is 0 or has magnitude in [2^-800, 2^400)
-//           (coordinates) / [2^-800, 2^20) (products); radius < 2^20; sigma, |cos_sight| in [2^-100, 2^100] (cos_sight may be
-//           0); V / sigma <= 2^100.  So rx, ry, qx, qy are 0 or multiples of 2^-852 of magnitude < 2^22: safe numerators of
-//           RecipDiv (zero, or |a| in [2^-959, 2^961)).
+//   guards: every coordinate of a present pedestrian is +0 or has magnitude in [2^-800, 2^400), every product stp * o is a zero
+//           or has magnitude in [2^-800, 2^20); radius < 2^20; sigma, |cos_sight| in [2^-100, 2^100] (cos_sight may be
+//           0); V / sigma <= 2^100.  So rx, ry, qx, qy are +0 or multiples of 2^-852 of magnitude < 2^22: safe numerators of
+//           RecipDiv (+0, or |a| in [2^-959, 2^961)).  Never -0, which RecipDiv::div would turn into +0: a difference x - y is
+//           -0 only for x = -0 and y = +0, so rx = px - ox needs the coordinate px = -0 (refused by the guard) and
+//           qx = rx - stp * o needs rx = -0.
 //   checks: the arguments of the first three square roots are >= 2^-100 (else `bad`): then rn >= 2^-50, qn >= 1e-10,
 //           b >= 2^-51 are safe denominators, 1 / b <= 2^51, k1 <= 2^72, |rep| <= 2^173, every sqrt argument is inside
 //           [2^-700, 2^1000) where the bare rsq + Goldschmidt core equals the compiler's sqrt (FastArith::sqrt); the argument
@@ -287,11 +289,17 @@ __device__ __forceinline__ bool crowd_params_ok(const sg_social_force &sf)
            __builtin_fabs(k2s) <= 0x1p100 && sf.ped_attract_C == 0.0 && sf.sight_weight > 0.0 && sf.sight_weight_use != 0.0;
 }
 
-// the per-entity guard of crowd_pair: c = coordinate / product of a present pedestrian
+// the per-entity guard of crowd_pair: v = a product stp * o of a present pedestrian
 __device__ __forceinline__ bool crowd_sane(double v, double hi_bound)
 {
     const double a = __builtin_fabs(v);
     return (v == 0.0) | ((a >= 0x1p-800) & (a < hi_bound));
+}
+// ... and v = one of its coordinates: of the two zeros only +0 (see above)
+__device__ __forceinline__ bool crowd_sane_coord(double v)
+{
+    const double a = __builtin_fabs(v);
+    return (__double_as_longlong(v) == 0) | ((a >= 0x1p-800) & (a < 0x1p400));
 }
 
 // (rx, ry) = owner - neighbour.  d2: the squared distance of the radius rule (sg_in_radius: dx*dx + dy*dy, and
