@@ -137,6 +137,20 @@ class SgEvent(C.Structure):
                 ("type", C.c_int32), ("reserved", C.c_int32)]
 
 
+# the pairs sg_<stem> / sg_<stem>_observers of obs_table.KINDS: what lies between the handle and outputs_device -- the arguments,
+# then a pointer per output
+_I, _D, _P = C.c_int32, C.c_double, C.c_void_p
+OBSERVATION_ARGTYPES = {
+    "nearest_entities": (_I, _D, _P, _P, _P),
+    "pose_history": (_I, _I, _I, _D, _P, _P, _P),
+    "lane_observation": (_I, _I, _D, _D, _P, _P, _P),
+    "range_scan": (_I, _D, _D, _D, _P, _P, _P),
+    "surface_scan": (_I, _P, _I, _D, _D, _D, _I, _I, _P, _P, _P),
+    "entity_status": (_P, _P, _P),
+    "route_observation": (_I, _D, _P, _P),
+    "time_to_collision": (_D, _P, _P),
+}
+
 _lib = None
 
 
@@ -249,30 +263,15 @@ def load():
     lib.sg_set_observers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sg_raster_map_observers.argtypes = [H, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_future_collision_observers.argtypes = [H, C.c_double, C.c_int32, C.c_void_p, C.c_int32]
-    lib.sg_nearest_entities.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_nearest_entities_observers.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_pose_history.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_pose_history_observers.argtypes = lib.sg_pose_history.argtypes
     lib.sg_set_lanes.argtypes = [H, C.POINTER(SgLanes)]
-    lib.sg_lane_observation.argtypes = [H, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_lane_observation_observers.argtypes = lib.sg_lane_observation.argtypes
-    lib.sg_range_scan.argtypes = [H, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_range_scan_observers.argtypes = lib.sg_range_scan.argtypes
-    lib.sg_entity_status.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_entity_status_observers.argtypes = lib.sg_entity_status.argtypes
     lib.sg_set_drivers.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sg_step_drivers.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_set_driver_policy.argtypes = [H, C.POINTER(SgDriverPolicy)]
     lib.sg_driver_policy_actions.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     lib.sg_step_drivers_policy.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32]
     lib.sg_set_routes.argtypes = [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.sg_route_observation.argtypes = [H, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_route_observation_observers.argtypes = lib.sg_route_observation.argtypes
-    lib.sg_time_to_collision.argtypes = [H, C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_time_to_collision_observers.argtypes = lib.sg_time_to_collision.argtypes
-    lib.sg_surface_scan.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int32]
-    lib.sg_surface_scan_observers.argtypes = lib.sg_surface_scan.argtypes
+    for stem, args in OBSERVATION_ARGTYPES.items():
+        getattr(lib, "sg_" + stem).argtypes = getattr(lib, f"sg_{stem}_observers").argtypes = [H, *args, C.c_int32]
     lib.sg_reset_scenarios_device.argtypes = [H, C.c_void_p]
     lib.sg_tick_drivers.argtypes = [H, C.c_void_p, C.c_int32, C.POINTER(SgEpisodeRules), C.POINTER(SgEpisodeView)]
     lib.sg_snapshot_create.argtypes = [H, C.POINTER(C.c_void_p)]

@@ -7,6 +7,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
+from .obs_table import KINDS
 
 TERMINAL_BITS = {"max_length": L.TERM_MAX_LENGTH, "collision": L.TERM_COLLISION,
                  "ego_collision": L.TERM_EGO_COLLISION, "ego_off_road": L.TERM_EGO_OFF_ROAD}
@@ -274,16 +275,17 @@ class RolloutEngine:
             raise RuntimeError(f"{what} failed ({rc}): {self.lib.sg_last_error(self.h).decode()}")
 
     def _outputs(self, torch_out, *specs):
-        """One uninitialised output array per (shape, dtype name): numpy arrays, or with torch_out torch tensors in HBM that
-        the handle's stream may write at once.  Returns (arrays, their addresses for the C side -- None for an empty array)."""
+        """One uninitialised output array per (shape, numpy dtype name, torch dtype name): numpy arrays, or with torch_out torch
+        tensors in HBM that the handle's stream may write at once.  Returns (arrays, their addresses for the C side -- None for an
+        empty array)."""
         if torch_out:
             import torch
 
             dev = f"cuda:{self.cfg.device}"
-            arrs = tuple(torch.empty(shape, dtype=getattr(torch, dt), device=dev) for shape, dt in specs)
+            arrs = tuple(torch.empty(shape, dtype=getattr(torch, dt), device=dev) for shape, _, dt in specs)
             torch.cuda.current_stream(arrs[0].device).synchronize()  # (the allocator's work before the handle's stream writes)
             return arrs, tuple(a.data_ptr() if a.numel() else None for a in arrs)
-        arrs = tuple(np.empty(shape, dt) for shape, dt in specs)
+        arrs = tuple(np.empty(shape, dt) for shape, dt, _ in specs)
         return arrs, tuple(a.ctypes.data if a.size else None for a in arrs)
 
     def _actions(self, actions, n, rows=None, wait=True):
@@ -312,6 +314,26 @@ class RolloutEngine:
         if torch_out:
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
         return outs
+
+    def _observation(self, kind, observers, user_args, torch_out=False, into=None, ordered=True):
+        """Every observation of obs_table.KINDS, for the egos or the observers of set_observers, from its row: the C call of the
+        pair, the arguments as the row casts them, the outputs the row describes.  Delivered as numpy arrays, with torch_out as
+        torch tensors in HBM (waited for: _observe), or into the caller's tensors `into` -- checked against the row: on this
+        GPU, dtype, contiguous, shape -- queued under ordered_with_torch(ordered) with no host wait."""
+        row = KINDS[kind]
+        call = getattr(self.lib, f"sg_{row.stem}_observers" if observers else f"sg_{row.stem}")
+        args, _keep = row.args(*user_args)
+        specs = row.outs(self._n_obs if observers else self.R, *args)
+        if into is None:
+            return self._observe(call, args, torch_out, *specs)
+        import torch
+
+        assert len(into) == len(specs)
+        for t, (shape, _, dt) in zip(into, specs):
+            assert t.is_cuda and t.device.index == self.cfg.device and t.dtype == getattr(torch, dt) and t.is_contiguous() and tuple(t.shape) == shape
+        with self.ordered_with_torch(ordered):
+            self._check(call(self.h, *args, *(t.data_ptr() if t.numel() else None for t in into), 1), call.__name__)
+        return tuple(into)
 
     def _entity_list(self, scenario, slot, who):
         """The (scenario, slot) pairs of a list call: ((the int32 arrays), n, their addresses -- None for an empty list)."""
@@ -432,7 +454,8 @@ class RolloutEngine:
         sine of the heading error, arclength along the path, remaining path).  Empty arrays when no policy is set.  torch_out:
         torch tensors in HBM the kernel writes directly (waited for, as in entity_status)."""
         m = getattr(self, "_n_pol", 0)
-        return self._observe(self.lib.sg_driver_policy_actions, (), torch_out, ((m, 2), "float64"), ((m, L.DP_NINFO), "int32"), ((m, L.DP_NFEAT), "float64"))
+        return self._observe(self.lib.sg_driver_policy_actions, (), torch_out, ((m, 2), "float64", "float64"), ((m, L.DP_NINFO), "int32", "int32"),
+                             ((m, L.DP_NFEAT), "float64", "float64"))
 
     def step_drivers_policy(self, actions=None, n=1):
         """step_drivers with the built-in policy in the loop (sg_step_drivers_policy): actions [n, n_drivers, 2] as for
@@ -585,7 +608,7 @@ class RolloutEngine:
 
         if torch_out:
             (count, geoms, layers), (p_count, p_geoms, p_layers) = self._outputs(
-                True, ((R, E), "int32"), ((R, E, int(cap)), "int32"), ((R, E), "int32"))
+                True, ((R, E), "int32", "int32"), ((R, E, int(cap)), "int32", "int32"), ((R, E), "uint32", "int32"))
             call(int(cap), p_count, p_geoms, p_layers)
             self._check(self.lib.sg_synchronize(self.h), "sg_synchronize")
             return count, geoms, layers
@@ -596,7 +619,7 @@ class RolloutEngine:
         addresses); asked once more with cap = count.max() when some list did not fit."""
         cap = int(cap)
         while True:
-            (count, geoms, layers), (_, p_geoms, _) = self._outputs(False, (shape, "int32"), (shape + (cap,), "int32"), (shape, "uint32"))
+            (count, geoms, layers), (_, p_geoms, _) = self._outputs(False, (shape, "int32", "int32"), (shape + (cap,), "int32", "int32"), (shape, "uint32", "int32"))
             call(cap, count.ctypes.data, p_geoms, layers.ctypes.data)  # (count is never null: no points is a valid question)
             if count.size == 0 or int(count.max()) <= cap:
                 return count, geoms, layers
@@ -615,7 +638,8 @@ class RolloutEngine:
         return self._road_query((len(xy),), cap, call)
 
     def set_observers(self, scenario, slot):
-        """sg_set_observers: the observers of raster_map_observers / future_collision_observers / nearest_entities_observers / pose_history_observers / lane_observation_observers / range_scan_observers / entity_status_observers / route_observation(observers=True) / time_to_collision_observers -- observer k is entity slot
+        """sg_set_observers: the observers of every `*_observers` call and of route_observation(observers=True) (the rows of
+        obs_table.KINDS) -- observer k is entity slot
         slot[k] of scenario scenario[k], any entity of its scenario (the reference builds its sensors per entity:
         sensor/map.py:136-271, sensor/common.py:60-106).  Duplicates and any order are fine; an empty list clears it; upload()
         forgets it.  A refused list (index out of range, a slot without an entity) leaves the engine without observers."""
@@ -629,34 +653,21 @@ class RolloutEngine:
         (sg_raster_map_observers): bool [n, n_layers, nh, nw]; layers as in raster_map.  An observer that is not in the scene
         gets zeros.  torch_out: a torch uint8 tensor in HBM the kernel writes directly; this wrapper waits for the kernel
         (sg_synchronize) before it returns, so the tensor can be used on any torch stream -- the C call itself does not wait."""
-        lay = np.ascontiguousarray(layers, np.int32)
-        (out,) = self._observe(self.lib.sg_raster_map_observers, (float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data), torch_out,
-                               ((self._n_obs, len(lay), int(nh), int(nw)), "uint8"))
+        (out,) = self._observation("raster", True, (layers, width, height, nw, nh), torch_out)
         return out if torch_out else out.astype(bool)
 
     def raster_map_observers_queued(self, out, layers, width=20.0, height=20.0, nw=20, nh=20, ordered=True):
         """raster_map_observers into `out`, a contiguous torch uint8 tensor [n, n_layers, nh, nw] on this GPU, without any host
         wait: the kernel is queued on the engine's stream behind the work of torch's current stream, and torch's current stream
         is ordered behind it (ordered=False: the caller orders the two streams itself, ordered_with_torch).  Returns `out`."""
-        import torch
-
-        lay = np.ascontiguousarray(layers, np.int32)
-        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (self._n_obs, len(lay), int(nh), int(nw))
-        with self.ordered_with_torch(ordered):
-            self._check(self.lib.sg_raster_map_observers(self.h, float(width), float(height), int(nw), int(nh), len(lay), lay.ctypes.data,
-                                                         out.data_ptr() if out.numel() else None, 1), "sg_raster_map_observers")
-        return out
+        return self._observation("raster", True, (layers, width, height, nw, nh), into=(out,), ordered=ordered)[0]
 
     def future_collision_observers(self, horizon=5.0, n_samples=10, torch_out=False):
         """FutureCollisionDetector._step (sensor/common.py:87-106) for every observer of set_observers at the current time of
         its scenario (sg_future_collision_observers): bool [n], or with torch_out a torch uint8 tensor in HBM (waited for, as
         in raster_map_observers)."""
-        (out,) = self._observe(self.lib.sg_future_collision_observers, (float(horizon), int(n_samples)), torch_out, ((self._n_obs,), "uint8"))
+        (out,) = self._observation("future", True, (horizon, n_samples), torch_out)
         return out if torch_out else out.astype(bool)
-
-    def _nearest(self, call, n, k, radius, torch_out):
-        k = int(k)
-        return self._observe(call, (k, float(radius)), torch_out, ((n, k, 8), "float64"), ((n, k), "int32"), ((n,), "int32"))
 
     def nearest_entities(self, k, radius=float("inf"), torch_out=False):
         """The vector observation of the ego of every scenario (sg_nearest_entities): the k <= 32 nearest other entities that are
@@ -665,17 +676,12 @@ class RolloutEngine:
         and sin of the relative heading, the relative velocity in that frame, box length and width; slots -1 and features 0
         behind the last neighbour; count = the candidates within the radius (it may exceed k), -1 for an ego that is not in the
         scene.  torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
-        return self._nearest(self.lib.sg_nearest_entities, self.R, k, radius, torch_out)
+        return self._observation("nearest", False, (k, radius), torch_out)
 
     def nearest_entities_observers(self, k, radius=float("inf"), torch_out=False):
         """nearest_entities for every observer of set_observers (sg_nearest_entities_observers): (feat [n, k, 8], slots [n, k],
         count [n]); empty arrays when no observers are set."""
-        return self._nearest(self.lib.sg_nearest_entities_observers, self._n_obs, k, radius, torch_out)
-
-    def _pose_history(self, call, n, n_samples, stride, k, radius, torch_out):
-        H, k = int(n_samples), int(k)
-        return self._observe(call, (H, int(stride), k, float(radius)), torch_out, ((n, 1 + max(k, 0), max(H, 0), L.HIST_NFEAT), "float64"),
-                             ((n, max(k, 0)), "int32"), ((n,), "int32"))
+        return self._observation("nearest", True, (k, radius), torch_out)
 
     def pose_history(self, n_samples, stride=1, k=0, radius=float("inf"), torch_out=False):
         """The pose history of the ego of every scenario (sg_pose_history): where the ego and its k <= 32 nearest entities --
@@ -690,29 +696,19 @@ class RolloutEngine:
         that covers the episode: the record takes record_capacity * 6 * R * EP * 8 bytes of device memory (EP: E rounded up to
         64), and snapshots copy it.  Every kind of reset starts the history anew.  torch_out: torch tensors in HBM the kernel
         writes directly (waited for, as in raster_map_observers)."""
-        return self._pose_history(self.lib.sg_pose_history, self.R, n_samples, stride, k, radius, torch_out)
+        return self._observation("pose_history", False, (n_samples, stride, k, radius), torch_out)
 
     def pose_history_observers(self, n_samples, stride=1, k=0, radius=float("inf"), torch_out=False):
         """pose_history for every observer of set_observers (sg_pose_history_observers): (feat [n, 1 + k, n_samples, 6], slots
         [n, k], count [n]); empty arrays when no observers are set."""
-        return self._pose_history(self.lib.sg_pose_history_observers, self._n_obs, n_samples, stride, k, radius, torch_out)
+        return self._observation("pose_history", True, (n_samples, stride, k, radius), torch_out)
 
     def pose_history_observers_queued(self, feat, slots, count, stride=1, radius=float("inf"), ordered=True):
         """pose_history_observers into `feat` [n, 1 + k, n_samples, 6] float64, `slots` [n, k] int32 and `count` [n] int32,
         contiguous torch tensors on this GPU (k and n_samples are read off feat), without any host wait: the kernel is queued on
         the engine's stream behind the work of torch's current stream, and torch's current stream is ordered behind it
         (ordered=False: the caller orders the two streams itself, ordered_with_torch).  Returns (feat, slots, count)."""
-        import torch
-
-        n, S, H = self._n_obs, int(feat.shape[1]), int(feat.shape[2])
-        assert feat.is_cuda and feat.dtype == torch.float64 and feat.is_contiguous() and tuple(feat.shape) == (n, S, H, L.HIST_NFEAT)
-        assert slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous() and tuple(slots.shape) == (n, S - 1)
-        assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (n,)
-        with self.ordered_with_torch(ordered):
-            self._check(self.lib.sg_pose_history_observers(self.h, H, int(stride), S - 1, float(radius), feat.data_ptr() if feat.numel() else None,
-                                                           slots.data_ptr() if slots.numel() else None,
-                                                           count.data_ptr() if count.numel() else None, 1), "sg_pose_history_observers")
-        return feat, slots, count
+        return self._observation("pose_history", True, (feat.shape[2], stride, feat.shape[1] - 1, radius), into=(feat, slots, count), ordered=ordered)
 
     def set_lanes(self, networks):
         """sg_set_lanes: the lane centre lines of the networks of set_road_networks, which comes first (its net_of_scenario
@@ -736,11 +732,6 @@ class RolloutEngine:
         st = L.SgLanes(len(networks), p(lane_off), p(pt_off), p(pts), p(succ_off), p(succ))
         self._check(self.lib.sg_set_lanes(self.h, C.byref(st)), "sg_set_lanes")
 
-    def _lane_observation(self, call, n, k, n_ahead, spacing, radius, torch_out):
-        k, n_ahead = int(k), int(n_ahead)
-        return self._observe(call, (k, n_ahead, float(spacing), float(radius)), torch_out,
-                             ((n, k, 6 + 2 * max(n_ahead, 0)), "float64"), ((n, k), "int32"), ((n,), "int32"))
-
     def lane_observation(self, k=3, n_ahead=4, spacing=2.0, radius=float("inf"), torch_out=False):
         """The lane-frame vector observation of the ego of every scenario (sg_lane_observation): the k <= 8 lanes of the
         scenario's network whose centre lines are nearest to the ego and within `radius` (inclusive), by ascending (squared
@@ -751,18 +742,12 @@ class RolloutEngine:
         point where they end.  lanes: indices into `RoadNetwork.lanes`, -1 and zero features behind the last; count = the lanes
         within the radius (it may exceed k), -1 for an ego that is not in the scene, 0 without a network or before set_lanes.
         torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
-        return self._lane_observation(self.lib.sg_lane_observation, self.R, k, n_ahead, spacing, radius, torch_out)
+        return self._observation("lane", False, (k, n_ahead, spacing, radius), torch_out)
 
     def lane_observation_observers(self, k=3, n_ahead=4, spacing=2.0, radius=float("inf"), torch_out=False):
         """lane_observation for every observer of set_observers (sg_lane_observation_observers): (feat [n, k, 6 + 2 * n_ahead],
         lanes [n, k], count [n]); empty arrays when no observers are set."""
-        return self._lane_observation(self.lib.sg_lane_observation_observers, self._n_obs, k, n_ahead, spacing, radius, torch_out)
-
-    def _range_scan(self, call, n, n_rays, angle0, dangle, max_range, torch_out):
-        n_rays = int(n_rays)
-        dangle = 2.0 * np.pi / max(n_rays, 1) if dangle is None else float(dangle)  # (n_rays < 1 is the library's to refuse)
-        return self._observe(call, (n_rays, float(angle0), dangle, float(max_range)), torch_out,
-                             ((n, max(n_rays, 0), 2), "float64"), ((n, max(n_rays, 0)), "int32"), ((n,), "int32"))
+        return self._observation("lane", True, (k, n_ahead, spacing, radius), torch_out)
 
     def range_scan(self, n_rays=64, angle0=-np.pi, dangle=None, max_range=100.0, torch_out=False):
         """The range scan of the ego of every scenario (sg_range_scan): n_rays <= 1024 beams from the ego's pose point, beam b at
@@ -773,22 +758,12 @@ class RolloutEngine:
         relative to the ego's along the beam, negative when it closes, 0 without a hit; slots: the hit entity or -1; hits: the
         beams that hit something, -1 for an ego that is not in the scene (features 0, slots -1).  torch_out: torch tensors in
         HBM the kernel writes directly (waited for, as in raster_map_observers)."""
-        return self._range_scan(self.lib.sg_range_scan, self.R, n_rays, angle0, dangle, max_range, torch_out)
+        return self._observation("range_scan", False, (n_rays, angle0, dangle, max_range), torch_out)
 
     def range_scan_observers(self, n_rays=64, angle0=-np.pi, dangle=None, max_range=100.0, torch_out=False):
         """range_scan for every observer of set_observers (sg_range_scan_observers): (feat [n, n_rays, 2], slots [n, n_rays],
         hits [n]); empty arrays when no observers are set."""
-        return self._range_scan(self.lib.sg_range_scan_observers, self._n_obs, n_rays, angle0, dangle, max_range, torch_out)
-
-    def _surface_scan(self, call, n, layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out):
-        from .road_network import surface_layer_bits
-
-        lay = np.ascontiguousarray(surface_layer_bits(layers), np.int32)
-        n_rays, nl = int(n_rays), len(lay)
-        dangle = 2.0 * np.pi / max(n_rays, 1) if dangle is None else float(dangle)  # (n_rays < 1 is the library's to refuse)
-        cells = (n, nl, max(n_rays, 0))
-        return self._observe(call, (nl, lay.ctypes.data if nl else None, n_rays, float(angle0), dangle, float(step), int(n_steps), int(n_refine)),
-                             torch_out, (cells, "float64"), (cells, "uint8"), ((n, nl), "int32"))
+        return self._observation("range_scan", True, (n_rays, angle0, dangle, max_range), torch_out)
 
     def surface_scan(self, layers, n_rays=64, angle0=-np.pi, dangle=None, step=0.5, n_steps=64, n_refine=16, torch_out=False):
         """The surface scan of the ego of every scenario (sg_surface_scan; set_road_networks comes first): n_rays <= 1024 beams
@@ -802,16 +777,12 @@ class RolloutEngine:
         SURF_HIT the beam changed side, SURF_INSIDE the pose point is on the layer; hits: the beams that changed side, -1 for
         an ego that is not in the scene (ranges and flags 0).  Without a road network every range is n_steps * step.
         torch_out: torch tensors in HBM the kernel writes directly (waited for, as in raster_map_observers)."""
-        return self._surface_scan(self.lib.sg_surface_scan, self.R, layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out)
+        return self._observation("surface_scan", False, (layers, n_rays, angle0, dangle, step, n_steps, n_refine), torch_out)
 
     def surface_scan_observers(self, layers, n_rays=64, angle0=-np.pi, dangle=None, step=0.5, n_steps=64, n_refine=16, torch_out=False):
         """surface_scan for every observer of set_observers (sg_surface_scan_observers): (ranges [n, n_layers, n_rays], flags
         [n, n_layers, n_rays], hits [n, n_layers]); empty arrays when no observers are set."""
-        return self._surface_scan(self.lib.sg_surface_scan_observers, self._n_obs, layers, n_rays, angle0, dangle, step, n_steps, n_refine,
-                                  torch_out)
-
-    def _entity_status(self, call, n, torch_out):
-        return self._observe(call, (), torch_out, ((n,), "int32" if torch_out else "uint32"), ((n, L.ST_NINFO), "int32"), ((n, L.ST_NFEAT), "float64"))
+        return self._observation("surface_scan", True, (layers, n_rays, angle0, dangle, step, n_steps, n_refine), torch_out)
 
     def entity_status(self, torch_out=False):
         """The episode status of the ego of every scenario (sg_entity_status): what a per-agent reward and termination need in
@@ -825,12 +796,12 @@ class RolloutEngine:
         when they collide, inf when it is alone.  An ego that is not in the scene: ST_OFF_ROAD alone, info -1, feat 0.
         torch_out: torch tensors in HBM the kernel writes directly (flags as int32 bit patterns; waited for, as in
         raster_map_observers)."""
-        return self._entity_status(self.lib.sg_entity_status, self.R, torch_out)
+        return self._observation("entity_status", False, (), torch_out)
 
     def entity_status_observers(self, torch_out=False):
         """entity_status for every observer of set_observers (sg_entity_status_observers): (flags [n], info [n, 4], feat
         [n, 3]); empty arrays when no observers are set."""
-        return self._entity_status(self.lib.sg_entity_status_observers, self._n_obs, torch_out)
+        return self._observation("entity_status", True, (), torch_out)
 
     def set_routes(self, scenario, slot, paths):
         """sg_set_routes: where entities are supposed to go.  Route j belongs to entity slot[j] of scenario scenario[j] (any
@@ -854,13 +825,7 @@ class RolloutEngine:
         segments; features 5 and up are zero then), and where the current time lies in the recording (0 within, -1 before its
         first knot, 1 after its last).  An entity that is not in the scene: info -1, -1 and zeros.  device: torch tensors in
         HBM the kernel writes directly (waited for, as in entity_status)."""
-        n_ahead = int(n_ahead)
-        n = self._n_obs if observers else self.R
-        call = self.lib.sg_route_observation_observers if observers else self.lib.sg_route_observation
-        return self._observe(call, (n_ahead, float(spacing)), device, ((n, L.RT_NFEAT + 2 * max(n_ahead, 0)), "float64"), ((n, L.RT_NINFO), "int32"))
-
-    def _time_to_collision(self, call, n, horizon, torch_out):
-        return self._observe(call, (float(horizon),), torch_out, ((n, L.TTC_NFEAT), "float64"), ((n, L.TTC_NINFO), "int32"))
+        return self._observation("route", observers, (n_ahead, spacing), device)
 
     def time_to_collision(self, horizon=float("inf"), torch_out=False):
         """The time to collision of the ego of every scenario (sg_time_to_collision): when its bounding box first touches the box
@@ -872,26 +837,19 @@ class RolloutEngine:
         first -- 0 the ego's front or rear, 1 its side, 2 / 3 the other box's front or rear / side, -1 for an overlap that exists
         already and without a threat.  An ego that is not in the scene: info -1, feat 0.  torch_out: torch tensors in HBM the
         kernel writes directly (waited for, as in entity_status)."""
-        return self._time_to_collision(self.lib.sg_time_to_collision, self.R, horizon, torch_out)
+        return self._observation("ttc", False, (horizon,), torch_out)
 
     def time_to_collision_observers(self, horizon=float("inf"), torch_out=False):
         """time_to_collision for every observer of set_observers (sg_time_to_collision_observers): (feat [n, 4], info [n, 3]);
         empty arrays when no observers are set."""
-        return self._time_to_collision(self.lib.sg_time_to_collision_observers, self._n_obs, horizon, torch_out)
+        return self._observation("ttc", True, (horizon,), torch_out)
 
     def time_to_collision_observers_queued(self, feat, info, horizon=float("inf"), ordered=True):
         """time_to_collision_observers into `feat` [n, 4] float64 and `info` [n, 3] int32, contiguous torch tensors on this GPU,
         without any host wait: the kernel is queued on the engine's stream behind the work of torch's current stream, and
         torch's current stream is ordered behind it (ordered=False: the caller orders the two streams itself,
         ordered_with_torch).  Returns (feat, info)."""
-        import torch
-
-        assert feat.is_cuda and feat.dtype == torch.float64 and feat.is_contiguous() and tuple(feat.shape) == (self._n_obs, L.TTC_NFEAT)
-        assert info.is_cuda and info.dtype == torch.int32 and info.is_contiguous() and tuple(info.shape) == (self._n_obs, L.TTC_NINFO)
-        with self.ordered_with_torch(ordered):
-            self._check(self.lib.sg_time_to_collision_observers(self.h, float(horizon), feat.data_ptr() if feat.numel() else None,
-                                                                info.data_ptr() if info.numel() else None, 1), "sg_time_to_collision_observers")
-        return feat, info
+        return self._observation("ttc", True, (horizon,), into=(feat, info), ordered=ordered)
 
     def raster_map(self, layers, width=20.0, height=20.0, nw=20, nh=20):
         """RasterizedMapSensor._step (sensor/map.py:136-149) around the ego of every scenario: bool [R, n_layers, nh, nw];

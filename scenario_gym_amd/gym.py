@@ -17,6 +17,7 @@ from .agent import (CombinedSensor, FutureCollisionDetector, LaneSensor, Nearest
                     SurfaceScanSensor, _create_agent)
 from .engine import TERMINAL_BITS, RolloutEngine
 from .metrics import RSS, CollisionPointMetric, Metric, RSSDistances, _DeviceMetric
+from .obs_table import KINDS, blank, public_call
 from .packing import pack_policy_drivers, pack_scenarios
 from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
@@ -375,45 +376,32 @@ class BatchedScenarioGym:
         return self._cached(("map", observers, codes, width, height, nw, nh), lambda: call(codes, width, height, nw, nh),
                             observers=observers, roads=any(codes))
 
-    def _future(self, observers: bool, horizon: float, n_samples: int):
-        call = self.engine.future_collision_observers if observers else self.engine.future_collision
-        return self._cached(("fut", observers, horizon, n_samples), lambda: call(horizon, n_samples), observers=observers)
+    def _observation(self, kind: str, observers: bool, *args):
+        """The outputs of observation `kind` (a row of obs_table.KINDS) with the arguments `args` at the current state, through
+        the engine's public method of the row; what the row needs on the device goes down first."""
+        needs = KINDS[kind].needs
+        if "record" in needs and not self.record:
+            raise RuntimeError(f"{KINDS[kind].ego} needs BatchedScenarioGym(record=True)")
 
-    def _nearest(self, observers: bool, k: int, radius: float):
-        """(feat [n, k, 8], slots [n, k], count [n]) of NearestEntitiesSensor."""
-        call = self.engine.nearest_entities_observers if observers else self.engine.nearest_entities
-        return self._cached(("near", observers, k, radius), lambda: call(k, radius), observers=observers)
+        def compute():
+            if "lanes" in needs:
+                self._set_lanes()
+            if "routes" in needs:
+                self._set_routes()
+            return public_call(self.engine, kind, observers, args)
 
-    def _pose_history(self, observers: bool, n_samples: int, stride: int, k: int, radius: float):
-        """(feat [n, 1 + k, n_samples, 6], slots [n, k], count [n]) of PoseHistorySensor; the device reads the pose record."""
-        if not self.record:
-            raise RuntimeError("pose_history needs BatchedScenarioGym(record=True)")
-        call = self.engine.pose_history_observers if observers else self.engine.pose_history
-        return self._cached(("hist", observers, n_samples, stride, k, radius), lambda: call(n_samples, stride, k, radius), observers=observers)
+        return self._cached((kind, observers, *args), compute, observers=observers, roads="roads" in needs)
 
-    def _range_scan(self, observers: bool, n_rays: int, angle0: float, dangle: Optional[float], max_range: float):
-        """(feat [n, n_rays, 2], slots [n, n_rays], hits [n]) of RangeScanSensor."""
-        call = self.engine.range_scan_observers if observers else self.engine.range_scan
-        return self._cached(("scan", observers, n_rays, angle0, dangle, max_range), lambda: call(n_rays, angle0, dangle, max_range),
-                            observers=observers)
-
-    def _surface_scan(self, observers: bool, bits, n_rays: int, angle0: float, dangle: Optional[float], step: float, n_steps: int, n_refine: int):
-        """(ranges [n, n_layers, n_rays], flags [n, n_layers, n_rays], hits [n, n_layers]) of SurfaceScanSensor; bits: LAYER_* bits."""
-        call = self.engine.surface_scan_observers if observers else self.engine.surface_scan
-        return self._cached(("surf", observers, bits, n_rays, angle0, dangle, step, n_steps, n_refine),
-                            lambda: call(bits, n_rays, angle0, dangle, step, n_steps, n_refine), observers=observers, roads=True)
-
-    def _entity_status(self, observers: bool):
-        """(flags [n], info [n, 4], feat [n, 3]) of State.entity_status."""
-        call = self.engine.entity_status_observers if observers else self.engine.entity_status
-        return self._cached(("status", observers), call, observers=observers, roads=True)
+    def _surface_scan(self, observers: bool, bits, *args):
+        """_observation("surface_scan", ...) under the name State.surface_scan asks by (a stand-in gym of the tests has it alone)."""
+        return self._observation("surface_scan", observers, bits, *args)
 
     def entity_status(self):
         """State.entity_status for every entity slot of the batch: (flags [R, E] ST_* bits, info [R, E, 4], feat [R, E, 3]) as
         RolloutEngine.entity_status gives them for the egos -- one device call with every slot an observer; a padding slot
         reads as an entity that is not in the scene.  The gym's own observer list is put back afterwards."""
         R, E = self.engine.R, self.engine.E
-        flags, info, feat = np.full((R, E), L.ST_OFF_ROAD, np.uint32), np.full((R, E, L.ST_NINFO), -1, np.int32), np.zeros((R, E, L.ST_NFEAT))
+        flags, info, feat = blank("entity_status", (R, E), (L.ST_OFF_ROAD, -1, 0.0))
         self._set_road_networks()
         r, e, (flags[r, e], info[r, e], feat[r, e]) = self._every_slot(self.engine.entity_status_observers)
         return flags, info, feat
@@ -433,17 +421,12 @@ class BatchedScenarioGym:
             else:
                 self.engine.set_observers([], [])
 
-    def _time_to_collision(self, observers: bool, horizon: float):
-        """(feat [n, 4], info [n, 3]) of State.time_to_collision."""
-        call = self.engine.time_to_collision_observers if observers else self.engine.time_to_collision
-        return self._cached(("ttc", observers, horizon), lambda: call(horizon), observers=observers)
-
     def time_to_collision(self, horizon: float = float("inf")):
         """State.time_to_collision for every entity slot of the batch: (feat [R, E, 4], info [R, E, 3]) as
         RolloutEngine.time_to_collision gives them for the egos -- one device call with every slot an observer; a padding slot
         reads as an entity that is not in the scene.  The gym's own observer list is put back afterwards."""
         R, E = self.engine.R, self.engine.E
-        feat, info = np.zeros((R, E, L.TTC_NFEAT)), np.full((R, E, L.TTC_NINFO), -1, np.int32)
+        feat, info = blank("ttc", (R, E), (0.0, -1), horizon)
         r, e, (feat[r, e], info[r, e]) = self._every_slot(lambda: self.engine.time_to_collision_observers(horizon))
         return feat, info
 
@@ -454,16 +437,6 @@ class BatchedScenarioGym:
         if not self._lanes_set and self.scenarios:
             self.engine.set_lanes(shared_lane_arrays(self.scenarios)[0])
             self._lanes_set = True
-
-    def _lane_observation(self, observers: bool, k: int, n_ahead: int, spacing: float, radius: float):
-        """(feat [n, k, 6 + 2 * n_ahead], lanes [n, k], count [n]) of LaneSensor."""
-        call = self.engine.lane_observation_observers if observers else self.engine.lane_observation
-
-        def compute():
-            self._set_lanes()
-            return call(k, n_ahead, spacing, radius)
-
-        return self._cached(("lane", observers, k, n_ahead, spacing, radius), compute, observers=observers)
 
     def set_routes(self, paths=None):
         """The routes of the route observation (State.route_observation): paths[i] = {entity index: polyline [n_pts, 2]} for
@@ -485,14 +458,6 @@ class BatchedScenarioGym:
         slot = [int(k) for d in paths for k in d]
         self.engine.set_routes(scen, slot, [q for d in paths for q in d.values()])
         self._routes_set = True
-
-    def _route_observation(self, observers: bool, n_ahead: int, spacing: float):
-        """(feat [n, 11 + 2 * n_ahead], info [n, 2]) of State.route_observation."""
-        def compute():
-            self._set_routes()
-            return self.engine.route_observation(n_ahead, spacing, observers=observers)
-
-        return self._cached(("route", observers, n_ahead, spacing), compute, observers=observers)
 
     def _raster(self, width, height, nw, nh):
         return self._cached(("raster", width, height, nw, nh), lambda: self.engine.raster_entities(width, height, nw, nh))

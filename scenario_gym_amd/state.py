@@ -196,7 +196,7 @@ class State:
         """FutureCollisionDetector(entity, horizon) at the current time (sensor/common.py:87-106), computed on the device;
         entity: any entity of the scenario (default: the ego)."""
         observers, row = self._sensor_row(entity)
-        return bool(self._gym._future(observers, float(horizon), int(n_samples))[row])
+        return bool(self._gym._observation("future", observers, float(horizon), int(n_samples))[row])
 
     def entity_raster(self, width: float = 20.0, height: float = 20.0, nw: int = 20, nh: int = 20) -> np.ndarray:
         """RasterizedMapSensor "entity" layer around the ego (sensor/map.py:120-192), computed on the device: bool [nh, nw]."""
@@ -216,7 +216,7 @@ class State:
         by ascending (squared distance, position in the scenario), and their [k, 8] feature rows in the entity's frame (zeros
         behind the last).  ([], zeros) for an entity that is not in `poses`."""
         observers, row = self._sensor_row(entity)
-        feat, slots, _ = self._gym._nearest(observers, int(k), float(radius))
+        feat, slots, _ = self._gym._observation("nearest", observers, int(k), float(radius))
         ents = self._scenario.entities
         return [ents[j] for j in slots[row] if j >= 0], feat[row].copy()
 
@@ -230,7 +230,7 @@ class State:
         six zeros for a sample from before the episode began, for an entity that was not in `poses` then, and behind the last
         neighbour.  (zeros, [], zeros) for an entity that is not in `poses`."""
         observers, row = self._sensor_row(entity)
-        feat, slots, _ = self._gym._pose_history(observers, int(n_samples), int(stride), int(k), float(radius))
+        feat, slots, _ = self._gym._observation("pose_history", observers, int(n_samples), int(stride), int(k), float(radius))
         ents = self._scenario.entities
         return feat[row, 0].copy(), [ents[j] for j in slots[row] if j >= 0], feat[row, 1:].copy()
 
@@ -242,8 +242,8 @@ class State:
         first other entity's bounding box within max_range (max_range without a hit), the rate at which it changes, and that
         entity (None without a hit).  (zeros, zeros, Nones) for an entity that is not in `poses`."""
         observers, row = self._sensor_row(entity)
-        feat, slots, _ = self._gym._range_scan(observers, int(n_rays), float(angle0), None if dangle is None else float(dangle),
-                                               float(max_range))
+        feat, slots, _ = self._gym._observation("range_scan", observers, int(n_rays), float(angle0), None if dangle is None else float(dangle),
+                                                float(max_range))
         ents = self._scenario.entities
         return feat[row, :, 0].copy(), feat[row, :, 1].copy(), [ents[j] if j >= 0 else None for j in slots[row]]
 
@@ -268,7 +268,7 @@ class State:
         off the road, box corners on the road, the road geometry classes under it, the nearest other box and the clearance
         to it, speed and distance travelled."""
         observers, row = self._sensor_row(entity)
-        flags, info, feat = self._gym._entity_status(observers)
+        flags, info, feat = self._gym._observation("entity_status", observers)
         ents = self._scenario.entities
         entity = self._scenario.ego if entity is None else entity
         f, near = int(flags[row]), int(info[row, 3])
@@ -286,7 +286,7 @@ class State:
         `RoadNetwork.lanes`), and their [k, 6 + 2 * n_ahead] feature rows (zeros behind the last).  ([], zeros) for an entity
         that is not in `poses` and for a scenario without a road network."""
         observers, row = self._sensor_row(entity)
-        feat, idx, _ = self._gym._lane_observation(observers, int(k), int(n_ahead), float(spacing), float(radius))
+        feat, idx, _ = self._gym._observation("lane", observers, int(k), int(n_ahead), float(spacing), float(radius))
         rn = self._scenario.road_network
         lanes = rn.lanes if rn is not None else []
         return [lanes[j] for j in idx[row] if j >= 0], feat[row].copy()
@@ -297,7 +297,7 @@ class State:
         the entity is from where its own recording has it, and where it is along its route with n_ahead points of the route
         ahead.  The routes are those of ScenarioGym.set_routes; by default every entity's own recorded trajectory."""
         observers, row = self._sensor_row(entity)
-        feat, info = self._gym._route_observation(observers, int(n_ahead), float(spacing))
+        feat, info = self._gym._observation("route", observers, int(n_ahead), float(spacing))
         entity = self._scenario.ego if entity is None else entity
         present = bool(self._s()["present"][self._i, self._scenario.entities.index(entity)])
         return RouteObservation(entity, present, feat[row].copy(), int(info[row, 0]), int(info[row, 1]))
@@ -308,7 +308,7 @@ class State:
         of another entity within `horizon` seconds if both keep their velocity and heading, until when, that entity, its
         relative velocity in the entity's frame, how many entities are met, and the face that meets first."""
         observers, row = self._sensor_row(entity)
-        feat, info = self._gym._time_to_collision(observers, float(horizon))
+        feat, info = self._gym._observation("ttc", observers, float(horizon))
         ents = self._scenario.entities
         threat = int(info[row, 0])
         return TimeToCollision(float(feat[row, 0]), float(feat[row, 1]), feat[row, 2:4].copy(), ents[threat] if threat >= 0 else None,

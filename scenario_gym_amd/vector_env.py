@@ -31,6 +31,7 @@ import numpy as np
 from . import _lib as L
 from .agent import ExternalVehicleAgent, ReplayTrajectoryAgent
 from .engine import RolloutEngine, terminal_mask
+from .obs_table import KINDS, public_call
 from .packing import pack_scenarios
 from .road_network import LAYER_CODES, shared_lane_arrays, shared_polygon_arrays
 from .scenario import Scenario
@@ -122,6 +123,14 @@ class VectorScenarioEnv:
                 raise ValueError("driver_history: dict(samples=H, stride=1, k=0, radius=inf)")
             self.driver_history = (int(driver_history["samples"]), int(driver_history.get("stride", 1)), int(driver_history.get("k", 0)),
                                    float(driver_history.get("radius", float("inf"))))
+        # the configured driver observations: (kind, arguments, those its *_observers_queued form takes behind the tensors, the
+        # `info` keys of its outputs); the tensors device_tick queues them into, by kind
+        self._driver_obs, self._dev_bufs = [], {}
+        if self.driver_ttc is not None:
+            self._driver_obs.append(("ttc", (self.driver_ttc,), (self.driver_ttc,), ("driver_ttc", "driver_ttc_info")))
+        if self.driver_history is not None:
+            self._driver_obs.append(("pose_history", self.driver_history, self.driver_history[1::2],  # (stride, radius: the tensors tell the rest)
+                                     ("driver_history", "driver_history_slots", "driver_history_count")))
         self.reset_info = {}
         self.device_tick = bool(device_tick)
         if self.device_tick and (drivers is None or not torch_obs):
@@ -231,7 +240,7 @@ class VectorScenarioEnv:
         self.engine.reset()
         self.done[:] = False
         self._route_s0 = None
-        self.reset_info = {**self._driver_ttc_info(), **self._driver_history_info()}
+        self.reset_info = self._driver_obs_info()
         return self._observe()
 
     def save_state(self):
@@ -259,7 +268,7 @@ class VectorScenarioEnv:
                 saved = token.route_s0 if token.route_s0 is not None else (np.zeros(self.n_drivers), np.zeros(self.n_drivers, bool))
                 self._route_s0[0][md] = saved[0][md]
                 self._route_s0[1][md] = saved[1][md]
-        self.reset_info = {**self._driver_ttc_info(), **self._driver_history_info()}
+        self.reset_info = self._driver_obs_info()
         return self._observe()
 
     def step(self, actions):
@@ -340,8 +349,7 @@ class VectorScenarioEnv:
             self.done = np.zeros(self.n_envs, bool)
             if self._route_s0 is not None:  # a new episode: its first tick has no previous arclength
                 self._route_s0[1][done[self._drv_env]] = False
-        info.update(self._driver_ttc_info())  # (the state the observation describes: behind the auto-reset)
-        info.update(self._driver_history_info())
+        info.update(self._driver_obs_info())  # (the state the observation describes: behind the auto-reset)
         return self._observe(), reward, done, info
 
     def _step_device(self, actions):
@@ -362,7 +370,7 @@ class VectorScenarioEnv:
             v = self.engine.tick_drivers(actions.contiguous(), terminal_mask=self._mask, auto_reset=self.auto_reset,
                                          w_progress=self.driver_progress or 0.0, ordered=False)
             obs = self.engine.raster_map_observers_queued(self._dev_obs, self._codes, self.width, self.height, self.n, self.n, ordered=False)
-            ttc = {**self._driver_ttc_info(queued=True), **self._driver_history_info(queued=True)}
+            ttc = self._driver_obs_info(queued=True)
         info = {"terminal_flags": v["term_flags"], "episode_return": v["ep_return"][:nd], "episode_length": v["ep_length"], **ttc}
         if self.driver_status and nd:
             info.update(driver_flags=v["drv_flags"][:nd], driver_info=v["drv_info"][:nd], driver_feat=v["drv_feat"][:nd],
@@ -371,46 +379,27 @@ class VectorScenarioEnv:
                 info.update(driver_route=v["drv_route"][:nd], driver_progress=v["drv_progress"][:nd])
         return obs, v["env_reward"], v["env_done"].view(torch.bool), info
 
-    def _driver_ttc_info(self, queued=False):
-        """driver_ttc=H: {driver_ttc [n_drivers, 4], driver_ttc_info [n_drivers, 3]} of the drivers at the current state
-        (sg_time_to_collision_observers), else {}.  queued (device_tick, inside its ordered_with_torch block): into tensors the
-        environment keeps, on the engine's stream with no host wait."""
-        if self.driver_ttc is None or not self.n_drivers:
-            return {}
-        if queued:
-            if getattr(self, "_dev_ttc", None) is None:
-                import torch
+    def _driver_obs_info(self, queued=False):
+        """The `info` entries of the configured driver observations (driver_ttc=H: driver_ttc [n_drivers, 4], driver_ttc_info
+        [n_drivers, 3], sg_time_to_collision_observers; driver_history=dict(...): driver_history [n_drivers, 1 + k, H, 6],
+        driver_history_slots [n_drivers, k], driver_history_count [n_drivers], sg_pose_history_observers) of the drivers at the
+        current state, in that order; {} without any.  queued (device_tick, inside its ordered_with_torch block): into tensors
+        the environment keeps, on the engine's stream with no host wait."""
+        out = {}
+        for kind, args, queued_args, keys in self._driver_obs if self.n_drivers else ():
+            if queued:
+                bufs = self._dev_bufs.get(kind)
+                if bufs is None:
+                    import torch
 
-                dev = self._dev_obs.device
-                self._dev_ttc = (torch.empty((self.n_drivers, L.TTC_NFEAT), dtype=torch.float64, device=dev),
-                                 torch.empty((self.n_drivers, L.TTC_NINFO), dtype=torch.int32, device=dev))
-            call = lambda: self.engine.time_to_collision_observers_queued(*self._dev_ttc, self.driver_ttc, ordered=False)  # noqa: E731
-        else:
-            call = lambda: self.engine.time_to_collision_observers(self.driver_ttc, torch_out=self.torch_obs)  # noqa: E731
-        feat, info = self._driver_call(call)
-        return {"driver_ttc": feat, "driver_ttc_info": info}
-
-    def _driver_history_info(self, queued=False):
-        """driver_history=dict(...): {driver_history [n_drivers, 1 + k, H, 6], driver_history_slots [n_drivers, k],
-        driver_history_count [n_drivers]} of the drivers at the current state (sg_pose_history_observers), else {}.  queued
-        (device_tick, inside its ordered_with_torch block): into tensors the environment keeps, on the engine's stream with no
-        host wait."""
-        if self.driver_history is None or not self.n_drivers:
-            return {}
-        H, stride, k, radius = self.driver_history
-        if queued:
-            if getattr(self, "_dev_hist", None) is None:
-                import torch
-
-                dev = self._dev_obs.device
-                self._dev_hist = (torch.empty((self.n_drivers, 1 + k, H, L.HIST_NFEAT), dtype=torch.float64, device=dev),
-                                  torch.empty((self.n_drivers, k), dtype=torch.int32, device=dev),
-                                  torch.empty((self.n_drivers,), dtype=torch.int32, device=dev))
-            call = lambda: self.engine.pose_history_observers_queued(*self._dev_hist, stride, radius, ordered=False)  # noqa: E731
-        else:
-            call = lambda: self.engine.pose_history_observers(H, stride, k, radius, torch_out=self.torch_obs)  # noqa: E731
-        feat, slots, count = self._driver_call(call)
-        return {"driver_history": feat, "driver_history_slots": slots, "driver_history_count": count}
+                    specs = KINDS[kind].outs(self.n_drivers, *KINDS[kind].args(*args)[0])
+                    bufs = self._dev_bufs[kind] = tuple(torch.empty(shape, dtype=getattr(torch, dt), device=self._dev_obs.device)
+                                                        for shape, _, dt in specs)
+                call = lambda: getattr(self.engine, KINDS[kind].observers + "_queued")(*bufs, *queued_args, ordered=False)  # noqa: E731
+            else:
+                call = lambda: public_call(self.engine, kind, True, args, torch_out=self.torch_obs)  # noqa: E731
+            out.update(zip(keys, self._driver_call(call)))
+        return out
 
     def _driver_status(self):
         """(flags [n_drivers], info [n_drivers, 4], feat [n_drivers, 3]) of the drivers at the current state, as numpy arrays."""
@@ -428,27 +417,35 @@ class VectorScenarioEnv:
             if not same:
                 self.engine.set_observers(self._obs_env, self._obs_slot)
 
+    def _observation(self, kind, observers, *args):
+        """Observation `kind` (a row of obs_table.KINDS) of the egos, or of the observers of set_observers with (env_of_observer
+        [n], slot [n]) behind its outputs; what the row needs on the device goes down first.  torch_obs: torch tensors in HBM."""
+        if "lanes" in KINDS[kind].needs:
+            self._set_lanes()
+        if "routes" in KINDS[kind].needs and not self._routes_set:
+            self.set_routes()
+        out = public_call(self.engine, kind, observers, args, torch_out=self.torch_obs)
+        return tuple(out) + self._observer_index(out[0]) if observers else out
+
     def status(self):
         """The episode status of the ego of every environment at the current state (sg_entity_status): (flags [R] ST_* bits, info
         [R, 4], feat [R, 3]: RolloutEngine.entity_status).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        return self.engine.entity_status(torch_out=self.torch_obs)
+        return self._observation("entity_status", False)
 
     def observe_entities_status(self):
         """The episode status of every observer of set_observers at the current state (sg_entity_status_observers): (flags [n],
         info [n, 4], feat [n, 3], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        out = self.engine.entity_status_observers(torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("entity_status", True)
 
     def time_to_collision(self, horizon: float = float("inf")):
         """The time to collision of the ego of every environment at the current state (sg_time_to_collision): (feat [R, 4], info
         [R, 3]: RolloutEngine.time_to_collision).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        return self.engine.time_to_collision(horizon, torch_out=self.torch_obs)
+        return self._observation("ttc", False, horizon)
 
     def time_to_collision_observers(self, horizon: float = float("inf")):
         """The time to collision of every observer of set_observers at the current state (sg_time_to_collision_observers): (feat
         [n, 4], info [n, 3], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        out = self.engine.time_to_collision_observers(horizon, torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("ttc", True, horizon)
 
     def road_info(self, cap: int = 32):
         """State.get_road_info_at_entity for the ego of every environment (sg_road_info): count [R], geoms [R, cap] indices
@@ -492,48 +489,45 @@ class VectorScenarioEnv:
     def nearest_entities(self, k: int = 8, radius: float = float("inf")):
         """The vector observation of the ego of every environment at the current state (sg_nearest_entities): (feat [R, k, 8],
         slots [R, k] positions in scenarios[i].entities or -1, count [R]).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        return self.engine.nearest_entities(k, radius, torch_out=self.torch_obs)
+        return self._observation("nearest", False, k, radius)
 
     def pose_history(self, n_samples: int = 8, stride: int = 1, k: int = 0, radius: float = float("inf")):
         """The pose history of the ego of every environment at the current state (sg_pose_history): (feat [R, 1 + k, n_samples, 6],
         slots [R, k] positions in scenarios[i].entities or -1, count [R]: RolloutEngine.pose_history).  Needs the pose record
         that driver_history=... makes the engine keep.  torch_obs: torch tensors in HBM; else numpy arrays."""
-        return self.engine.pose_history(n_samples, stride, k, radius, torch_out=self.torch_obs)
+        return self._observation("pose_history", False, n_samples, stride, k, radius)
 
     def observe_entities_nearest(self, k: int = 8, radius: float = float("inf")):
         """The vector observation of every observer of set_observers at the current state (sg_nearest_entities_observers):
         (feat [n, k, 8], slots [n, k], count [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else numpy
         arrays."""
-        out = self.engine.nearest_entities_observers(k, radius, torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("nearest", True, k, radius)
 
     def range_scan(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0):
         """The range scan of the ego of every environment at the current state (sg_range_scan): (feat [R, n_rays, 2] range and
         range rate per beam, slots [R, n_rays] positions in scenarios[i].entities or -1, hits [R]).  torch_obs: torch tensors in
         HBM; else numpy arrays."""
-        return self.engine.range_scan(n_rays, angle0, dangle, max_range, torch_out=self.torch_obs)
+        return self._observation("range_scan", False, n_rays, angle0, dangle, max_range)
 
     def observe_entities_ranges(self, n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None, max_range: float = 100.0):
         """The range scan of every observer of set_observers at the current state (sg_range_scan_observers): (feat
         [n, n_rays, 2], slots [n, n_rays], hits [n], env_of_observer [n], slot [n]).  torch_obs: torch tensors in HBM; else
         numpy arrays."""
-        out = self.engine.range_scan_observers(n_rays, angle0, dangle, max_range, torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("range_scan", True, n_rays, angle0, dangle, max_range)
 
     def surface_scan(self, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
                      step: float = 0.5, n_steps: int = 64, n_refine: int = 16):
         """The surface scan of the ego of every environment at the current state (sg_surface_scan): (ranges
         [R, n_layers, n_rays], flags [R, n_layers, n_rays] SURF_HIT / SURF_INSIDE, hits [R, n_layers]:
         RolloutEngine.surface_scan).  torch_obs: torch tensors in HBM; else numpy arrays."""
-        return self.engine.surface_scan(layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out=self.torch_obs)
+        return self._observation("surface_scan", False, layers, n_rays, angle0, dangle, step, n_steps, n_refine)
 
     def surface_scan_observers(self, layers=("driveable_surface",), n_rays: int = 64, angle0: float = -np.pi, dangle: Optional[float] = None,
                                step: float = 0.5, n_steps: int = 64, n_refine: int = 16):
         """The surface scan of every observer of set_observers at the current state (sg_surface_scan_observers): (ranges
         [n, n_layers, n_rays], flags [n, n_layers, n_rays], hits [n, n_layers], env_of_observer [n], slot [n]).  torch_obs:
         torch tensors in HBM; else numpy arrays."""
-        out = self.engine.surface_scan_observers(layers, n_rays, angle0, dangle, step, n_steps, n_refine, torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("surface_scan", True, layers, n_rays, angle0, dangle, step, n_steps, n_refine)
 
     def _set_lanes(self):
         if not self._lanes_set:
@@ -544,16 +538,13 @@ class VectorScenarioEnv:
         """The lane-frame vector observation of the ego of every environment at the current state (sg_lane_observation):
         (feat [R, k, 6 + 2 * n_ahead], lanes [R, k] positions in scenarios[i].road_network.lanes or -1, count [R]).  torch_obs:
         torch tensors in HBM; else numpy arrays."""
-        self._set_lanes()
-        return self.engine.lane_observation(k, n_ahead, spacing, radius, torch_out=self.torch_obs)
+        return self._observation("lane", False, k, n_ahead, spacing, radius)
 
     def observe_entities_lanes(self, k: int = 3, n_ahead: int = 4, spacing: float = 2.0, radius: float = float("inf")):
         """The lane-frame vector observation of every observer of set_observers at the current state
         (sg_lane_observation_observers): (feat [n, k, 6 + 2 * n_ahead], lanes [n, k], count [n], env_of_observer [n], slot [n]).
         torch_obs: torch tensors in HBM; else numpy arrays."""
-        self._set_lanes()
-        out = self.engine.lane_observation_observers(k, n_ahead, spacing, radius, torch_out=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("lane", True, k, n_ahead, spacing, radius)
 
     def set_routes(self, paths=None):
         """The routes of route_observation / observe_entities_routes and of the progress reward (sg_set_routes): paths[i] =
@@ -580,19 +571,14 @@ class VectorScenarioEnv:
         (sg_route_observation): (feat [R, 11 + 2 * n_ahead], info [R, 2]: RolloutEngine.route_observation).  The routes are those
         of set_routes (before any: its default); an ego without one has its route part zero.  torch_obs: torch tensors in HBM;
         else numpy arrays."""
-        if not self._routes_set:
-            self.set_routes()
-        return self.engine.route_observation(n_ahead, spacing, device=self.torch_obs)
+        return self._observation("route", False, n_ahead, spacing)
 
     def observe_entities_routes(self, n_ahead: int = 4, spacing: float = 2.0):
         """The route and recorded-track observation of every observer of set_observers at the current state
         (sg_route_observation_observers): (feat [n, 11 + 2 * n_ahead], info [n, 2], env_of_observer [n], slot [n]).  Before any
         set_routes every observer and driver gets its own recording as its route.  torch_obs: torch tensors in HBM; else numpy
         arrays."""
-        if not self._routes_set:
-            self.set_routes()
-        out = self.engine.route_observation(n_ahead, spacing, observers=True, device=self.torch_obs)
-        return tuple(out) + self._observer_index(out[0])
+        return self._observation("route", True, n_ahead, spacing)
 
     def close(self):
         self.engine.close()

@@ -36,6 +36,7 @@ def make_env(packed, per_scenario, device_tick):
     env._codes = [LAYER_CODES[l] for l in env.layers]
     env.height, env.width, env.n = 30.0, 30.0, N_PX
     env.auto_reset, env.torch_obs, env.driver_status, env.driver_progress, env.device_tick = True, True, True, 1.0, device_tick
+    env._driver_obs, env._dev_bufs = [], {}  # (no driver_ttc, no driver_history)
     env.n_envs = R
     env._drv_env = np.repeat(np.arange(R, dtype=np.int32), per_scenario)
     env._drv_slot = np.tile(np.arange(1, per_scenario + 1, dtype=np.int32), R)
