@@ -30,6 +30,7 @@ GENERATORS = {
     "make_golden_collision_types": ["collision_types"],
     "make_golden_inputs": ["inputs_xosc", "inputs_roads_1", "inputs_roads_2"],
     "make_golden_json": ["json", "elevation"],
+    "make_golden_knots": ["knots"],
     "make_golden_long": ["long"],
     "make_golden_mixed_peds": ["mixed_peds"],
     "make_golden_observers": ["observers"],
